@@ -2,15 +2,20 @@
 """Headline benchmark: greedy batch-1 decode of a Llama-2-7B-shaped model with
 Q4_B32T1A weights (BASELINE.json configs[1]) on N MI355X GPUs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one decoded token (one pass of the fused decode path over the whole
 model).  Weights are synthetic N(0,0.02) tensors quantised on the device with
 the reference rule (inferflow_amd/synth.py); the prompt is 16 random token ids.
-Rank 0 prints ONE JSON line.  Extra keys:
-  roofline      -- dominant kernel (fused W1/W3 GEMV): algorithmic bytes / HIP-event time
-  cpu_baseline  -- the oracle port of the same quantised decode path timed on the host
-                   cores (bounded sample; rank 0, N=1 only)
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps
+and prints the line.  --full adds the legs that take runs of their own (N=1 only):
+  roofline, kernels     -- per-kernel HIP-event timings; dominant kernel (fused W1/W3 GEMV):
+                           algorithmic bytes / HIP-event time
+  prefill_tok_s_by_prompt_len, decode_tok_s_by_context, batch_decode
+  cpu_baseline          -- the oracle port of the same quantised decode path timed on the host
+                           cores (bounded sample), and the reference's own CPU path
+--dump-outputs DIR writes what the timed call computed (tokens.npy: the ids of all K steps;
+logits.npy: the logits row of the last step, single-device runner) as float32 / float64.
 """
 import argparse
 import json
@@ -273,6 +278,15 @@ def reference_cpu_baseline_7b_width(n_tokens=16, layers=32, with_gpu=True):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def dump_outputs(d, tokens, logits=None):
+    """What the timed call returned, seeded inputs: two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "tokens.npy"), np.asarray(tokens, np.float64))
+    if logits is not None:
+        np.save(os.path.join(d, "logits.npy"), np.asarray(logits, np.float32))
+
+
 class Watchdog:
     """A hang in communicator setup or in a collective must not cost the whole scaling record: every rank watches its own
     progress and, when a phase overruns its limit, rank 0 prints ONE JSON line with an "error" key (the driver's contract)
@@ -356,6 +370,8 @@ def loopback_line(args):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     dog.disarm()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gen)
     ranks = eng.model_info("partition_ranks")
     eng.close()
     out = {"metric": "decode tokens/sec, %s batch=1 greedy (whole job)" % args.shape, "value": args.steps / wall, "unit": "tokens/s", "n_gpus": 1,
@@ -380,15 +396,20 @@ def main():
     ap.add_argument("--kv-dtype", default="f16", help="KV cache: f16 or q8 (configs[2] = --wdtype q3h --kv-dtype q8)")
     ap.add_argument("--groups", type=int, default=1, help="device groups (layer ranges) of the HYBRID partition; "
                     "gpus // groups ranks per group are tensor-parallel (default 1 = pure tensor parallelism)")
-    ap.add_argument("--prefill-lens", default="128,1024", help="extra prompt lengths whose prefill rate is reported (N=1 only)")
+    ap.add_argument("--full", action="store_true", help="also run the legs that take runs of their own (N=1 only): per-kernel "
+                    "timings + roofline, prefill by prompt length, decode by context, batched decode, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed call computed to DIR/<name>.npy")
+    ap.add_argument("--prefill-lens", default="128,1024", help="extra prompt lengths whose prefill rate is reported (--full, N=1 only)")
     ap.add_argument("--batch", type=int, default=8, help="also time dynamic-batching decode: B queries, one new token each per "
-                    "step (N=1 only; reported as batch_decode, never as value; 0 = skip)")
+                    "step (--full, N=1 only; reported as batch_decode, never as value; 0 = skip)")
     ap.add_argument("--loopback", type=int, default=0, help="R > 1: run the tensor-parallel partition with R ranks on ONE device "
                     "(the C++ InferenceEngine with devices = 0&0..., in-process loopback group instead of RCCL) and print its line; "
                     "a functional check of the N > 1 step logic on a one-GPU box, not a scaling number")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-tokens", type=int, default=0, help="CPU baseline sample size (0 = auto)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -535,6 +556,10 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        # the logits row of the last step: the single-device worker holds the whole row (tensor-parallel ranks hold slices)
+        logits = runner.worker.read_buffer("logits").view(np.float16) if isinstance(runner, parallel.SingleRunner) else None
+        dump_outputs(args.dump_outputs, toks, logits)
 
     tok_s = steps / wall
     n_avg = PROMPT_LEN + warmup + steps / 2.0
@@ -574,9 +599,11 @@ def main():
         "build_s": t_build,
         "last_tokens": [int(t) for t in toks[-4:]],
     }
+    # ---- everything below runs with --full only (N=1): legs with launches of their own, outside the timed region
+    full = args.full and world == 1 and not os.environ.get("IFA_FORCE_TP")
     # ---- roofline of the dominant kernel, timed live with HIP events on the worker's stream
     is_moe = bool(runner.shape.get("experts", 0))
-    if world == 1 and hasattr(runner, "export_host_tensors") and not os.environ.get("IFA_FORCE_TP") and not is_moe:
+    if full and hasattr(runner, "export_host_tensors") and not is_moe:
         s = runner.shape
         ffn_rows, d = s["ffn"], s["dim"]
         rb = dt.row_bytes                          # ALGORITHMIC bytes per row (the reference's block sizes; Q3H_B64T1: 32 per 64 weights)
@@ -623,7 +650,7 @@ def main():
                            "bytes_per_launch": ffn13_bytes, "streamed_bytes_per_launch": ffn13_streamed, "us_per_launch": us}
         out["kernels"] = per_kernel
     # ---- prefill rate at longer prompts (16 / 128 / 1024-token prompts), outside the timed decode region
-    if world == 1 and hasattr(runner, "worker") and not os.environ.get("IFA_FORCE_TP"):
+    if full and hasattr(runner, "worker"):
         pf = {}
         out["prefill_tok_s_first_call"] = PROMPT_LEN / prefill_s   # cold: code objects, scratch and KV pages touched for the first time
         for n in [PROMPT_LEN] + [n for n in prefill_lens if n != PROMPT_LEN]:
@@ -646,7 +673,7 @@ def main():
         out["prefill_gemm_route"] = "in-tree kernels only (csrc/ifa_gemm.hip: large-tile MFMA kernel above 128 tokens, four launches per layer); no vendor GEMM in the library"
     # ---- decode rate at a few hundred keys (secondary key, outside the timed region): the headline line sits at 21..41 keys, a served
     # query at hundreds; a real 16-step call after an n-token prompt (every layer's cache rows read cold, unlike a per-launch timing loop)
-    if world == 1 and hasattr(runner, "worker") and not os.environ.get("IFA_FORCE_TP") and not is_moe:
+    if full and hasattr(runner, "worker") and not is_moe:
         try:
             by_ctx = {}
             for n in (256, 450):
@@ -666,7 +693,7 @@ def main():
             out["decode_tok_s_by_context"] = {"error": str(e)[:200]}
     # ---- dynamic batching: B queries with their own KV caches, one decode step appends one token to each (the reference's
     # InferenceEngine::Infer over several queries, inference_engine.cc:1300-1406); outside the timed headline region
-    if world == 1 and args.batch > 1 and hasattr(runner, "worker") and not os.environ.get("IFA_FORCE_TP"):
+    if full and args.batch > 1 and hasattr(runner, "worker"):
         try:
             B, wk = args.batch, runner.worker
             wk.kv_slots(B)
@@ -699,7 +726,7 @@ def main():
         except Exception as e:      # an extra leg: never at the expense of the headline line
             out["batch_decode"] = {"batch": args.batch, "error": repr(e)}
     # ---- CPU baseline (oracle port) on a bounded sample
-    if world == 1 and not args.no_cpu_baseline and not os.environ.get("IFA_FORCE_TP") and not is_moe:
+    if full and not args.no_cpu_baseline and not is_moe:
         try:
             flags = "-O2 (the parity object)"
             try:                                        # the port built for this host's cores; the parity object when that fails
@@ -742,7 +769,7 @@ def main():
     # ---- the REFERENCE's own CPU path (oracle/_ref/ifa_ref_engine: /root/reference sources compiled by oracle/Makefile,
     # travels prebuilt) on configs[0] -- the stories15M-shaped llama2.c checkpoint of bin/llm_inference.tiny.ini, the case
     # the reference itself runs on CPU -- with this engine on the very same checkpoint next to it
-    if world == 1 and not args.no_cpu_baseline and not os.environ.get("IFA_FORCE_TP"):
+    if full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline_reference"] = reference_cpu_baseline()
         except Exception as e:
@@ -807,4 +834,12 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    try:
+        main()
+    finally:
+        # an exception that skips main's own destroy_process_group() must not leave the process group's watchdog thread
+        # running into interpreter teardown: it throws there and the process aborts instead of reporting the error
+        if "torch.distributed" in sys.modules:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                dist.destroy_process_group()

@@ -27,6 +27,26 @@ def test_single_gpu_line_has_the_contract_keys():
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in j, k
     assert j["n_gpus"] == 1 and j["steps"] == 8 and j["value"] > 0 and j["config"]["fallbacks"] == []
+    assert "roofline" not in j and "kernels" not in j and "decode_tok_s_by_context" not in j     # --full legs only
+
+
+def test_full_adds_the_legs_of_their_own():
+    j, _ = _run({}, "--full")
+    assert j["value"] > 0 and j["roofline"]["achieved"] > 0 and set(j["kernels"]) == {"qkv", "attn", "wo", "ffn13", "w2", "lm_head"}
+    assert list(j["prefill_tok_s_by_prompt_len"]) == ["16"]        # (--prefill-lens "": the prompt's own length only)
+
+
+def test_dump_outputs_are_what_the_timed_call_returned(tmp_path):
+    """--dump-outputs: the ids of the timed steps and the logits row of the last step (the id it chose is a maximum of it)."""
+    import numpy as np
+    j, _ = _run({}, "--dump-outputs", str(tmp_path))
+    toks, logits = np.load(tmp_path / "tokens.npy"), np.load(tmp_path / "logits.npy")
+    assert toks.dtype == np.float64 and logits.dtype == np.float32
+    assert toks.shape == (8,) and [int(t) for t in toks[-4:]] == j["last_tokens"]
+    assert logits.ndim == 1 and np.isfinite(logits).all() and logits[int(toks[-1])] == logits.max()
+    _run({}, "--dump-outputs", str(tmp_path / "again"))
+    assert np.array_equal(np.load(tmp_path / "again" / "tokens.npy"), toks)                # same arguments, same inputs
+    assert np.array_equal(np.load(tmp_path / "again" / "logits.npy"), logits)
 
 
 @pytest.mark.parametrize("inject,expect", [("", "c-abi"), ("c-graph", "[eager steps]"), ("c-graph,c-eager", "torch.distributed")])

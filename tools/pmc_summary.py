@@ -4,7 +4,7 @@ per decode kernel the average FETCH_SIZE per launch, corrected as MI355X_MICROAR
 (FETCH_SIZE is in KiB and counts 64 B per 128-B request of a wide streaming read: bytes = value * 1024 * 2;
 calibrated here on the F16 lm_head kernel whose byte count is known exactly).
 
-    cd /tmp && rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT -o pmc -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline
+    cd /tmp && rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d OUT -o pmc -- python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline
     python tools/pmc_summary.py OUT/pmc_counter_collection.csv profiles/r02_pmc_traffic.json
 """
 import collections

@@ -11,7 +11,7 @@ for B in ${SIZES:-2 8 17 32}; do
   rm -rf $OUT/b$B
 done
 if [ -z "$NO_MIXTRAL" ]; then
-(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/mx -o st -- python $R/bench.py --no-cpu-baseline --shape mixtral_8x7b --batch 8 --steps 4 --warmup 2 --prefill-lens "" > $OUT/mx.log 2>&1)
+(cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/mx -o st -- python $R/bench.py --full --no-cpu-baseline --shape mixtral_8x7b --batch 8 --steps 4 --warmup 2 --prefill-lens "" > $OUT/mx.log 2>&1)
 f=$(find $OUT/mx -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && head -40 $f > $OUT/mixtral_b8_kernel_stats.csv
 rm -rf $OUT/mx

@@ -11,15 +11,15 @@ OUT=$PWD/gpurun_out/prof_r03
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 R=$PWD
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o st -- python $R/bench.py --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/stats.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o st -- python $R/bench.py --full --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/stats.log 2>&1)
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/r03_rocprofv3_kernel_stats.csv
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc -o pmc -- python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/pmc.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc -o pmc -- python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/pmc.log 2>&1)
 python tools/pmc_summary.py $(find $OUT/pmc -name "*counter_collection.csv" | head -1) $OUT/r03_pmc_traffic.json > $OUT/pmc_summary.log 2>&1
 cp $OUT/r03_pmc_traffic.json profiles/r03_pmc_traffic.json
-timeout 900 python bench.py > $OUT/r03_bench_n1.json 2> $OUT/bench.err
-timeout 600 python bench.py --no-cpu-baseline --wdtype q3h --kv-dtype q8 > $OUT/r03_bench_n1_q3h_q8.json 2>> $OUT/bench.err
-timeout 600 python bench.py --no-cpu-baseline --wdtype q3h > $OUT/r03_bench_n1_q3h_f16.json 2>> $OUT/bench.err
-timeout 600 python bench.py --no-cpu-baseline --shape mixtral_8x7b --batch 8 --steps 64 > $OUT/r03_bench_mixtral.json 2>> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/r03_bench_n1.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --wdtype q3h --kv-dtype q8 > $OUT/r03_bench_n1_q3h_q8.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --wdtype q3h > $OUT/r03_bench_n1_q3h_f16.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --shape mixtral_8x7b --batch 8 --steps 64 > $OUT/r03_bench_mixtral.json 2>> $OUT/bench.err
 timeout 600 python bench.py --loopback 2 --steps 32 --warmup 4 > $OUT/r03_bench_loopback_tp2.json 2>> $OUT/bench.err
 IFA_BATCH_SIZES=1,2,4,8,16,17,24,32 timeout 600 python tools/bench_batch.py > $OUT/r03_bench_batch.jsonl 2>> $OUT/bench.err
 (cd /tmp && IFA_BATCH_SIZES=8 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/b8 -o b8 -- python $R/tools/bench_batch.py > $OUT/b8.log 2>&1)

@@ -15,19 +15,19 @@ OUT=$PWD/gpurun_out/prof_r04
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 R=$PWD
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o st -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/stats.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o st -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/stats.log 2>&1)
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $OUT/r04_rocprofv3_kernel_stats.csv
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc -o pmc -- python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/pmc.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc -o pmc -- python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --prefill-lens "" --batch 0 > $OUT/pmc.log 2>&1)
 python tools/pmc_summary.py $(find $OUT/pmc -name "*counter_collection.csv" | head -1) $OUT/r04_pmc_traffic.json > $OUT/pmc_summary.log 2>&1
 cp $OUT/r04_pmc_traffic.json profiles/r04_pmc_traffic.json
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/r04_bench_n1.json 2> $OUT/bench.err
-timeout 600 python bench.py --no-cpu-baseline > $OUT/r04_bench_n1_steps128.json 2>> $OUT/bench.err
-timeout 600 python bench.py --no-cpu-baseline --steps 20 --warmup 5 --wdtype q3h --kv-dtype q8 --prefill-lens "" --batch 0 > $OUT/r04_bench_n1_q3h_q8.json 2>> $OUT/bench.err
-timeout 600 python bench.py --no-cpu-baseline --steps 20 --warmup 5 --wdtype q3h --prefill-lens "" --batch 0 > $OUT/r04_bench_n1_q3h_f16.json 2>> $OUT/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/r04_bench_n1.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline > $OUT/r04_bench_n1_steps128.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --wdtype q3h --kv-dtype q8 --prefill-lens "" --batch 0 > $OUT/r04_bench_n1_q3h_q8.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --wdtype q3h --prefill-lens "" --batch 0 > $OUT/r04_bench_n1_q3h_f16.json 2>> $OUT/bench.err
 timeout 300 python tools/trace_fused.py > $OUT/r04_fused_launch_phase_trace.log 2>&1
 timeout 300 python tools/trace_kernels.py > $OUT/r04_kernel_phase_trace.log 2>&1
 (for o in fuse_attn attn_kt step_tail fuse_wo fuse_wo_ffn; do timeout 300 python tools/ab_option.py $o --steps 20 --prompt 21 --kernels; done; timeout 300 python tools/ab_option.py graph_steps --values 1,4,8,16 --steps 20 --prompt 21) > $OUT/r04_ab_options.log 2>&1
-timeout 600 python bench.py --no-cpu-baseline --shape mixtral_8x7b --batch 8 --steps 64 > $OUT/r04_bench_mixtral.json 2>> $OUT/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --shape mixtral_8x7b --batch 8 --steps 64 > $OUT/r04_bench_mixtral.json 2>> $OUT/bench.err
 IFA_BATCH_SIZES=1,2,4,8,16,17,24,32 timeout 600 python tools/bench_batch.py > $OUT/r04_bench_batch.jsonl 2>> $OUT/bench.err
 bash tools/profile_batch.sh > $OUT/profile_batch.log 2>&1
 for f in gpurun_out/prof_batch/*_kernel_stats.csv; do cp $f $OUT/r04_$(basename $f); done

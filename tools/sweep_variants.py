@@ -85,7 +85,7 @@ def run(steps):
             if not os.path.exists(so):
                 continue
             env = dict(os.environ, IFA_LIB=so)
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "8", "--no-cpu-baseline",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps), "--warmup", "8", "--no-cpu-baseline",
                                 "--prefill-lens", ""] + BENCH_ARGS, env=env, capture_output=True, text=True)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if not line:
