@@ -214,6 +214,14 @@ int ifa_argmax(const void *logits_f16, size_t n, int *out_index_dev, ifa_stream 
  * SamplingStrategy::GetSortedTopK never offers to its queue: the vocabulary's unk id and Invalid-type tokens
  * (src/transformer/sampling_strategy.cc:281-297) */
 int ifa_argmax_masked(const void *logits_f16, size_t n, const int *excluded_dev, int *out_index_dev, ifa_stream stream);
+#define IFA_POOL_MAX 256
+/* SamplingStrategy::GetSortedTopK (src/transformer/sampling_strategy.cc:281-297) for `rows` logits rows [rows][n] F16:
+ * per row the k best (value, id) pairs, best first; equal values: lower id first (+0.0 and -0.0 are equal); NaN never
+ * enters; ids whose bit is set in excluded_bits_dev (nullable, ceil(n/32) words, bit id % 32 of word id / 32) are never
+ * offered.  ids_out [rows][k] int32, vals_out [rows][k] F16 bits (the bits the row holds at that id), count_out [rows] =
+ * min(k, admissible entries); slots past the count are unspecified.  1 <= k <= IFA_POOL_MAX.  Enqueue-only, capturable. */
+int ifa_topk_pool(const void *logits_f16, size_t rows, size_t n, int k, const unsigned *excluded_bits_dev,
+                  int *ids_out_dev, void *vals_out_f16_dev, int *count_out_dev, ifa_stream stream);
 
 /* ======================================================================== */
 /* Per-device decode worker: counterpart of GpuInferenceWorker                */
@@ -327,6 +335,30 @@ int ifa_model_decode_prepare(ifa_model *m, int start_pos, int n_steps);
  * (the weights are streamed once for all queries), attention per row on its own cache.  logits_out: optional [n][vocab] F16. */
 int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host,
                            int *next_tokens_host, void *logits_out_dev);
+/* ---- steps that end in a candidate pool (sampled decoding without the logits row on the host): ifa_topk_pool runs on the
+ * step's logits on the worker's stream, in front of the step's ONE synchronisation, and (count, ids, values) come back
+ * in one copy through pinned staging.  Everything after the pool -- softmax, cuts, the draw -- stays with the caller.
+ * Partitioned workers (tp_size > 1, or a step driven through ifa_model_tp_*) return IFA_ERR_STATE; options exact_order
+ * and perf_stat keep their own step (ifa_model_decode's fallbacks) and end in the same pool, the batched form under
+ * exact_order returns IFA_ERR_STATE. */
+/* device-resident mask of ids the pool never offers (any count); n = 0 clears it */
+int ifa_model_set_pool_excluded(ifa_model *m, const int *ids_host, int n);
+/* ifa_model_decode(first_token, start_pos, 1 step) followed by the pool of that step's logits row; the greedy id in
+ * *next_token_host as before.  Takes whatever route ifa_model_decode takes for this model (fused + graph where
+ * supported, else its fallback).  pool_ids_host / pool_vals_host hold k entries, *pool_count_host of them are valid. */
+int ifa_model_decode_pool(ifa_model *m, int token, int pos, int k, int *next_token_host,
+                          int *pool_ids_host, unsigned short *pool_vals_host, int *pool_count_host);
+/* the same behind a batched step: rows_sel_host[n_sel] = strictly ascending indices (into the step's n rows) whose pools
+ * are wanted; pool_ids_host / pool_vals_host [n_sel][k], pool_counts_host [n_sel] */
+int ifa_model_decode_batch_pool(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host,
+                                int *next_tokens_host, int k, const int *rows_sel_host, int n_sel,
+                                int *pool_ids_host, unsigned short *pool_vals_host, int *pool_counts_host);
+/* the same behind a prompt step: ifa_model_forward(tokens, n_tokens, prefix_len, logits_out_dev) + the pool of the LAST row.
+ * logits_out_dev as in ifa_model_forward (nullable); it also selects that call's arithmetic -- with it the lm_head runs over all
+ * rows (the rows GEMM), without it over the last row only -- so a caller that wants the pool of exactly the logits
+ * ifa_model_forward(..., logits_out_dev) produces passes the same buffer. */
+int ifa_model_forward_pool(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, void *logits_out_dev, int k,
+                           int *next_token_host, int *pool_ids_host, unsigned short *pool_vals_host, int *pool_count_host);
 /* debugging taps: "logits", "hidden", "kcache", "vcache" (device pointers) */
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes);
 void *ifa_model_stream(ifa_model *m);

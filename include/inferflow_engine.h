@@ -41,6 +41,12 @@ int ifa_sampling_choose(const uint16_t *logits_f16, int vocab, int strategy_id, 
 int ifa_sampling_choose_ex(const uint16_t *logits_f16, int vocab, int strategy_id, const float *params9, float temperature,
                            long long seed, int n_draws, int *out_ids, float *out_probs, int *pool_ids, float *pool_probs,
                            int pool_capacity, float *mirostat_mu_inout, const int *text_tokens, int n_text);
+/* the same from a candidate pool instead of the logits row: cand_ids / cand_vals_f16 [cand_count] = the row's SortedTopK for
+ * the strategy's pool length (1 for greedy, min(pool_size, vocab) otherwise), best first -- what ifa_topk_pool builds on the
+ * device.  Everything else as ifa_sampling_choose_ex; given that pool it returns what ifa_sampling_choose_ex returns on the row. */
+int ifa_sampling_choose_from_pool(const int *cand_ids, const uint16_t *cand_vals_f16, int cand_count, int strategy_id, const float *params9,
+                                  float temperature, long long seed, int n_draws, int *out_ids, float *out_probs, int *pool_ids,
+                                  float *pool_probs, int pool_capacity, float *mirostat_mu_inout, const int *text_tokens, int n_text);
 /* the first n NextDouble() values of the generator seeded with `seed` (known-answer tests of the LCG) */
 int ifa_sampling_random_doubles(long long seed, int n, double *out);
 int ifa_engine_query_count(ifa_engine *e);
@@ -75,7 +81,9 @@ double ifa_perplexity_token_nll(const uint16_t *logits_f16, int vocab, int token
 
 /* facts of the loaded model: "vocab_size", "embd_dims", "hidden_dim", "decoder_layers", "decoder_heads",
  * "decoder_kv_heads", "max_context_len", "device_weight_data_type", "device_kv_cache_data_type", "partition_ranks"
- * (workers of the multi-GPU partition; 1 = single device); -1 if unknown */
+ * (workers of the multi-GPU partition; 1 = single device), "device_sampling_pool" (the .ini key, 0 / 1), "sampled_fused_steps"
+ * (single-token steps of sampled queries served by the worker's decode step + device pool so far, one per query per step;
+ * stays 0 on the host path); -1 if unknown */
 int ifa_engine_model_info(ifa_engine *e, const char *key);
 
 /* the per-device worker of partition rank `rank` (an ifa_model * for the ifa_model_* calls of inferflow_amd.h; rank 0 of a

@@ -93,6 +93,7 @@ SIGNATURES = {
     "ifa_kv_store": (_i, [_i, _vp, _sz, _sz, _vp, _sz, _vp]),
     "ifa_argmax": (_i, [_vp, _sz, _vp, _vp]),
     "ifa_argmax_masked": (_i, [_vp, _sz, _vp, _vp, _vp]),
+    "ifa_topk_pool": (_i, [_vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "ifa_model_create": (_i, [_vp, C.POINTER(_vp)]),
     "ifa_model_destroy": (_i, [_vp]),
     "ifa_model_set_tensor": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _sz]),
@@ -110,6 +111,10 @@ SIGNATURES = {
     "ifa_model_kv_slots": (_i, [_vp, _i]),
     "ifa_model_select_kv": (_i, [_vp, _i]),
     "ifa_model_decode_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_model_set_pool_excluded": (_i, [_vp, _vp, _i]),
+    "ifa_model_decode_pool": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ifa_model_decode_batch_pool": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "ifa_model_forward_pool": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_get_buffer": (_i, [_vp, C.c_char_p, _i, C.POINTER(_vp), C.POINTER(_sz)]),
     "ifa_model_stream": (_vp, [_vp]),
     "ifa_model_time_kernel": (_i, [_vp, _i, _i, _vp]),
@@ -163,6 +168,7 @@ ENGINE_SIGNATURES = {
     "ifa_engine_strategy_id": (_i, [_vp, C.c_char_p]),
     "ifa_sampling_choose": (_i, [_vp, _i, _i, _i, _f, _i, _f, C.c_longlong, _i, _ip, C.POINTER(_f), _ip, C.POINTER(_f), _i]),
     "ifa_sampling_choose_ex": (_i, [_vp, _i, _i, C.POINTER(_f), _f, C.c_longlong, _i, _ip, C.POINTER(_f), _ip, C.POINTER(_f), _i, C.POINTER(_f), _ip, _i]),
+    "ifa_sampling_choose_from_pool": (_i, [_ip, _vp, _i, _i, C.POINTER(_f), _f, C.c_longlong, _i, _ip, C.POINTER(_f), _ip, C.POINTER(_f), _i, C.POINTER(_f), _ip, _i]),
     "ifa_sampling_random_doubles": (_i, [C.c_longlong, _i, C.POINTER(C.c_double)]),
     "ifa_engine_query_count": (_i, [_vp]),
     "ifa_engine_remove_query": (_i, [_vp, _i]),

@@ -834,6 +834,7 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     }
     th("steps enqueued");
     if (elapsed_ms) IFA_HIP_CHECK(hipEventRecord(e1, s));
+    if ((rc = pool_enqueue(m, m->logits, 1))) return rc;      // (armed by ifa_model_decode_pool only: the last step's row)
     IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned + 8, m->state + 8, sizeof(int) * (size_t)n_steps, hipMemcpyDeviceToHost, s));
     int *qerr = m->host_pinned + 8 + ifa_model::RING;
     qerr[0] = 0;

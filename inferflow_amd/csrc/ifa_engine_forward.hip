@@ -404,6 +404,7 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
     } else {
         if ((rc = ifa_argmax_masked(m->logits + (size_t)(T - 1) * V, V, m->state + 3, m->state, s))) return rc;
         IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned, m->state, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+        if ((rc = pool_enqueue(m, m->logits + (size_t)(T - 1) * V, 1))) return rc;
     }
     const auto host_t1 = std::chrono::steady_clock::now();
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -641,6 +642,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
         auto it = m->batch_graphs.find(n);
         if (it != m->batch_graphs.end()) {
             IFA_HIP_CHECK(hipGraphLaunch(it->second, m->stream));
+            if ((rc = pool_enqueue(m, m->logits, n))) return rc;
             IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
             if ((rc = wait_err_check("batched decode step"))) { drop_graphs(m); return rc; }      // (the captured steps hold K-parts launches: re-captured without them)
             if (next_tokens) for (int r = 0; r < n; r++) next_tokens[r] = m->host_pinned[8 + r];
@@ -727,6 +729,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
         m->batch_graphs[n] = ex;
         IFA_HIP_CHECK(hipGraphLaunch(ex, m->stream));
     } else if (rc) return rc;
+    if (!tp && (rc = pool_enqueue(m, m->logits, n))) return rc;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     if ((rc = wait_err_check("batched decode step"))) { drop_graphs(m); return rc; }
     if (next_tokens) for (int r = 0; r < n; r++) next_tokens[r] = m->host_pinned[8 + r];
@@ -799,6 +802,7 @@ int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const in
         const int k = (n + fused_max - 1) / fused_max, per = (n + k - 1) / k;
         for (int c0 = 0; c0 < n; c0 += per) {
             const int nc = std::min(per, n - c0);
+            m->pool.chunk0 = c0; m->pool.last_chunk = c0 + nc >= n;
             int rc = forward_batch(m, nc, tokens_host + c0, positions_host + c0, kv_slots_host + c0, next_tokens_host ? next_tokens_host + c0 : nullptr,
                                    logits_out_dev ? (char *)logits_out_dev + (size_t)c0 * m->g[T_LM_HEAD].rows * 2 : nullptr);
             if (rc) return rc;

@@ -191,6 +191,19 @@ struct ifa_model {
     int opt_prefill_res_mid = 2048;   // prefill_mid_max + 1 .. this many tokens: wo / w2 still through k_gemm_mid, the other products through the large tiles (0: never)
     int opt_rows_kparts = 1, opt_gemm_splitk = 1;   // 0: never the launches whose workgroups wait for partner workgroups (K parts of the 9..32-row GEMM, split-K halves of the large-tile GEMM)
     int opt_debug_mo_alloc_fail = 0;           // tests: ensure_mo_build fails like an exhausted allocator after its first copy
+    // Steps that end in a candidate pool (ifa_model_decode_pool / _decode_batch_pool / _forward_pool, ifa_engine_pool.hip): the entry
+    // point arms `pool`, the step calls pool_enqueue() on its logits in front of its one synchronisation (never under capture), the
+    // entry point reads the pinned block afterwards.  Result block: counts [n_sel] | ids [n_sel][k] | F16 bits [n_sel][k].
+    struct PoolReq {
+        int k = 0;                             // > 0: armed
+        int n_sel = 0;                         // rows wanted (1 for a single-query step)
+        const int *rows_sel = nullptr;         // batched step: ascending row indices (host); null: the step's one row
+        int chunk0 = 0; bool last_chunk = true;      // batched step taken as several steps: first row / last step of this one
+        int done = 0;                          // rows whose pool has been enqueued
+    } pool;
+    unsigned *pool_excl = nullptr;             // device bitmask of ids the pool never offers (null: none)
+    void *pool_dev = nullptr, *pool_pin = nullptr; size_t pool_bytes = 0;      // result block, device / pinned
+    int *pool_idx_dev = nullptr, *pool_idx_pin = nullptr; size_t pool_idx_cap = 0;
     static constexpr int RING = 1024;
 };
 
@@ -332,6 +345,11 @@ bool prefill_mid_ok(ifa_model *m, int T, bool any_length);
 int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext, const void *rows_l);
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
                          void *logits_out);
+// ---- ifa_engine_pool.hip
+// armed (m->pool.k > 0): ifa_topk_pool over the wanted rows of `logits` ([n_rows][vocab], this step's rows) + the copy of the result
+// block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.
+int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
+void pool_free(ifa_model *m);
 // ---- ifa_engine_moe.hip
 int launch_moe_router(ifa_model *m, int l);
 // Mixture of experts (ProcessGpuLayer_Moe, inference_worker.cc:1924-2146): router GEMV -> softmax -> D2H ->

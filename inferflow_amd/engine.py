@@ -173,6 +173,24 @@ def sampling_choose_ex(logits_f16, strategy_id, temperature=1.0, seed=1, n_draws
     return [ids[i] for i in range(n_draws)], [pr[i] for i in range(n_draws)], [pid[i] for i in range(min(n, 256))], [ppr[i] for i in range(min(n, 256))], m.value
 
 
+def sampling_choose_from_pool(cand_ids, cand_vals_f16, strategy_id, temperature=1.0, seed=1, n_draws=1, mu=None, max_k=8, top_p=0.9, pool_size=50,
+                              min_p=0.05, z=0.95, typical_p=0.95, eta=0.1, tau=5.0, text=()):
+    """sampling_choose_ex given the row's candidate pool (ids, F16 values, best first: SortedTopK / ifa_topk_pool) instead of the row."""
+    cid = np.ascontiguousarray(cand_ids, np.int32).reshape(-1)
+    cv = np.ascontiguousarray(cand_vals_f16).view(np.uint16).reshape(-1) if len(cand_vals_f16) else np.zeros(0, np.uint16)
+    assert cid.size == cv.size
+    params = (C.c_float * 9)(max_k, top_p, pool_size, min_p, z, typical_p, eta, tau, 0)
+    ids = (C.c_int * max(1, n_draws))(); pr = (C.c_float * max(1, n_draws))()
+    pid = (C.c_int * 256)(); ppr = (C.c_float * 256)()
+    m = C.c_float(float("nan") if mu is None else mu)
+    txt = (C.c_int * max(1, len(text)))(*[int(t) for t in text])
+    n = _capi.lib().ifa_sampling_choose_from_pool(cid.ctypes.data_as(C.POINTER(C.c_int)), cv.ctypes.data_as(C.c_void_p), cid.size, int(strategy_id), params,
+                                                  temperature, int(seed), n_draws, ids, pr, pid, ppr, 256, C.byref(m), txt, len(text))
+    if n < 0:
+        raise EngineError(_capi.lib().ifa_engine_last_error().decode(errors="replace"))
+    return [ids[i] for i in range(n_draws)], [pr[i] for i in range(n_draws)], [pid[i] for i in range(min(n, 256))], [ppr[i] for i in range(min(n, 256))], m.value
+
+
 def random_doubles(seed, n):
     out = (C.c_double * n)()
     _capi.lib().ifa_sampling_random_doubles(int(seed), n, out)

@@ -10,6 +10,7 @@
 #include "inference_engine.h"
 #include "inferflow_service.h"
 #include "perplexity.h"
+#include "half_bits.h"
 
 using namespace inferflow_amd;
 
@@ -94,6 +95,33 @@ int ifa_sampling_choose_ex(const uint16_t *logits_f16, int vocab, int strategy_i
     for (int d = 0; d < std::max(1, n_draws); d++) {
         SamplingOutput out;
         if (!ChooseTokens(out, logits_f16, vocab, (SamplingStrategyId)strategy_id, cfg, temperature, rng, st, text)) { EngineSetError("ifa_sampling_choose_ex: unsupported strategy %d", strategy_id); return -1; }
+        if (d < n_draws && !out.selected.empty()) { if (out_ids) out_ids[d] = out.selected[0].id; if (out_probs) out_probs[d] = out.selected[0].weight; }
+        pool_n = (int)out.token_pool.size();
+        for (int i = 0; i < pool_n && i < pool_capacity; i++) { if (pool_ids) pool_ids[i] = out.token_pool[(size_t)i].id; if (pool_probs) pool_probs[i] = out.token_pool[(size_t)i].weight; }
+    }
+    if (mirostat_mu_inout) *mirostat_mu_inout = st.mirostat_mu;
+    return pool_n;
+}
+
+int ifa_sampling_choose_from_pool(const int *cand_ids, const uint16_t *cand_vals_f16, int cand_count, int strategy_id, const float *params9,
+                                  float temperature, long long seed, int n_draws, int *out_ids, float *out_probs, int *pool_ids,
+                                  float *pool_probs, int pool_capacity, float *mirostat_mu_inout, const int *text_tokens, int n_text)
+{
+    if (cand_count < 0 || (cand_count > 0 && (!cand_ids || !cand_vals_f16)) || n_draws < 0 || !params9) { EngineSetError("ifa_sampling_choose_from_pool: bad arguments"); return -1; }
+    SamplingConfig cfg;
+    cfg.max_k = (int)params9[0]; cfg.top_p = params9[1]; cfg.pool_size = (int)params9[2]; cfg.min_p = params9[3]; cfg.tfs_z = params9[4];
+    cfg.typical_p = params9[5]; cfg.mirostat_eta = params9[6]; cfg.mirostat_tau = params9[7]; cfg.eos_bypassing_max = (int)params9[8];
+    cfg.rfsd_top_p = cfg.top_p;
+    std::vector<IdWeight> cand((size_t)cand_count);
+    for (int i = 0; i < cand_count; i++) { cand[(size_t)i].id = cand_ids[i]; cand[(size_t)i].weight = HalfBitsToFloat(cand_vals_f16[i]); }
+    JavaRandom rng((uint64_t)seed);
+    SamplingState st;
+    if (mirostat_mu_inout) st.mirostat_mu = *mirostat_mu_inout;
+    const std::vector<int> text(text_tokens, text_tokens + (text_tokens ? std::max(0, n_text) : 0));
+    int pool_n = 0;
+    for (int d = 0; d < std::max(1, n_draws); d++) {
+        SamplingOutput out;
+        if (!ChooseTokensFromPool(out, cand, (SamplingStrategyId)strategy_id, cfg, temperature, rng, st, text)) { EngineSetError("ifa_sampling_choose_from_pool: unsupported strategy %d", strategy_id); return -1; }
         if (d < n_draws && !out.selected.empty()) { if (out_ids) out_ids[d] = out.selected[0].id; if (out_probs) out_probs[d] = out.selected[0].weight; }
         pool_n = (int)out.token_pool.size();
         for (int i = 0; i < pool_n && i < pool_capacity; i++) { if (pool_ids) pool_ids[i] = out.token_pool[(size_t)i].id; if (pool_probs) pool_probs[i] = out.token_pool[(size_t)i].weight; }
@@ -200,6 +228,8 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "device_weight_data_type") return s.device_weight_data_type;
     if (k == "device_kv_cache_data_type") return s.device_kv_cache_data_type;
     if (k == "partition_ranks") return e->engine.PartitionRanks();
+    if (k == "device_sampling_pool") return e->engine.config().device_sampling_pool ? 1 : 0;
+    if (k == "sampled_fused_steps") return (int)std::min<long long>(e->engine.sampled_fused_steps(), 0x7FFFFFFF);
     return -1;
 }
 

@@ -14,6 +14,7 @@
 #include "inferflow_amd.h"
 #include "inference_engine.h"
 #include "ifa_ini.h"
+#include "half_bits.h"
 
 namespace inferflow_amd {
 
@@ -228,6 +229,7 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "return_output_tensors", config.return_output_tensors);
     cfg.GetItem(section, "dynamic_batching_min_queries", config.dynamic_batching_min_queries);
     cfg.GetItem(section, "force_partition_path", config.force_partition_path);
+    cfg.GetItem(section, "device_sampling_pool", config.device_sampling_pool);
     cfg.GetItem(section, "is_study_mode", config.debug.is_study_mode);
     cfg.GetItem(section, "show_tensors", config.debug.show_tensors);
     return true;
@@ -275,6 +277,11 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
         if (multi_) for (WorkerPlan &w : multi_->plans) all.push_back(w.model); else all.push_back(model_);
         for (ifa_model *mm : all)
             if (ifa_model_set_excluded_tokens(mm, excl.data(), (int)excl.size()) != IFA_OK) { EngineSetError("excluded tokens: %s", ifa_last_error()); Clear(); return false; }
+        // the device pool's mask has no limit: the full list
+        const std::vector<int> &full = default_sampling_.excluded_ids;
+        if (config_.device_sampling_pool && !multi_ && ifa_model_set_pool_excluded(model_, full.data(), (int)full.size()) != IFA_OK) {
+            EngineSetError("excluded tokens of the device pool: %s", ifa_last_error()); Clear(); return false;
+        }
     }
     // Per-phase keys of InferencePerfStat ((layer + 1) * 10000 + phase, inference_worker.cc:2670-2697) are filled in study mode only: the
     // reference times the host side of its launches for free, here the phases exist as separate launches only on the op-by-op step
@@ -500,6 +507,30 @@ bool InferenceEngine::SampleRow(Query &q, const uint16_t *logits_row, QueryInfer
     return true;
 }
 
+bool InferenceEngine::SamplePool(Query &q, const int *ids, const uint16_t *vals, int count, QueryInferenceResult &item)
+{
+    std::vector<IdWeight> pool((size_t)std::max(count, 0));
+    for (int i = 0; i < count; i++) { pool[(size_t)i].id = ids[i]; pool[(size_t)i].weight = HalfBitsToFloat(vals[i]); }
+    SamplingOutput out;
+    if (!ChooseTokensFromPool(out, std::move(pool), q.strategy, q.sampling, q.options.temperature, q.rng, q.sampling_state, q.tokens)
+        || out.selected.empty()) {
+        EngineSetError("Sampling failed for query %d", q.id); return false;
+    }
+    item.next_tokens.clear();
+    item.next_tokens.push_back(out.selected[0]);
+    return true;
+}
+
+int InferenceEngine::PoolLen(const Query &q) const { return PoolLength(q.strategy, q.sampling, spec_.hyper_params.vocab_size); }
+
+bool InferenceEngine::PoolRoute(const Query &q) const
+{
+    if (!config_.device_sampling_pool || config_.return_output_tensors || multi_) return false;
+    if (q.strategy == SamplingStrategyId::Greedy && !host_greedy_) return false;      // (the device argmax serves it)
+    const int k = PoolLen(q);
+    return k >= 1 && k <= IFA_POOL_MAX;
+}
+
 bool InferenceEngine::RemoveQuery(int query_id)
 {
     return queries_.erase(query_id) != 0;
@@ -533,7 +564,17 @@ bool InferenceEngine::Infer(InferenceResult &res)
         for (int r = 0; r < n; r++) { toks[(size_t)r] = batch[(size_t)r]->tokens.back(); pos[(size_t)r] = batch[(size_t)r]->processed; slots[(size_t)r] = batch[(size_t)r]->kv_slot; }
         void *lg = nullptr;
         bool any_sampled = false;
-        for (Query *bq : batch) any_sampled = any_sampled || bq->strategy != SamplingStrategyId::Greedy || host_greedy_;
+        // rows whose candidates come from the device pool behind the step (device_sampling_pool): no logits row leaves the device
+        // for them; one pool length serves the launch (the longest wanted; a query reads its own prefix of the sorted pool)
+        std::vector<int> pool_rows; int pool_k = 0;
+        for (int r = 0; r < n; r++) {
+            Query *bq = batch[(size_t)r];
+            const bool smp = bq->strategy != SamplingStrategyId::Greedy || host_greedy_;
+            if (smp && PoolRoute(*bq)) { pool_rows.push_back(r); pool_k = std::max(pool_k, PoolLen(*bq)); }
+            else any_sampled = any_sampled || smp;
+        }
+        if (any_sampled) { pool_rows.clear(); pool_k = 0; }      // (a row that needs the host path brings the whole block over anyway)
+        std::vector<int> pool_ids, pool_counts; std::vector<uint16_t> pool_vals;
         std::vector<uint16_t> all;
         if (multi_) {
             // Query batching over a tensor-parallel device group (the reference: query batching, inference_engine.cc:1054-1124,
@@ -550,6 +591,15 @@ bool InferenceEngine::Infer(InferenceResult &res)
             }
             lg = logits_dev_;
         }
+        if (!pool_rows.empty()) {
+            const size_t ns = pool_rows.size();
+            pool_ids.resize(ns * (size_t)pool_k); pool_vals.resize(ns * (size_t)pool_k); pool_counts.resize(ns);
+            if (ifa_model_decode_batch_pool(model_, n, toks.data(), pos.data(), slots.data(), next.data(), pool_k, pool_rows.data(), (int)ns,
+                                            pool_ids.data(), pool_vals.data(), pool_counts.data()) != IFA_OK) {
+                EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
+            }
+            sampled_fused_steps_ += (long long)ns;
+        } else
         if (ifa_model_decode_batch(model_, n, toks.data(), pos.data(), slots.data(), next.data(), lg) != IFA_OK) {
             EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
         }
@@ -567,6 +617,12 @@ bool InferenceEngine::Infer(InferenceResult &res)
             q.processed = (int)q.tokens.size();
             IdWeight w; w.id = next[(size_t)r]; w.weight = 1.0f;
             item.next_tokens.push_back(w);
+            const auto pr = std::find(pool_rows.begin(), pool_rows.end(), r);
+            if (pr != pool_rows.end()) {
+                const size_t j = (size_t)(pr - pool_rows.begin());
+                const int cnt = std::min(pool_counts[j], PoolLen(q));
+                if (!SamplePool(q, pool_ids.data() + j * (size_t)pool_k, pool_vals.data() + j * (size_t)pool_k, cnt, item)) return false;
+            } else
             if ((q.strategy != SamplingStrategyId::Greedy || host_greedy_) && !SampleRow(q, all.data() + (size_t)r * V, item)) return false;
             res.items.push_back(std::move(item));
         }
@@ -591,6 +647,23 @@ bool InferenceEngine::Infer(InferenceResult &res)
             continue;
         }
         if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
+        if (sampled && PoolRoute(q)) {                               // the step ends in the candidate pool: nothing of size V leaves the device
+            const int k = PoolLen(q);
+            int ids[IFA_POOL_MAX], cnt = 0; uint16_t vals[IFA_POOL_MAX];
+            // (a prompt keeps today's forward step -- lm_head over all rows into the engine's logits buffer, so its last row is bit for
+            //  bit the row the host path samples from -- and only the pool of that row comes to the host)
+            if (n_new > 1 && (size_t)n_new > logits_rows_) {
+                if (logits_dev_) ifa_free(logits_dev_);
+                logits_dev_ = nullptr; logits_rows_ = 0;
+                if (ifa_malloc(&logits_dev_, (size_t)n_new * V * 2) != IFA_OK) { EngineSetError("logits buffer: %s", ifa_last_error()); return false; }
+                logits_rows_ = (size_t)n_new;
+            }
+            const int rc = n_new == 1 ? ifa_model_decode_pool(model_, q.tokens.back(), q.processed, k, &next, ids, vals, &cnt)
+                                      : ifa_model_forward_pool(model_, q.tokens.data() + q.processed, n_new, q.processed, logits_dev_, k, &next, ids, vals, &cnt);
+            if (rc != IFA_OK) { EngineSetError("%s step failed: %s", n_new == 1 ? "decode" : "forward", ifa_last_error()); return false; }
+            if (n_new == 1) sampled_fused_steps_++;
+            if (!SamplePool(q, ids, vals, cnt, item)) return false;
+        } else
         if (n_new == 1 && !want_tensor) {                            // decode: fused graph-replayed step
             if (ifa_model_decode(model_, q.tokens.back(), q.processed, 1, &next, nullptr) != IFA_OK) {
                 EngineSetError("decode step failed: %s", ifa_last_error()); return false;

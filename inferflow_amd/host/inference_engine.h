@@ -95,6 +95,11 @@ struct InferenceConfig {
     // extension (tests on a 1-GPU box): run a single device through the partition path -- rank thread, communicator of
     // one rank, the C-driven step with its collectives -- instead of the plain single-worker path
     bool force_partition_path = false;
+    // extension: sampled queries (and greedy ones over a vocabulary with more than 3 excluded ids) take the fused / batched step
+    // and receive the step's candidate pool -- the top pool_size (value, id) pairs, built on the device by ifa_topk_pool -- instead
+    // of the logits row.  Applies when return_output_tensors is false, the engine is a single device and pool_size <= IFA_POOL_MAX;
+    // every other case keeps the host path.  The sampler's rules, draws and generator are the same code either way.
+    bool device_sampling_pool = false;
     DebugOptions debug;
 };
 
@@ -188,6 +193,9 @@ public:
     int default_device_id() const { return device_; }
     int PartitionRanks() const;     // workers of the multi-GPU partition (1: single device)
     ifa_model *worker() { return model_; }
+    // single-token steps of sampled queries that took the worker's decode step + device pool instead of ifa_model_forward
+    // (one per query per step; 0 unless device_sampling_pool is on)
+    long long sampled_fused_steps() const { return sampled_fused_steps_; }
     // worker of partition rank r and its place in the partition (stage, n_stages, tp_rank, tp_size, layer0, layer1); rank 0 of a
     // single-device engine is worker().  The tests read the ranks' weight slices back and rebuild the whole model for the oracle.
     ifa_model *worker(int rank);
@@ -207,6 +215,10 @@ private:
         SamplingState sampling_state;   // Mirostat's mu, the FSD n-gram model, the EOS bypass count
     };
     bool SampleRow(Query &q, const uint16_t *logits_row, QueryInferenceResult &item);
+    // the same from a device-built candidate pool (ifa_topk_pool: count entries of ids / F16 bits, best first)
+    bool SamplePool(Query &q, const int *ids, const uint16_t *vals, int count, QueryInferenceResult &item);
+    bool PoolRoute(const Query &q) const;       // this query's candidates come from the device pool (device_sampling_pool)
+    int PoolLen(const Query &q) const;
     // ---- multi-GPU partitions (devices = 0&1 | 0;1 | 0&1;2&3): one worker and one host thread per GPU, like the
     // reference's Infer_TensorParallelism / Infer_Std over GpuInferenceWorker threads (inference_engine.cc:1161-1296)
     struct MultiGpu;
@@ -228,6 +240,7 @@ private:
     std::map<int, Query> queries_;
     void *logits_dev_ = nullptr;
     size_t logits_rows_ = 0;
+    long long sampled_fused_steps_ = 0;
 };
 
 // error text of the last failed call on this thread (the reference logs through LogError)

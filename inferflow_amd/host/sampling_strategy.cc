@@ -235,12 +235,18 @@ bool ChooseTokens(SamplingOutput &out, const uint16_t *logits, int vocab, Sampli
 {
     out = SamplingOutput();
     if (!logits || vocab <= 0 || !IsSupportedStrategy(strategy)) return false;
-    int max_queue_len = 1;
-    float top_p = 1.0f;
-    if (strategy != SamplingStrategyId::Greedy) max_queue_len = std::min(cfg.pool_size, vocab);
-    if (strategy == SamplingStrategyId::StdSampling || strategy == SamplingStrategyId::TopP) top_p = cfg.top_p;
     std::vector<IdWeight> pool;
-    SortedTopK(logits, vocab, max_queue_len, pool, cfg.excluded_ids);
+    SortedTopK(logits, vocab, PoolLength(strategy, cfg, vocab), pool, cfg.excluded_ids);
+    return ChooseTokensFromPool(out, std::move(pool), strategy, cfg, temperature, rng, state, text, eos_id);
+}
+
+bool ChooseTokensFromPool(SamplingOutput &out, std::vector<IdWeight> pool, SamplingStrategyId strategy, const SamplingConfig &cfg,
+                          float temperature, JavaRandom &rng, SamplingState &state, const std::vector<int> &text, int eos_id)
+{
+    out = SamplingOutput();
+    if (!IsSupportedStrategy(strategy)) return false;
+    float top_p = 1.0f;
+    if (strategy == SamplingStrategyId::StdSampling || strategy == SamplingStrategyId::TopP) top_p = cfg.top_p;
     if (pool.empty()) return true;
     const std::vector<IdWeight> raw = pool;                     // logits of the pool (Mirostat re-normalises a prefix of them)
     bool drawn = false;

@@ -118,5 +118,15 @@ IdWeight DrawOne(JavaRandom &rng, const std::vector<IdWeight> &pool);
 bool ChooseTokens(SamplingOutput &out, const uint16_t *logits_f16, int vocab, SamplingStrategyId strategy,
                   const SamplingConfig &cfg, float temperature, JavaRandom &rng, SamplingState &state,
                   const std::vector<int> &text = std::vector<int>(), int eos_id = -1);
+// length of the candidate pool ChooseTokens asks SortedTopK for: 1 for Greedy, min(pool_size, vocab) otherwise
+inline int PoolLength(SamplingStrategyId strategy, const SamplingConfig &cfg, int vocab)
+{
+    return strategy == SamplingStrategyId::Greedy ? 1 : (cfg.pool_size < vocab ? cfg.pool_size : vocab);
+}
+// everything of ChooseTokens after SortedTopK: `pool` is that function's result for PoolLength() entries -- built on the host, or
+// on the device behind the step (ifa_topk_pool).  ChooseTokens = SortedTopK + this.
+bool ChooseTokensFromPool(SamplingOutput &out, std::vector<IdWeight> pool, SamplingStrategyId strategy, const SamplingConfig &cfg,
+                          float temperature, JavaRandom &rng, SamplingState &state,
+                          const std::vector<int> &text = std::vector<int>(), int eos_id = -1);
 
 } // namespace inferflow_amd

@@ -107,6 +107,47 @@ class DecodeWorker:
                                      out.ctypes.data_as(C.c_void_p), C.byref(ms) if timed else None))
         return out, ms.value
 
+    def set_pool_excluded(self, ids):
+        """ids (any count) the device candidate pool never offers; an empty list clears the mask"""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        check(lib().ifa_model_set_pool_excluded(self._h, a.ctypes.data_as(C.c_void_p) if a.size else None, a.size))
+
+    def decode_pool(self, token, pos, k):
+        """One decode step that ends in the candidate pool of its logits row (ifa_model_decode_pool).
+        Returns (greedy next token, pool ids int32 [count], pool values as F16 bits uint16 [count]), best first."""
+        ids, vals = np.zeros(k, np.int32), np.zeros(k, np.uint16)
+        nxt, cnt = C.c_int(-1), C.c_int(0)
+        check(lib().ifa_model_decode_pool(self._h, int(token), int(pos), int(k), C.byref(nxt), ids.ctypes.data_as(C.c_void_p),
+                                          vals.ctypes.data_as(C.c_void_p), C.byref(cnt)))
+        return nxt.value, ids[:cnt.value].copy(), vals[:cnt.value].copy()
+
+    def forward_pool(self, tokens, prefix_len, k, logits_out=None):
+        """One prompt step (forward) that ends in the candidate pool of its LAST row; returns like decode_pool.
+        logits_out: optional torch cuda f16 [T][vocab], as in forward()."""
+        toks = np.ascontiguousarray(tokens, np.int32)
+        ids, vals = np.zeros(k, np.int32), np.zeros(k, np.uint16)
+        nxt, cnt = C.c_int(-1), C.c_int(0)
+        check(lib().ifa_model_forward_pool(self._h, toks.ctypes.data_as(C.c_void_p), toks.size, int(prefix_len),
+                                           C.c_void_p(logits_out.data_ptr()) if logits_out is not None else None, int(k), C.byref(nxt),
+                                           ids.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), C.byref(cnt)))
+        return nxt.value, ids[:cnt.value].copy(), vals[:cnt.value].copy()
+
+    def decode_batch_pool(self, tokens, positions, slots, k, rows_sel):
+        """decode_batch whose rows rows_sel (ascending indices into the step's rows) end in their candidate pools.
+        Returns (next tokens [n], [(ids, F16 bits)] per selected row)."""
+        toks = np.ascontiguousarray(tokens, np.int32)
+        pos = np.ascontiguousarray(positions, np.int32)
+        sl = np.ascontiguousarray(slots, np.int32)
+        sel = np.ascontiguousarray(rows_sel, np.int32).reshape(-1)
+        out = np.zeros(toks.size, np.int32)
+        ids, vals = np.zeros((max(sel.size, 1), k), np.int32), np.zeros((max(sel.size, 1), k), np.uint16)
+        cnt = np.zeros(max(sel.size, 1), np.int32)
+        check(lib().ifa_model_decode_batch_pool(self._h, toks.size, toks.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.c_void_p),
+                                                sl.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), int(k),
+                                                sel.ctypes.data_as(C.c_void_p), sel.size, ids.ctypes.data_as(C.c_void_p),
+                                                vals.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
+        return out, [(ids[j, :cnt[j]].copy(), vals[j, :cnt[j]].copy()) for j in range(sel.size)]
+
     def decode_prepare(self, start_pos, n_steps):
         """Set up (capture) what decode(., start_pos, n_steps) replays, without running a step."""
         check(lib().ifa_model_decode_prepare(self._h, int(start_pos), int(n_steps)))
@@ -207,6 +248,21 @@ class DecodeWorker:
             self.close()
         except Exception:
             pass
+
+
+def topk_pool(logits, k, excluded_bits=None, stream=None):
+    """ifa_topk_pool over a torch cuda F16 tensor [rows][n] (or [n]): the k best (value, id) pairs per row, best first, lower id
+    among equal values, NaN and the ids of excluded_bits (torch cuda int32 bitmask, ceil(n / 32) words) never offered.
+    Returns torch cuda tensors (ids int32 [rows][k], values int16 = F16 bits [rows][k], counts int32 [rows]); enqueue-only."""
+    import torch
+    rows, n = (1, logits.numel()) if logits.dim() == 1 else logits.shape
+    ids = torch.empty((rows, max(k, 1)), dtype=torch.int32, device=logits.device)
+    vals = torch.empty((rows, max(k, 1)), dtype=torch.int16, device=logits.device)
+    cnt = torch.empty(rows, dtype=torch.int32, device=logits.device)
+    check(lib().ifa_topk_pool(C.c_void_p(logits.data_ptr()), rows, n, int(k),
+                              C.c_void_p(excluded_bits.data_ptr()) if excluded_bits is not None else None,
+                              C.c_void_p(ids.data_ptr()), C.c_void_p(vals.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
+    return ids, vals, cnt
 
 
 class TpTopology(C.Structure):
