@@ -222,6 +222,18 @@ int ifa_argmax_masked(const void *logits_f16, size_t n, const int *excluded_dev,
  * min(k, admissible entries); slots past the count are unspecified.  1 <= k <= IFA_POOL_MAX.  Enqueue-only, capturable. */
 int ifa_topk_pool(const void *logits_f16, size_t rows, size_t n, int k, const unsigned *excluded_bits_dev,
                   int *ids_out_dev, void *vals_out_f16_dev, int *count_out_dev, ifa_stream stream);
+/* The softmax normaliser of `rows` F16 logits rows over the FULL vocabulary (no exclusion mask: the perplexity tool's softmax):
+ * lse = max + log(sum exp(x - max)), x widened from F16, fp32 arithmetic; log p(id) = float(row[id]) - lse.  Row r is
+ * logits + (row_idx_dev ? row_idx_dev[r] : r) * row_stride halfs (row_stride >= n).  targets_dev (nullable) holds one id per row;
+ * target_logit_out_dev[r] (nullable) = the row's value at that id widened exactly, NaN for a target below 0.  -inf entries
+ * contribute 0; lse is NaN exactly when the float64 definition is: a NaN or +inf in the row, or a row of -inf only.
+ * Wave64, 16-byte loads, 2048 independent partial sums per workgroup and fixed reduction trees: no float atomics, run-to-run
+ * identical.  With `rows` below 64 a row is split over up to 64 workgroups whose (max, sum) pairs a second small launch combines in
+ * a fixed order; that needs workspace_dev of ifa_logsumexp_workspace(rows, n) bytes (0 bytes: no split).  A null workspace_dev
+ * takes one workgroup per row whatever the row count.  Enqueue-only, capturable. */
+size_t ifa_logsumexp_workspace(size_t rows, size_t n);
+int ifa_logsumexp_rows(const void *logits_f16, size_t row_stride, const int *row_idx_dev, size_t rows, size_t n,
+                       const int *targets_dev, float *lse_out_dev, float *target_logit_out_dev, void *workspace_dev, ifa_stream stream);
 
 /* ======================================================================== */
 /* Per-device decode worker: counterpart of GpuInferenceWorker                */
@@ -359,6 +371,20 @@ int ifa_model_decode_batch_pool(ifa_model *m, int n, const int *tokens_host, con
  * ifa_model_forward(..., logits_out_dev) produces passes the same buffer. */
 int ifa_model_forward_pool(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, void *logits_out_dev, int k,
                            int *next_token_host, int *pool_ids_host, unsigned short *pool_vals_host, int *pool_count_host);
+/* Option "pool_lse" = 1 (ifa_model_set_option; default 0): the three pool steps above also run ifa_logsumexp_rows over every pooled
+ * row and its lse rides in the same staged block; after the step ifa_model_pool_lse copies out the n_sel (1 for the single-query
+ * steps) values, log p(pool id) = float(pool value) - lse.  With the option off the steps enqueue exactly what they did before and
+ * *n_out is 0.  Changing the option keeps the captured graphs. */
+int ifa_model_pool_lse(ifa_model *m, float *lse_host, int cap, int *n_out);
+/* A scoring prompt: ifa_model_forward(tokens, n_tokens, prefix_len) with the lm_head over ALL rows into the worker's own logits
+ * buffer -- bit for bit the rows ifa_model_forward(..., logits_out_dev) delivers, on the same route (one pass, the two passes of a
+ * 34..48-token prompt, options exact_order and perf_stat) -- then ifa_logsumexp_rows over them: lse_host[i] and
+ * target_logit_host[i] = float(row i at targets_host[i]) (NaN for a target below 0) come back as 2 * n_tokens floats through pinned
+ * staging in front of the prompt's one synchronisation.  log p(targets[i] | tokens[0..i]) = target_logit[i] - lse[i].  No
+ * [n_tokens][vocab] block is allocated by the caller or copied.  *next_token_host (nullable) as in ifa_model_forward.  Partitioned
+ * workers (tp_size > 1, or a topology) return IFA_ERR_STATE. */
+int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, const int *targets_host,
+                            float *lse_host, float *target_logit_host, int *next_token_host);
 /* debugging taps: "logits", "hidden", "kcache", "vcache" (device pointers) */
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes);
 void *ifa_model_stream(ifa_model *m);

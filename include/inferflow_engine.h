@@ -27,6 +27,18 @@ int ifa_engine_add_query(ifa_engine *e, const int *tokens, int n_tokens);
  * greedy, 1 sample.std, 2 greedy, 3 top_k, 4 top_p, 5 fsd, 6 random_fsd, 7 min_p, 8 tfs, 9 typical, 10 mirostat), random_seed != 0 seeds the
  * query's generator (sslib Random = the java.util.Random LCG), temperature as in SamplingStrategy::SoftMax */
 int ifa_engine_add_query_ex(ifa_engine *e, const int *tokens, int n_tokens, int strategy_id, int random_seed, float temperature);
+/* the same with QueryOptions::logprobs: -1 off; 0: the chosen token's log-probability; 1..20: also the n most probable tokens
+ * with theirs (softmax over the full vocabulary at temperature 1).  The query's steps end in the device candidate pool of
+ * max(the sampler's pool length, n, 1) entries plus the row's log-sum-exp (ifa_logsumexp_rows): log p = float(value) - lse;
+ * tokens, rules and draws are those of the same query without logprobs.  Limits: a multi-device engine, or
+ * return_output_tensors = true, returns -1 with a message; any other value of logprobs too. */
+int ifa_engine_add_query_lp(ifa_engine *e, const int *tokens, int n_tokens, int strategy_id, int random_seed, float temperature, int logprobs);
+/* logprobs of the query's most recent step (after ifa_engine_infer): *chosen = log p of the token the step chose; ids / logprobs
+ * [min(cap, *n)] = the *n most probable tokens, best first.  1 ok, 0 failure (unknown id, or a query without logprobs). */
+int ifa_engine_last_logprobs(ifa_engine *e, int query_id, float *chosen, int *ids, float *logprobs, int cap, int *n);
+/* InferenceEngine::ScoreTokens: logprobs_out[i] = log p(tokens[i + 1] | tokens[0..i]) for i = 0 .. n_tokens - 2, reduced on the
+ * device (ifa_model_forward_score on a free KV slot; n_tokens < max_context_len; single-device engines).  1 ok, 0 failure. */
+int ifa_engine_score(ifa_engine *e, const int *tokens, int n_tokens, float *logprobs_out);
 /* GetSamplingStrategyId(name): "sample.top_p", "greedy", ...; NULL/"" = the loaded model's default; 0 if unknown */
 int ifa_engine_strategy_id(ifa_engine *e, const char *name);
 /* host-only (no GPU): StdSamplingStrategy::ChooseTokens (src/transformer/sampling_strategy.cc:359-431) on one F16 logits
@@ -75,6 +87,11 @@ int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_token
  * no active query.  1 ok (PPL, its error estimate, scored-token count), 0 failure. */
 int ifa_engine_perplexity(ifa_engine *e, const int *tokens, int n_tokens, int max_length, int stride,
                           double *ppl, double *ppl_stderr, long long *count);
+/* the same harness with every window scored on the device (ifa_engine_score's path: the rows' log-sum-exp and target logits come
+ * back, no [T][vocab] block): same windows, double sums and statistics.  Needs a single-device engine with
+ * return_output_tensors = false in the .ini (the opposite of the call above) and no active query. */
+int ifa_engine_perplexity_device(ifa_engine *e, const int *tokens, int n_tokens, int max_length, int stride,
+                                 double *ppl, double *ppl_stderr, long long *count);
 
 /* host-only: -log softmax(logits)[token_id] of one F16 logits row with the tool's arithmetic (perplexity.cc:100-119); < 0 on bad arguments */
 double ifa_perplexity_token_nll(const uint16_t *logits_f16, int vocab, int token_id);
@@ -114,6 +131,12 @@ int ifa_service_format_response(const int *token_ids, int n, int is_end, int is_
  * {ok, hung, ret_code, is_end, finish_reason, token_ids, active, openai}.  0, or -1 on bad arguments / a small buffer. */
 int ifa_service_selftest_loop(int max_ctx, int max_queries, int fail_at_infer_call, const int *prompt, int n_prompt, int max_output_len,
                               int eos_token_id, int n_requests, int timeout_ms, char *out_json, size_t cap);
+
+/* host-only: one request body through the parser and the loop over the same loopback engine (which answers a query with logprobs
+ * by a fixed table: candidate j of a step is (next + j) % 1000 with log p = -0.25 - j): writes {ok, ret_code, chunks: [the streamed
+ * payloads], final: the final message} with time_cost zeroed.  The body's fields are the service's: prompt_token_ids, max_output_len /
+ * max_tokens, is_streaming_mode / stream, "logprobs": true, "top_logprobs": n (0..20) ... */
+int ifa_service_selftest_request(const char *body, int is_openai_mode, int max_ctx, char *out_json, size_t cap);
 
 #ifdef __cplusplus
 }

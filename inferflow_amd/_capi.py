@@ -94,6 +94,8 @@ SIGNATURES = {
     "ifa_argmax": (_i, [_vp, _sz, _vp, _vp]),
     "ifa_argmax_masked": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "ifa_topk_pool": (_i, [_vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_logsumexp_workspace": (_sz, [_sz, _sz]),
+    "ifa_logsumexp_rows": (_i, [_vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ifa_model_create": (_i, [_vp, C.POINTER(_vp)]),
     "ifa_model_destroy": (_i, [_vp]),
     "ifa_model_set_tensor": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _sz]),
@@ -115,6 +117,8 @@ SIGNATURES = {
     "ifa_model_decode_pool": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_decode_batch_pool": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "ifa_model_forward_pool": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ifa_model_pool_lse": (_i, [_vp, _vp, _i, _vp]),
+    "ifa_model_forward_score": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_get_buffer": (_i, [_vp, C.c_char_p, _i, C.POINTER(_vp), C.POINTER(_sz)]),
     "ifa_model_stream": (_vp, [_vp]),
     "ifa_model_time_kernel": (_i, [_vp, _i, _i, _vp]),
@@ -165,6 +169,9 @@ ENGINE_SIGNATURES = {
     "ifa_engine_last_error": (C.c_char_p, []),
     "ifa_engine_add_query": (_i, [_vp, _ip, _i]),
     "ifa_engine_add_query_ex": (_i, [_vp, _ip, _i, _i, _i, _f]),
+    "ifa_engine_add_query_lp": (_i, [_vp, _ip, _i, _i, _i, _f, _i]),
+    "ifa_engine_last_logprobs": (_i, [_vp, _i, C.POINTER(_f), _ip, C.POINTER(_f), _i, _ip]),
+    "ifa_engine_score": (_i, [_vp, _ip, _i, C.POINTER(_f)]),
     "ifa_engine_strategy_id": (_i, [_vp, C.c_char_p]),
     "ifa_sampling_choose": (_i, [_vp, _i, _i, _i, _f, _i, _f, C.c_longlong, _i, _ip, C.POINTER(_f), _ip, C.POINTER(_f), _i]),
     "ifa_sampling_choose_ex": (_i, [_vp, _i, _i, C.POINTER(_f), _f, C.c_longlong, _i, _ip, C.POINTER(_f), _ip, C.POINTER(_f), _i, C.POINTER(_f), _ip, _i]),
@@ -178,6 +185,7 @@ ENGINE_SIGNATURES = {
     "ifa_engine_perf_stat": (_i, [_vp, _vp, _vp, _i]),
     "ifa_engine_generate": (_i, [_vp, _i, _i, _ip, C.POINTER(_f)]),
     "ifa_engine_perplexity": (_i, [_vp, _ip, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
+    "ifa_engine_perplexity_device": (_i, [_vp, _ip, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "ifa_perplexity_token_nll": (C.c_double, [_vp, _i, _i]),
     "ifa_engine_model_info": (_i, [_vp, C.c_char_p]),
     "ifa_engine_worker": (_vp, [_vp, _i]),
@@ -185,6 +193,7 @@ ENGINE_SIGNATURES = {
     "ifa_service_parse_request": (_i, [C.c_char_p, _i, C.c_char_p, _sz]),
     "ifa_service_format_response": (_i, [_ip, _i, _i, _i, _i, _i, C.c_char_p, _sz]),
     "ifa_service_selftest_loop": (_i, [_i, _i, _i, _ip, _i, _i, _i, _i, _i, C.c_char_p, _sz]),
+    "ifa_service_selftest_request": (_i, [C.c_char_p, _i, _i, C.c_char_p, _sz]),
     "ifa_partition_slice": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _sz, _sz, C.POINTER(_sz)]),
     "ifa_partition_split_layers": (_i, [_i, _i, _ip, _i]),
 }

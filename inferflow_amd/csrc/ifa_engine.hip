@@ -325,6 +325,7 @@ int ifa_model_destroy(ifa_model *m)
     if (m->st_keys) (void)hipFree(m->st_keys);
     if (m->st_counter) (void)hipFree(m->st_counter);
     pool_free(m);
+    score_free(m);
     if (m->stream) (void)ifa_gemm_release_stream((ifa_stream)m->stream);
     if (m->stream && m->own_stream) (void)hipStreamDestroy(m->stream);
     if (m->side_stream) (void)hipStreamDestroy(m->side_stream);
@@ -539,6 +540,7 @@ int ifa_model_select_kv(ifa_model *m, int slot)
 int ifa_model_set_option(ifa_model *m, const char *name, int value)
 {
     IFA_REQUIRE(m && name, "ifa_model_set_option: null pointer");
+    if (strcmp(name, "pool_lse") == 0) { m->opt_pool_lse = value != 0; return IFA_OK; }      // (nothing captured depends on it: the graphs stay)
     struct { const char *n; int *p; } opts[] = {
         {"fused", &m->opt_fused}, {"graph", &m->opt_graph}, {"rpw_qkv", &m->opt_rpw_qkv}, {"rpw_wo", &m->opt_rpw_wo},
         {"rpw_ffn", &m->opt_rpw_ffn}, {"rpw_w2", &m->opt_rpw_w2}, {"rpw_lm", &m->opt_rpw_lm}, {"trace", &m->opt_trace},

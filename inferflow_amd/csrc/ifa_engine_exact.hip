@@ -166,6 +166,7 @@ int forward_exact(ifa_model *m, int token, int pos, void *logits_out, int *next_
     if ((rc = ifa_argmax_masked(m->logits, lm.rows, m->state + 3, m->state, s))) return rc;
     IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned, m->state, sizeof(int), hipMemcpyDeviceToHost, m->stream));
     if ((rc = pool_enqueue(m, m->logits, 1))) return rc;
+    if ((rc = score_enqueue(m, m->logits, 1))) return rc;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     if (next_token) *next_token = m->host_pinned[0];
     return IFA_OK;

@@ -373,7 +373,8 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
         if (next_token) *next_token = m->host_pinned[0];
         return IFA_OK;
     }
-    if (no_head && !logits_out) return IFA_OK;
+    const bool all_rows = logits_out || m->score.n > 0;      // the lm_head over every row: for the caller's buffer, or for a scoring prompt
+    if (no_head && !all_rows) return IFA_OK;
     PerfSpan sp_out(m, 1000009);         // (ProcessPostLayer: output norm + lm_head, inference_worker.cc:326-336, 673-675)
     if (scale_on(c.out_scale) && (rc = ifa_scale(x, c.out_scale, (size_t)T * D, x, s))) return rc;
     const half_t *hfin = x;
@@ -385,8 +386,8 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
     }
     const Tensor &lm = m->g[T_LM_HEAD];
     const size_t V = lm.rows;                        // (this rank's vocabulary shard under tensor parallelism)
-    int t0 = logits_out ? 0 : T - 1;
-    if (logits_out) { if ((rc = matmul(m, hfin, T, lm, none, m->logits))) return rc; }
+    int t0 = all_rows ? 0 : T - 1;
+    if (all_rows) { if ((rc = matmul(m, hfin, T, lm, none, m->logits))) return rc; }
     else if (lm.dtype == F16 && D % 8 == 0 && D <= 8192) {
         // the last row only: the decode step's lm_head kernel on the normalised row (same per-row chain as the op-level GEMV --
         // bit-identical logits -- at 6 TB/s instead of 1.1: 232 -> 45 us per prompt, rocprofv3 r06)
@@ -405,6 +406,7 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
         if ((rc = ifa_argmax_masked(m->logits + (size_t)(T - 1) * V, V, m->state + 3, m->state, s))) return rc;
         IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned, m->state, sizeof(int), hipMemcpyDeviceToHost, m->stream));
         if ((rc = pool_enqueue(m, m->logits + (size_t)(T - 1) * V, 1))) return rc;
+        if ((rc = score_enqueue(m, m->logits, T))) return rc;
     }
     const auto host_t1 = std::chrono::steady_clock::now();
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));

@@ -8,11 +8,14 @@
 namespace ifa {
 int topk_pool_rows(const void *logits, size_t row_stride, const int *row_idx_dev, size_t rows, size_t n, int k, const unsigned *excl,
                    int *ids_out, void *vals_out, int *count_out, hipStream_t s);
+int lse_rows(const void *logits, size_t row_stride, const int *row_idx_dev, size_t rows, size_t n, const int *targets_dev, float *lse_out,
+             float *target_out, float *part_dev, hipStream_t s);
 }
 
 namespace ifae {
 
-static size_t pool_block_bytes(int n_sel, int k) { return (size_t)n_sel * 4 + (size_t)n_sel * (size_t)k * 6; }
+// counts [n_sel] | (with_lse: lse [n_sel] |) ids [n_sel][k] | F16 bits [n_sel][k]
+static size_t pool_block_bytes(int n_sel, int k, bool with_lse) { return (size_t)n_sel * (with_lse ? 8 : 4) + (size_t)n_sel * (size_t)k * 6; }
 
 void pool_free(ifa_model *m)
 {
@@ -28,7 +31,7 @@ void pool_free(ifa_model *m)
 // staging for n_sel rows of k entries (grown on demand, outside any capture; one allocation serves every later step)
 static int pool_reserve(ifa_model *m, int n_sel, int k)
 {
-    const size_t bytes = pool_block_bytes(std::max(n_sel, 8), IFA_POOL_MAX >= k ? IFA_POOL_MAX : k);
+    const size_t bytes = pool_block_bytes(std::max(n_sel, 8), IFA_POOL_MAX >= k ? IFA_POOL_MAX : k, true);
     if (bytes > m->pool_bytes) {
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
         if (m->pool_dev) (void)hipFree(m->pool_dev);
@@ -57,11 +60,14 @@ int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
     if (R.k <= 0) return IFA_OK;
     const size_t V = m->g[T_LM_HEAD].rows;
     const int k = R.k, n_sel = R.n_sel;
-    int *counts = (int *)m->pool_dev, *ids = counts + n_sel;
+    int *counts = (int *)m->pool_dev;
+    float *lse = R.lse ? (float *)(counts + n_sel) : nullptr;
+    int *ids = counts + (R.lse ? 2 : 1) * n_sel;
     uint16_t *vals = (uint16_t *)(ids + (size_t)n_sel * k);
     int rc = IFA_OK;
     if (!R.rows_sel) {                 // a single-query step: its one row
         if ((rc = topk_pool_rows(logits, V, nullptr, 1, V, k, m->pool_excl, ids, vals, counts, m->stream))) return rc;
+        if (lse && (rc = lse_rows(logits, V, nullptr, 1, V, nullptr, lse, nullptr, m->lse_part, m->stream))) return rc;
         R.done = 1;
     } else {                           // a batched step (or one chunk of it): the wanted rows among [chunk0, chunk0 + n_rows)
         int j0 = R.done, j1 = j0;
@@ -71,11 +77,12 @@ int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
             IFA_HIP_CHECK(hipMemcpyAsync(m->pool_idx_dev + j0, m->pool_idx_pin + j0, sizeof(int) * (size_t)(j1 - j0), hipMemcpyHostToDevice, m->stream));
             if ((rc = topk_pool_rows(logits, V, m->pool_idx_dev + j0, (size_t)(j1 - j0), V, k, m->pool_excl, ids + (size_t)j0 * k, vals + (size_t)j0 * k,
                                      counts + j0, m->stream))) return rc;
+            if (lse && (rc = lse_rows(logits, V, m->pool_idx_dev + j0, (size_t)(j1 - j0), V, nullptr, lse + j0, nullptr, m->lse_part, m->stream))) return rc;
         }
         R.done = j1;
         if (!R.last_chunk) return IFA_OK;
     }
-    IFA_HIP_CHECK(hipMemcpyAsync(m->pool_pin, m->pool_dev, pool_block_bytes(n_sel, k), hipMemcpyDeviceToHost, m->stream));
+    IFA_HIP_CHECK(hipMemcpyAsync(m->pool_pin, m->pool_dev, pool_block_bytes(n_sel, k, R.lse), hipMemcpyDeviceToHost, m->stream));
     return IFA_OK;
 }
 
@@ -88,7 +95,10 @@ static int pool_arm(ifa_model *m, int k, int n_sel, const int *rows_sel, const c
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
     int rc = pool_reserve(m, n_sel, k);
     if (rc) return rc;
+    if (m->opt_pool_lse && (rc = lse_part_reserve(m))) return rc;
+    m->pool_lse_last.clear();
     m->pool = ifa_model::PoolReq();
+    m->pool.lse = m->opt_pool_lse != 0;
     m->pool.k = k; m->pool.n_sel = n_sel; m->pool.rows_sel = rows_sel;
     return IFA_OK;
 }
@@ -100,7 +110,8 @@ static int pool_finish(ifa_model *m, int step_rc, int *ids_host, unsigned short 
     m->pool = ifa_model::PoolReq();
     if (step_rc) return step_rc;
     if (R.done != R.n_sel) return ifa_fail(IFA_ERR_STATE, "%s: the step served %d of %d pools", who, R.done, R.n_sel);
-    const int *counts = (const int *)m->pool_pin, *ids = counts + R.n_sel;
+    const int *counts = (const int *)m->pool_pin, *ids = counts + (R.lse ? 2 : 1) * R.n_sel;
+    if (R.lse) m->pool_lse_last.assign((const float *)(counts + R.n_sel), (const float *)(counts + R.n_sel) + R.n_sel);
     const uint16_t *vals = (const uint16_t *)(ids + (size_t)R.n_sel * R.k);
     memcpy(counts_host, counts, sizeof(int) * (size_t)R.n_sel);
     memcpy(ids_host, ids, sizeof(int) * (size_t)R.n_sel * R.k);
@@ -130,6 +141,16 @@ int ifa_model_set_pool_excluded(ifa_model *m, const int *ids_host, int n)
     for (int i = 0; i < n; i++) bits[(size_t)ids_host[i] >> 5] |= 1u << (ids_host[i] & 31);
     if (!m->pool_excl) IFA_HIP_CHECK(hipMalloc((void **)&m->pool_excl, words * sizeof(unsigned)));
     IFA_HIP_CHECK(hipMemcpy(m->pool_excl, bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice));
+    return IFA_OK;
+}
+
+int ifa_model_pool_lse(ifa_model *m, float *lse_host, int cap, int *n_out)
+{
+    IFA_REQUIRE(m && n_out && cap >= 0 && (cap == 0 || lse_host), "ifa_model_pool_lse: bad arguments");
+    const int n = (int)m->pool_lse_last.size();
+    if (n > cap) return ifa_fail(IFA_ERR_ARG, "ifa_model_pool_lse: the last pool step staged %d values, room for %d", n, cap);
+    if (n) memcpy(lse_host, m->pool_lse_last.data(), sizeof(float) * (size_t)n);
+    *n_out = n;
     return IFA_OK;
 }
 

@@ -1,0 +1,104 @@
+// ifa_engine_score.hip -- a prompt that ends in log-probabilities instead of a logits block (ifa_model_forward_score): the entry
+// point arms m->score, runs ifa_model_forward -- with the request armed the lm_head runs over ALL rows into the worker's own
+// m->logits, exactly as it does for a caller's logits_out_dev -- and every route that call takes (one pass, the two passes of a
+// 34..48-token prompt, exact_order's row-by-row steps, perf_stat's op-by-op layer) calls score_enqueue() on the rows it has just
+// written: the row log-sum-exp + target gather (csrc/ifa_logprob.hip) and, behind the last row, ONE copy of 2 * n floats into
+// pinned staging, all in front of that route's synchronisation.  No [T][vocab] block leaves the worker.
+#include "ifa_engine_state.h"
+
+namespace ifa {
+int lse_rows(const void *logits, size_t row_stride, const int *row_idx_dev, size_t rows, size_t n, const int *targets_dev, float *lse_out,
+             float *target_out, float *part_dev, hipStream_t s);
+}
+
+namespace ifae {
+
+void score_free(ifa_model *m)
+{
+    if (m->score_tgt_dev) (void)hipFree(m->score_tgt_dev);
+    if (m->score_tgt_pin) (void)hipHostFree(m->score_tgt_pin);
+    if (m->score_dev) (void)hipFree(m->score_dev);
+    if (m->score_pin) (void)hipHostFree(m->score_pin);
+    if (m->lse_part) (void)hipFree(m->lse_part);
+    m->score_tgt_dev = m->score_tgt_pin = nullptr; m->score_dev = m->score_pin = nullptr; m->lse_part = nullptr;
+    m->score_cap = 0;
+}
+
+int lse_part_reserve(ifa_model *m)
+{
+    if (!m->lse_part) IFA_HIP_CHECK(hipMalloc((void **)&m->lse_part, LSE_PART_FLOATS * sizeof(float)));
+    return IFA_OK;
+}
+
+// staging for n rows (grown on demand, outside any step)
+static int score_reserve(ifa_model *m, int n)
+{
+    int rc = lse_part_reserve(m);
+    if (rc) return rc;
+    if ((size_t)n <= m->score_cap) return IFA_OK;
+    IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if (m->score_tgt_dev) (void)hipFree(m->score_tgt_dev);
+    if (m->score_tgt_pin) (void)hipHostFree(m->score_tgt_pin);
+    if (m->score_dev) (void)hipFree(m->score_dev);
+    if (m->score_pin) (void)hipHostFree(m->score_pin);
+    m->score_tgt_dev = m->score_tgt_pin = nullptr; m->score_dev = m->score_pin = nullptr; m->score_cap = 0;
+    const size_t cap = (size_t)std::max(n, 64);
+    IFA_HIP_CHECK(hipMalloc((void **)&m->score_tgt_dev, cap * sizeof(int)));
+    IFA_HIP_CHECK(hipHostMalloc((void **)&m->score_tgt_pin, cap * sizeof(int), hipHostMallocDefault));
+    IFA_HIP_CHECK(hipMalloc((void **)&m->score_dev, 2 * cap * sizeof(float)));
+    IFA_HIP_CHECK(hipHostMalloc((void **)&m->score_pin, 2 * cap * sizeof(float), hipHostMallocDefault));
+    m->score_cap = cap;
+    return IFA_OK;
+}
+
+int score_enqueue(ifa_model *m, const half_t *logits, int n_rows)
+{
+    ifa_model::ScoreReq &R = m->score;
+    if (R.n <= 0) return IFA_OK;
+    if (n_rows <= 0 || R.done + n_rows > R.n) return ifa_fail(IFA_ERR_STATE, "score: a step of %d rows after %d of %d", n_rows, R.done, R.n);
+    const size_t V = m->g[T_LM_HEAD].rows;
+    // lse [n] | target logit [n]: the parts of a prompt taken in several steps land side by side
+    int rc = lse_rows(logits, V, nullptr, (size_t)n_rows, V, m->score_tgt_dev + R.done, m->score_dev + R.done, m->score_dev + R.n + R.done,
+                      m->lse_part, m->stream);
+    if (rc) return rc;
+    R.done += n_rows;
+    if (R.done == R.n)
+        IFA_HIP_CHECK(hipMemcpyAsync(m->score_pin, m->score_dev, sizeof(float) * 2 * (size_t)R.n, hipMemcpyDeviceToHost, m->stream));
+    return IFA_OK;
+}
+
+} // namespace ifae
+
+extern "C" {
+
+int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, const int *targets_host,
+                            float *lse_host, float *target_logit_host, int *next_token_host)
+{
+    IFA_REQUIRE(m && m->finalized, "ifa_model_forward_score: model not finalized");
+    IFA_REQUIRE(tokens_host && n_tokens >= 1 && targets_host && lse_host && target_logit_host, "ifa_model_forward_score: bad arguments");
+    if (m->cfg.tp_size > 1 || m->topo)
+        return ifa_fail(IFA_ERR_STATE, "ifa_model_forward_score: the vocabulary of a partitioned worker is sharded; score on the host there");
+    if (!m->g[T_LM_HEAD].present()) return ifa_fail(IFA_ERR_STATE, "ifa_model_forward_score: lm_head missing (pipeline stage worker)");
+    const size_t V = m->g[T_LM_HEAD].rows;
+    for (int i = 0; i < n_tokens; i++)
+        IFA_REQUIRE(targets_host[i] < 0 || (size_t)targets_host[i] < V, "ifa_model_forward_score: target %d outside the vocabulary", targets_host[i]);
+    IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
+    int rc = score_reserve(m, n_tokens);
+    if (rc) return rc;
+    memcpy(m->score_tgt_pin, targets_host, sizeof(int) * (size_t)n_tokens);
+    IFA_HIP_CHECK(hipMemcpyAsync(m->score_tgt_dev, m->score_tgt_pin, sizeof(int) * (size_t)n_tokens, hipMemcpyHostToDevice, m->stream));
+    m->score = ifa_model::ScoreReq();
+    m->score.n = n_tokens;
+    int next = -1;
+    rc = ifa_model_forward(m, tokens_host, n_tokens, prefix_len, nullptr, &next);
+    const ifa_model::ScoreReq R = m->score;
+    m->score = ifa_model::ScoreReq();
+    if (rc) return rc;
+    if (R.done != R.n) return ifa_fail(IFA_ERR_STATE, "ifa_model_forward_score: the prompt served %d of %d rows", R.done, R.n);
+    memcpy(lse_host, m->score_pin, sizeof(float) * (size_t)n_tokens);
+    memcpy(target_logit_host, m->score_pin + n_tokens, sizeof(float) * (size_t)n_tokens);
+    if (next_token_host) *next_token_host = next;
+    return IFA_OK;
+}
+
+} // extern "C"

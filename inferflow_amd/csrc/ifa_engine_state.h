@@ -200,10 +200,25 @@ struct ifa_model {
         const int *rows_sel = nullptr;         // batched step: ascending row indices (host); null: the step's one row
         int chunk0 = 0; bool last_chunk = true;      // batched step taken as several steps: first row / last step of this one
         int done = 0;                          // rows whose pool has been enqueued
+        bool lse = false;                      // option pool_lse at arming: the rows' log-sum-exp ride in the block
     } pool;
     unsigned *pool_excl = nullptr;             // device bitmask of ids the pool never offers (null: none)
     void *pool_dev = nullptr, *pool_pin = nullptr; size_t pool_bytes = 0;      // result block, device / pinned
     int *pool_idx_dev = nullptr, *pool_idx_pin = nullptr; size_t pool_idx_cap = 0;
+    // option pool_lse = 1: the pool steps also deliver the log-sum-exp of every pooled row (csrc/ifa_logprob.hip; log p = value - lse).
+    // The block then reads counts [n_sel] | lse [n_sel] | ids | F16 bits, still one copy; ifa_model_pool_lse hands out the last step's.
+    int opt_pool_lse = 0;
+    std::vector<float> pool_lse_last;
+    float *lse_part = nullptr;                 // device: (max, sum) pairs of the rows a launch splits over workgroups (LSE_PART_FLOATS)
+    // Scoring prompt (ifa_model_forward_score, ifa_engine_score.hip): armed like `pool`; the prompt runs its lm_head over all rows
+    // and every route calls score_enqueue() on the rows it has just written, in front of its synchronisation.
+    struct ScoreReq {
+        int n = 0;                             // > 0: armed, rows wanted in all
+        int done = 0;                          // rows whose launch has been enqueued
+    } score;
+    int *score_tgt_dev = nullptr, *score_tgt_pin = nullptr;     // [cap] target ids
+    float *score_dev = nullptr, *score_pin = nullptr;           // lse [cap] | target logit [cap]
+    size_t score_cap = 0;
     static constexpr int RING = 1024;
 };
 
@@ -350,6 +365,13 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
 // block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.
 int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
 void pool_free(ifa_model *m);
+// ---- ifa_engine_score.hip
+static constexpr size_t LSE_PART_FLOATS = 256;      // rows * splits <= 128 pairs whatever the row count (ifa_logprob.hip, lse_splits)
+int lse_part_reserve(ifa_model *m);
+// armed (m->score.n > 0): the row log-sum-exp + target gather over `logits` ([n_rows][vocab], the next n_rows rows of the prompt); after
+// the last row the copy of the 2 * n floats into pinned staging.  A no-op otherwise.
+int score_enqueue(ifa_model *m, const half_t *logits, int n_rows);
+void score_free(ifa_model *m);
 // ---- ifa_engine_moe.hip
 int launch_moe_router(ifa_model *m, int l);
 // Mixture of experts (ProcessGpuLayer_Moe, inference_worker.cc:1924-2146): router GEMV -> softmax -> D2H ->

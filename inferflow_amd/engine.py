@@ -45,9 +45,13 @@ class InferenceEngine:
         except Exception:
             pass
 
-    def add_query(self, tokens, strategy=None, seed=0, temperature=1.0):
-        """strategy: None (the model's default) or a name / SamplingStrategyId ("sample.top_p", "greedy", 1 ...)"""
+    def add_query(self, tokens, strategy=None, seed=0, temperature=1.0, logprobs=-1):
+        """strategy: None (the model's default) or a name / SamplingStrategyId ("sample.top_p", "greedy", 1 ...).
+        logprobs: -1 off; 0: the chosen token's log-probability; 1..20: also the n most probable tokens (last_logprobs)."""
         arr = (C.c_int * len(tokens))(*[int(t) for t in tokens])
+        if logprobs != -1:
+            sid = 0 if strategy is None else (strategy if isinstance(strategy, int) else self.strategy_id(strategy))
+            return _capi.lib().ifa_engine_add_query_lp(self._h, arr, len(tokens), int(sid), int(seed), float(temperature), int(logprobs))
         if strategy is None and seed == 0 and temperature == 1.0:
             return _capi.lib().ifa_engine_add_query(self._h, arr, len(tokens))
         sid = 0 if strategy is None else (strategy if isinstance(strategy, int) else self.strategy_id(strategy))
@@ -97,6 +101,22 @@ class InferenceEngine:
             _capi.lib().ifa_engine_last_logits(self._h, query_id, out.ctypes.data_as(C.c_void_p), out.size, C.byref(rows), C.byref(cols))
         return out
 
+    def last_logprobs(self, query_id, cap=32):
+        """(log p of the token the query's last step chose, [(token id, log p)] of its most probable tokens, best first)"""
+        chosen, n = C.c_float(0), C.c_int(0)
+        ids = (C.c_int * cap)(); lps = (C.c_float * cap)()
+        if not _capi.lib().ifa_engine_last_logprobs(self._h, int(query_id), C.byref(chosen), ids, lps, cap, C.byref(n)):
+            raise EngineError(self._err())
+        return chosen.value, [(ids[i], lps[i]) for i in range(min(n.value, cap))]
+
+    def score(self, tokens):
+        """float32 [len(tokens) - 1]: log p(tokens[i + 1] | tokens[:i + 1]), reduced on the device (InferenceEngine::ScoreTokens)"""
+        arr = (C.c_int * len(tokens))(*[int(t) for t in tokens])
+        out = np.zeros(max(len(tokens) - 1, 1), np.float32)
+        if not _capi.lib().ifa_engine_score(self._h, arr, len(tokens), out.ctypes.data_as(C.POINTER(C.c_float))):
+            raise EngineError("score failed: " + self._err())
+        return out[:len(tokens) - 1]
+
     def generate(self, query_id, n_steps):
         out = (C.c_int * max(1, n_steps))()
         ms = C.c_float(0)
@@ -105,11 +125,13 @@ class InferenceEngine:
             raise EngineError("Generate failed: " + self._err())
         return [out[i] for i in range(n)], ms.value
 
-    def perplexity(self, tokens, max_length=512, stride=512):
-        """(PPL, error estimate, scored tokens) of a token-id stream -- the reference's perplexity tool."""
+    def perplexity(self, tokens, max_length=512, stride=512, device_scoring=False):
+        """(PPL, error estimate, scored tokens) of a token-id stream -- the reference's perplexity tool.  device_scoring: every
+        window is scored on the device (an engine with return_output_tensors = false; the default needs it true)."""
         arr = (C.c_int * len(tokens))(*[int(t) for t in tokens])
         ppl, err, cnt = C.c_double(0), C.c_double(0), C.c_longlong(0)
-        if not _capi.lib().ifa_engine_perplexity(self._h, arr, len(tokens), max_length, stride, C.byref(ppl), C.byref(err), C.byref(cnt)):
+        fn = _capi.lib().ifa_engine_perplexity_device if device_scoring else _capi.lib().ifa_engine_perplexity
+        if not fn(self._h, arr, len(tokens), max_length, stride, C.byref(ppl), C.byref(err), C.byref(cnt)):
             raise EngineError("perplexity failed: " + self._err())
         return ppl.value, err.value, cnt.value
 

@@ -49,6 +49,35 @@ int ifa_engine_add_query_ex(ifa_engine *e, const int *tokens, int n_tokens, int 
     return e->engine.AddQuery(std::vector<int>(tokens, tokens + n_tokens), opt);
 }
 
+int ifa_engine_add_query_lp(ifa_engine *e, const int *tokens, int n_tokens, int strategy_id, int random_seed, float temperature, int logprobs)
+{
+    if (!e || !tokens || n_tokens <= 0) { EngineSetError("ifa_engine_add_query_lp: bad arguments"); return -1; }
+    QueryOptions opt; opt.strategy_id = strategy_id; opt.random_seed = random_seed; opt.temperature = temperature; opt.logprobs = logprobs;
+    return e->engine.AddQuery(std::vector<int>(tokens, tokens + n_tokens), opt);
+}
+
+int ifa_engine_last_logprobs(ifa_engine *e, int query_id, float *chosen, int *ids, float *logprobs, int cap, int *n)
+{
+    if (!e || cap < 0 || (cap > 0 && (!ids || !logprobs))) { EngineSetError("ifa_engine_last_logprobs: bad arguments"); return 0; }
+    auto it = e->last.find(query_id);
+    if (it == e->last.end()) { EngineSetError("no result for query %d", query_id); return 0; }
+    if (!it->second.has_logprobs) { EngineSetError("query %d was added without logprobs", query_id); return 0; }
+    if (chosen) *chosen = it->second.chosen_logprob;
+    const int m = (int)it->second.top_logprobs.size();
+    for (int i = 0; i < std::min(m, cap); i++) { ids[i] = it->second.top_logprobs[(size_t)i].id; logprobs[i] = it->second.top_logprobs[(size_t)i].weight; }
+    if (n) *n = m;
+    return 1;
+}
+
+int ifa_engine_score(ifa_engine *e, const int *tokens, int n_tokens, float *logprobs_out)
+{
+    if (!e || !tokens || n_tokens < 2 || !logprobs_out) { EngineSetError("ifa_engine_score: bad arguments"); return 0; }
+    std::vector<float> lp;
+    if (!e->engine.ScoreTokens(std::vector<int>(tokens, tokens + n_tokens), lp)) return 0;
+    memcpy(logprobs_out, lp.data(), sizeof(float) * lp.size());
+    return 1;
+}
+
 int ifa_engine_strategy_id(ifa_engine *e, const char *name)
 {
     return (int)(e ? e->engine.GetSamplingStrategyId(name ? name : "") : SamplingStrategyIdFromName(name ? name : ""));
@@ -201,16 +230,28 @@ int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_token
     return (int)toks.size();
 }
 
-int ifa_engine_perplexity(ifa_engine *e, const int *tokens, int n_tokens, int max_length, int stride,
-                          double *ppl, double *ppl_stderr, long long *count)
+static int engine_perplexity(ifa_engine *e, const int *tokens, int n_tokens, int max_length, int stride, bool device_scoring,
+                             double *ppl, double *ppl_stderr, long long *count)
 {
     if (!e || !tokens || n_tokens <= 0) { EngineSetError("ifa_engine_perplexity: bad arguments"); return 0; }
     PerplexityResult r;
-    if (!ComputePerplexity(e->engine, std::vector<int>(tokens, tokens + n_tokens), max_length, stride, r)) return 0;
+    if (!ComputePerplexity(e->engine, std::vector<int>(tokens, tokens + n_tokens), max_length, stride, r, 8, device_scoring)) return 0;
     if (ppl) *ppl = r.ppl;
     if (ppl_stderr) *ppl_stderr = r.ppl_stderr;
     if (count) *count = r.count;
     return 1;
+}
+
+int ifa_engine_perplexity(ifa_engine *e, const int *tokens, int n_tokens, int max_length, int stride,
+                          double *ppl, double *ppl_stderr, long long *count)
+{
+    return engine_perplexity(e, tokens, n_tokens, max_length, stride, false, ppl, ppl_stderr, count);
+}
+
+int ifa_engine_perplexity_device(ifa_engine *e, const int *tokens, int n_tokens, int max_length, int stride,
+                                 double *ppl, double *ppl_stderr, long long *count)
+{
+    return engine_perplexity(e, tokens, n_tokens, max_length, stride, true, ppl, ppl_stderr, count);
 }
 
 int ifa_engine_model_info(ifa_engine *e, const char *key)
@@ -274,7 +315,8 @@ int ifa_service_parse_request(const char *body, int is_openai_mode, char *out_js
     char tmp[64]; snprintf(tmp, sizeof tmp, "%.4f", r.temperature);
     const std::string js = "{\"prompt_token_ids\": " + ids + ", \"max_output_len\": " + std::to_string(r.max_output_len) + ", \"decoding_alg\": \"" + r.decoding_alg
         + "\", \"random_seed\": " + std::to_string(r.random_seed) + ", \"temperature\": " + tmp + ", \"is_streaming_mode\": " + (r.is_streaming_mode ? "true" : "false")
-        + ", \"eos_token_id\": " + std::to_string(r.eos_token_id) + ", \"fn\": \"" + r.fn + "\"}";
+        + ", \"eos_token_id\": " + std::to_string(r.eos_token_id) + ", \"fn\": \"" + r.fn + "\""
+        + (r.logprobs >= 0 ? ", \"logprobs\": " + std::to_string(r.logprobs) : std::string()) + "}";
     if (js.size() + 1 > cap) return -1;
     memcpy(out_json, js.c_str(), js.size() + 1);
     return 0;
@@ -299,15 +341,17 @@ int ifa_service_format_response(const int *token_ids, int n, int is_end, int is_
 // without items; Commit appends, is_end ends) over a trivial "model": next token = (last + 1) % vocab.
 namespace {
 struct LoopbackEngine : QueryEngine {
-    struct Q { std::vector<int> tokens; int processed = 0; bool ended = false; };
+    struct Q { std::vector<int> tokens; int processed = 0; bool ended = false; int logprobs = -1; };
     std::map<int, Q> qs;
     int max_ctx, max_queries, fail_at, vocab = 1000, next_id = 1, infer_calls = 0;
     LoopbackEngine(int ctx, int mq, int fail) : max_ctx(ctx), max_queries(mq), fail_at(fail) {}
-    int AddQuery(const std::vector<int> &t, const QueryOptions &) override {
+    int AddQuery(const std::vector<int> &t, const QueryOptions &o) override {
         if (t.empty() || (int)t.size() >= max_ctx) return -1;
+        if (o.logprobs < -1 || o.logprobs > QueryOptions::MAX_LOGPROBS) return -1;       // (InferenceEngine::AddQuery's rule)
         if ((int)qs.size() >= max_queries) return 0;
-        Q q; q.tokens = t; qs[next_id] = q; return next_id++;
+        Q q; q.tokens = t; q.logprobs = o.logprobs; qs[next_id] = q; return next_id++;
     }
+    bool SupportsLogprobs() const override { return true; }
     int QueryCount() const override { return (int)qs.size(); }
     bool Infer(InferenceResult &res) override {
         res.items.clear();
@@ -322,6 +366,10 @@ struct LoopbackEngine : QueryEngine {
             QueryInferenceResult item; item.query_id = kv.first; item.prefix_len = q.processed;
             IdWeight w; w.id = (q.tokens.back() + 1) % vocab; w.weight = 1.0f;
             item.next_tokens.push_back(w);
+            if (q.logprobs >= 0) {           // a fixed "distribution": candidate j is (next + j) % vocab with log p = -0.25 - j
+                item.has_logprobs = true; item.chosen_logprob = -0.25f;
+                for (int j = 0; j < q.logprobs; j++) { IdWeight c; c.id = (w.id + j) % vocab; c.weight = -0.25f - (float)j; item.top_logprobs.push_back(c); }
+            }
             q.processed = (int)q.tokens.size();
             res.items.push_back(item);
         }
@@ -371,6 +419,39 @@ int ifa_service_selftest_loop(int max_ctx, int max_queries, int fail_at_infer_ca
     }
     core.Stop();
     js += "]";
+    if (js.size() + 1 > cap) return -1;
+    memcpy(out_json, js.c_str(), js.size() + 1);
+    return 0;
+}
+
+// one request BODY through the parser and the loop over the loopback engine, the way the HTTP front handles it: writes
+// {"ok", "ret_code", "chunks": [the streamed payloads' JSON ...], "final": the final message}.  0, or -1 on bad arguments / a small buffer.
+int ifa_service_selftest_request(const char *body, int is_openai_mode, int max_ctx, char *out_json, size_t cap)
+{
+    if (!body || !out_json || cap == 0) return -1;
+    InferFlowRequest req;
+    std::string perr, js;
+    if (!InferFlowServiceCore::ParseRequest(req, body, is_openai_mode != 0, &perr)) js = "{\"ok\": false, \"ret_code\": \"" + perr + "\", \"chunks\": [], \"final\": null}";
+    else {
+        LoopbackEngine eng(max_ctx, 4, 0);
+        InferFlowServiceCore core(eng);
+        core.Start();
+        std::string chunks;
+        std::function<bool(const InferFlowResponseChunk &)> on_chunk = [&](const InferFlowResponseChunk &c) {
+            std::string one;
+            if (is_openai_mode) c.ToJsonOpenAI(one, true, "ifa-test");
+            else { InferFlowResponseChunk cc = c; cc.ret_code = c.is_end ? "succ" : ""; cc.time_cost = 0; cc.ToJson(one); }
+            chunks += (chunks.empty() ? "" : ", ") + one;
+            return true;
+        };
+        InferFlowResponseChunk res;
+        const bool ok = core.ProcessQuery(res, req, req.is_streaming_mode ? &on_chunk : nullptr);
+        core.Stop();
+        res.time_cost = 0;
+        std::string fin;
+        if (is_openai_mode) res.ToJsonOpenAI(fin, false, "ifa-test"); else res.ToJson(fin);
+        js = std::string("{\"ok\": ") + (ok ? "true" : "false") + ", \"ret_code\": \"" + res.ret_code + "\", \"chunks\": [" + chunks + "], \"final\": " + fin + "}";
+    }
     if (js.size() + 1 > cap) return -1;
     memcpy(out_json, js.c_str(), js.size() + 1);
     return 0;

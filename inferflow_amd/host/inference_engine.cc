@@ -279,7 +279,7 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
             if (ifa_model_set_excluded_tokens(mm, excl.data(), (int)excl.size()) != IFA_OK) { EngineSetError("excluded tokens: %s", ifa_last_error()); Clear(); return false; }
         // the device pool's mask has no limit: the full list
         const std::vector<int> &full = default_sampling_.excluded_ids;
-        if (config_.device_sampling_pool && !multi_ && ifa_model_set_pool_excluded(model_, full.data(), (int)full.size()) != IFA_OK) {
+        if (!multi_ && ifa_model_set_pool_excluded(model_, full.data(), (int)full.size()) != IFA_OK) {
             EngineSetError("excluded tokens of the device pool: %s", ifa_last_error()); Clear(); return false;
         }
     }
@@ -457,10 +457,16 @@ int InferenceEngine::AddQuery(const std::vector<int> &tokens, const QueryOptions
     if (query_options.strategy_id < 0 || query_options.strategy_id > (int)SamplingStrategyId::Mirostat) { EngineSetError("Invalid strategy id %d", query_options.strategy_id); return -1; }
     if (strategy == SamplingStrategyId::Auto) strategy = default_strategy_;
     if (!IsSupportedStrategy(strategy)) { EngineSetError("Decoding strategy %d is not supported", query_options.strategy_id); return -1; }
+    if (query_options.logprobs < -1 || query_options.logprobs > QueryOptions::MAX_LOGPROBS) { EngineSetError("logprobs %d is outside -1..%d", query_options.logprobs, QueryOptions::MAX_LOGPROBS); return -1; }
+    if (query_options.logprobs >= 0 && multi_) { EngineSetError("logprobs are not available on a multi-device engine (the vocabulary is sharded)"); return -1; }
+    if (query_options.logprobs >= 0 && config_.return_output_tensors) { EngineSetError("logprobs are not available with return_output_tensors = true (take them from the output tensor)"); return -1; }
     if ((int)queries_.size() >= std::min(config_.max_concurrent_queries, kv_slots_)) return 0;      // busy
     Query q; q.id = next_query_id_++; q.tokens = tokens; q.options = query_options;
     q.strategy = strategy; q.sampling = default_sampling_;
     if (query_options.random_seed != 0) q.rng.SetSeed((uint64_t)(int64_t)query_options.random_seed);    // SamplingStrategy::BeginQuery
+    if (query_options.logprobs >= 0 && PoolK(q) > IFA_POOL_MAX) {      // (its steps could not end in a device pool: no logprobs would come back)
+        EngineSetError("logprobs need the query's %d sampling candidates in one device pool of at most %d", PoolK(q), IFA_POOL_MAX); return -1;
+    }
     std::vector<bool> used((size_t)kv_slots_, false);
     for (const auto &kv : queries_) used[(size_t)kv.second.kv_slot] = true;
     while (q.kv_slot < kv_slots_ && used[(size_t)q.kv_slot]) q.kv_slot++;
@@ -523,12 +529,74 @@ bool InferenceEngine::SamplePool(Query &q, const int *ids, const uint16_t *vals,
 
 int InferenceEngine::PoolLen(const Query &q) const { return PoolLength(q.strategy, q.sampling, spec_.hyper_params.vocab_size); }
 
+int InferenceEngine::PoolK(const Query &q) const
+{
+    return q.options.logprobs >= 0 ? std::max(std::max(PoolLen(q), q.options.logprobs), 1) : PoolLen(q);
+}
+
 bool InferenceEngine::PoolRoute(const Query &q) const
 {
-    if (!config_.device_sampling_pool || config_.return_output_tensors || multi_) return false;
+    if (config_.return_output_tensors || multi_) return false;
+    const int k = PoolK(q);
+    if (q.options.logprobs >= 0) return k <= IFA_POOL_MAX;      // logprobs ride on the pool whatever device_sampling_pool says
+    if (!config_.device_sampling_pool) return false;
     if (q.strategy == SamplingStrategyId::Greedy && !host_greedy_) return false;      // (the device argmax serves it)
-    const int k = PoolLen(q);
     return k >= 1 && k <= IFA_POOL_MAX;
+}
+
+bool InferenceEngine::SetPoolLse(bool on)
+{
+    if (on == pool_lse_on_) return true;
+    if (ifa_model_set_option(model_, "pool_lse", on ? 1 : 0) != IFA_OK) { EngineSetError("pool_lse: %s", ifa_last_error()); return false; }
+    pool_lse_on_ = on;
+    return true;
+}
+
+// log p = float(value) - lse for the chosen token (it must be one of the pool's) and the pool's first `logprobs` entries
+bool InferenceEngine::FillLogprobs(const Query &q, const int *ids, const uint16_t *vals, int count, float lse, QueryInferenceResult &item)
+{
+    if (q.options.logprobs < 0) return true;
+    if (item.next_tokens.empty()) { EngineSetError("logprobs: no token was chosen for query %d", q.id); return false; }
+    const int chosen = item.next_tokens[0].id;
+    int at = -1;
+    for (int i = 0; i < count && at < 0; i++) if (ids[i] == chosen) at = i;
+    if (at < 0) { EngineSetError("logprobs: the chosen token %d of query %d is not among the %d pool entries", chosen, q.id, count); return false; }
+    item.has_logprobs = true;
+    item.chosen_logprob = HalfBitsToFloat(vals[at]) - lse;
+    item.top_logprobs.clear();
+    for (int i = 0; i < std::min(count, q.options.logprobs); i++) { IdWeight w; w.id = ids[i]; w.weight = HalfBitsToFloat(vals[i]) - lse; item.top_logprobs.push_back(w); }
+    return true;
+}
+
+bool InferenceEngine::ScoreTokens(const std::vector<int> &tokens, std::vector<float> &logprobs_out, std::vector<float> *lse_out,
+                                  std::vector<float> *target_logit_out)
+{
+    logprobs_out.clear();
+    if (!model_) { EngineSetError("The engine is not initialized"); return false; }
+    if (multi_) { EngineSetError("ScoreTokens is not available on a multi-device engine (the vocabulary is sharded)"); return false; }
+    const int n = (int)tokens.size();
+    const int max_ctx = spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
+    if (n < 2) { EngineSetError("ScoreTokens needs at least two tokens"); return false; }
+    if (n >= max_ctx) { EngineSetError("ScoreTokens: %d tokens; max_context_len is %d", n, max_ctx); return false; }
+    for (int t : tokens)
+        if (t < 0 || t >= spec_.hyper_params.vocab_size) { EngineSetError("Token id %d is out of range", t); return false; }
+    std::vector<bool> used((size_t)kv_slots_, false);
+    for (const auto &kv : queries_) used[(size_t)kv.second.kv_slot] = true;
+    int slot = 0;
+    while (slot < kv_slots_ && used[(size_t)slot]) slot++;
+    if (slot >= kv_slots_) { EngineSetError("ScoreTokens: every KV slot is taken by a query"); return false; }
+    if (ifa_model_select_kv(model_, slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
+    std::vector<int> targets(tokens.begin() + 1, tokens.end());
+    targets.push_back(-1);                   // (the last row scores nothing)
+    std::vector<float> lse((size_t)n), tl((size_t)n);
+    if (ifa_model_forward_score(model_, tokens.data(), n, 0, targets.data(), lse.data(), tl.data(), nullptr) != IFA_OK) {
+        EngineSetError("scoring step failed: %s", ifa_last_error()); return false;
+    }
+    logprobs_out.resize((size_t)n - 1);
+    for (int i = 0; i + 1 < n; i++) logprobs_out[(size_t)i] = tl[(size_t)i] - lse[(size_t)i];
+    if (lse_out) lse_out->assign(lse.begin(), lse.end() - 1);
+    if (target_logit_out) target_logit_out->assign(tl.begin(), tl.end() - 1);
+    return true;
 }
 
 bool InferenceEngine::RemoveQuery(int query_id)
@@ -567,13 +635,29 @@ bool InferenceEngine::Infer(InferenceResult &res)
         // rows whose candidates come from the device pool behind the step (device_sampling_pool): no logits row leaves the device
         // for them; one pool length serves the launch (the longest wanted; a query reads its own prefix of the sorted pool)
         std::vector<int> pool_rows; int pool_k = 0;
+        bool any_lp = false;
         for (int r = 0; r < n; r++) {
             Query *bq = batch[(size_t)r];
             const bool smp = bq->strategy != SamplingStrategyId::Greedy || host_greedy_;
-            if (smp && PoolRoute(*bq)) { pool_rows.push_back(r); pool_k = std::max(pool_k, PoolLen(*bq)); }
+            if (PoolRoute(*bq)) { pool_rows.push_back(r); pool_k = std::max(pool_k, PoolK(*bq)); any_lp = any_lp || bq->options.logprobs >= 0; }
             else any_sampled = any_sampled || smp;
         }
-        if (any_sampled) { pool_rows.clear(); pool_k = 0; }      // (a row that needs the host path brings the whole block over anyway)
+        // (a row that needs the host path brings the whole block over anyway)
+        if (any_sampled && !any_lp) { pool_rows.clear(); pool_k = 0; }
+        if (any_sampled && any_lp) {         // a logprobs row needs its pool and lse: the sampled rows next to it take their pools too
+            pool_rows.clear();
+            for (int r = 0; r < n; r++) {
+                Query *bq = batch[(size_t)r];
+                const bool smp = bq->strategy != SamplingStrategyId::Greedy || host_greedy_;
+                if (PoolRoute(*bq)) { pool_rows.push_back(r); continue; }
+                if (!smp) continue;
+                const int k = PoolLen(*bq);
+                if (k < 1 || k > IFA_POOL_MAX) { EngineSetError("query %d samples from %d candidates, more than a device pool holds; it cannot share a step with a logprobs query", bq->id, k); return false; }
+                pool_rows.push_back(r); pool_k = std::max(pool_k, k);
+            }
+            any_sampled = false;
+        }
+        std::vector<float> pool_lse;
         std::vector<int> pool_ids, pool_counts; std::vector<uint16_t> pool_vals;
         std::vector<uint16_t> all;
         if (multi_) {
@@ -594,9 +678,14 @@ bool InferenceEngine::Infer(InferenceResult &res)
         if (!pool_rows.empty()) {
             const size_t ns = pool_rows.size();
             pool_ids.resize(ns * (size_t)pool_k); pool_vals.resize(ns * (size_t)pool_k); pool_counts.resize(ns);
+            if (!SetPoolLse(any_lp)) return false;
             if (ifa_model_decode_batch_pool(model_, n, toks.data(), pos.data(), slots.data(), next.data(), pool_k, pool_rows.data(), (int)ns,
                                             pool_ids.data(), pool_vals.data(), pool_counts.data()) != IFA_OK) {
                 EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
+            }
+            if (any_lp) {
+                pool_lse.resize(ns); int got = 0;
+                if (ifa_model_pool_lse(model_, pool_lse.data(), (int)ns, &got) != IFA_OK || got != (int)ns) { EngineSetError("pool lse: %s", ifa_last_error()); return false; }
             }
             sampled_fused_steps_ += (long long)ns;
         } else
@@ -621,7 +710,10 @@ bool InferenceEngine::Infer(InferenceResult &res)
             if (pr != pool_rows.end()) {
                 const size_t j = (size_t)(pr - pool_rows.begin());
                 const int cnt = std::min(pool_counts[j], PoolLen(q));
-                if (!SamplePool(q, pool_ids.data() + j * (size_t)pool_k, pool_vals.data() + j * (size_t)pool_k, cnt, item)) return false;
+                const bool smp = q.strategy != SamplingStrategyId::Greedy || host_greedy_;      // (else: the device argmax already chose)
+                if (smp && !SamplePool(q, pool_ids.data() + j * (size_t)pool_k, pool_vals.data() + j * (size_t)pool_k, cnt, item)) return false;
+                if (q.options.logprobs >= 0 && !FillLogprobs(q, pool_ids.data() + j * (size_t)pool_k, pool_vals.data() + j * (size_t)pool_k,
+                                                             std::min(pool_counts[j], PoolK(q)), pool_lse[j], item)) return false;
             } else
             if ((q.strategy != SamplingStrategyId::Greedy || host_greedy_) && !SampleRow(q, all.data() + (size_t)r * V, item)) return false;
             res.items.push_back(std::move(item));
@@ -647,8 +739,10 @@ bool InferenceEngine::Infer(InferenceResult &res)
             continue;
         }
         if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
-        if (sampled && PoolRoute(q)) {                               // the step ends in the candidate pool: nothing of size V leaves the device
-            const int k = PoolLen(q);
+        if (PoolRoute(q)) {                                          // the step ends in the candidate pool: nothing of size V leaves the device
+            const int k = PoolK(q);
+            const bool lp = q.options.logprobs >= 0;
+            if (!SetPoolLse(lp)) return false;
             int ids[IFA_POOL_MAX], cnt = 0; uint16_t vals[IFA_POOL_MAX];
             // (a prompt keeps today's forward step -- lm_head over all rows into the engine's logits buffer, so its last row is bit for
             //  bit the row the host path samples from -- and only the pool of that row comes to the host)
@@ -662,7 +756,13 @@ bool InferenceEngine::Infer(InferenceResult &res)
                                       : ifa_model_forward_pool(model_, q.tokens.data() + q.processed, n_new, q.processed, logits_dev_, k, &next, ids, vals, &cnt);
             if (rc != IFA_OK) { EngineSetError("%s step failed: %s", n_new == 1 ? "decode" : "forward", ifa_last_error()); return false; }
             if (n_new == 1) sampled_fused_steps_++;
-            if (!SamplePool(q, ids, vals, cnt, item)) return false;
+            if (sampled && !SamplePool(q, ids, vals, std::min(cnt, PoolLen(q)), item)) return false;
+            if (!sampled) { IdWeight w; w.id = next; w.weight = 1.0f; item.next_tokens.push_back(w); }      // (the device argmax chose)
+            if (lp) {
+                float lse = 0.0f; int got = 0;
+                if (ifa_model_pool_lse(model_, &lse, 1, &got) != IFA_OK || got != 1) { EngineSetError("pool lse: %s", ifa_last_error()); return false; }
+                if (!FillLogprobs(q, ids, vals, cnt, lse, item)) return false;
+            }
         } else
         if (n_new == 1 && !want_tensor) {                            // decode: fused graph-replayed step
             if (ifa_model_decode(model_, q.tokens.back(), q.processed, 1, &next, nullptr) != IFA_OK) {

@@ -109,6 +109,11 @@ struct QueryOptions {               // SamplingStrategy::QueryOptions (sampling_
     int random_seed = 0;            // != 0: seeds the query's generator (reproducible draws)
     float temperature = 1.0f;
     int max_output_len = -1;
+    // extension: -1 off; 0: the chosen token's log-probability; 1..20: also the n most probable tokens with theirs.  The softmax is
+    // over the full vocabulary at temperature 1 (the perplexity tool's), whatever the sampler does with the row afterwards.
+    // Single-device engines with return_output_tensors = false only: AddQuery refuses it elsewhere.
+    int logprobs = -1;
+    static const int MAX_LOGPROBS = 20;
 };
 
 struct QueryInferenceResult {
@@ -117,6 +122,10 @@ struct QueryInferenceResult {
     std::vector<IdWeight> next_tokens;          // [0] = the chosen token (greedy: weight 1; sampled: its pool probability)
     std::vector<uint16_t> output_tensor;        // F16 logits [output_rows][output_cols] if return_output_tensors
     int output_rows = 0, output_cols = 0;
+    // QueryOptions::logprobs >= 0: log p of next_tokens[0] and of the `logprobs` best candidates (best first; weight = log p)
+    bool has_logprobs = false;
+    float chosen_logprob = 0.0f;
+    std::vector<IdWeight> top_logprobs;
 };
 
 struct QueryNextToken { int id = 0; bool is_end = false; };
@@ -146,6 +155,8 @@ public:
     virtual std::string Version() const = 0;
     virtual std::string ModelId() const = 0;
     virtual int VocabSize() const = 0;
+    // whether AddQuery accepts QueryOptions::logprobs >= 0 (the service answers "error.unsupported" otherwise)
+    virtual bool SupportsLogprobs() const { return false; }
 };
 
 class InferenceEngine : public QueryEngine {
@@ -172,6 +183,14 @@ public:
     int MaxContextLen() const override { return spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN; }
     std::string ModelId() const override { return spec_.sid; }
     int VocabSize() const override { return spec_.hyper_params.vocab_size; }
+    bool SupportsLogprobs() const override { return model_ && !multi_ && !config_.return_output_tensors; }
+
+    // Extension: log p(tokens[i + 1] | tokens[0..i]) for i = 0 .. n - 2 (softmax over the full vocabulary, as the perplexity tool
+    // takes it) through ifa_model_forward_score on a free KV slot: the rows' log-sum-exp and target logits are reduced on the
+    // device, 2 * n floats come back instead of [n][vocab] halfs.  tokens.size() obeys AddQuery's limit (< max_context_len).
+    // Single-device engines only.  lse_out / target_logit_out (nullable): the two floats logprobs_out[i] is the difference of.
+    bool ScoreTokens(const std::vector<int> &tokens, std::vector<float> &logprobs_out, std::vector<float> *lse_out = nullptr,
+                     std::vector<float> *target_logit_out = nullptr);
 
     // Extension: n greedy steps with the token fed back on the device (hipGraph replay, no host
     // round trip per token).  Equivalent to n x {Infer, CommitInferenceResult(greedy)}.
@@ -219,6 +238,9 @@ private:
     bool SamplePool(Query &q, const int *ids, const uint16_t *vals, int count, QueryInferenceResult &item);
     bool PoolRoute(const Query &q) const;       // this query's candidates come from the device pool (device_sampling_pool)
     int PoolLen(const Query &q) const;
+    int PoolK(const Query &q) const;            // entries asked of the device: the sampler's pool length, or more for logprobs
+    bool SetPoolLse(bool on);
+    bool FillLogprobs(const Query &q, const int *ids, const uint16_t *vals, int count, float lse, QueryInferenceResult &item);
     // ---- multi-GPU partitions (devices = 0&1 | 0;1 | 0&1;2&3): one worker and one host thread per GPU, like the
     // reference's Infer_TensorParallelism / Infer_Std over GpuInferenceWorker threads (inference_engine.cc:1161-1296)
     struct MultiGpu;
@@ -241,6 +263,7 @@ private:
     void *logits_dev_ = nullptr;
     size_t logits_rows_ = 0;
     long long sampled_fused_steps_ = 0;
+    bool pool_lse_on_ = false;      // the worker's option pool_lse as last set
 };
 
 // error text of the last failed call on this thread (the reference logs through LogError)

@@ -25,12 +25,29 @@ static std::string JoinIds(const std::vector<int> &ids)
     return s + "]";
 }
 
+// [{"token_id": t, "logprob": x, "top_logprobs": [{"token_id": t, "logprob": x} ...]} ...]
+static std::string JoinLogprobs(const std::vector<TokenLogprob> &lps)
+{
+    char buf[48];
+    std::string s = "[";
+    for (size_t i = 0; i < lps.size(); i++) {
+        snprintf(buf, sizeof buf, "%.6f", lps[i].logprob);
+        s += std::string(i ? ", " : "") + "{\"token_id\": " + std::to_string(lps[i].token_id) + ", \"logprob\": " + buf + ", \"top_logprobs\": [";
+        for (size_t j = 0; j < lps[i].top.size(); j++) {
+            snprintf(buf, sizeof buf, "%.6f", lps[i].top[j].weight);
+            s += std::string(j ? ", " : "") + "{\"token_id\": " + std::to_string(lps[i].top[j].id) + ", \"logprob\": " + buf + "}";
+        }
+        s += "]}";
+    }
+    return s + "]";
+}
+
 void InferFlowResponseChunk::ToJson(std::string &out) const
 {
     char buf[64];
     snprintf(buf, sizeof buf, "%.4f", time_cost);
     out = "{\"ret_code\": \"" + ret_code + "\", \"token_ids\": " + JoinIds(token_ids) + ", \"is_end\": " + (is_end ? "true" : "false")
-        + ", \"time_cost\": " + buf + "}";
+        + ", \"time_cost\": " + buf + (want_logprobs ? ", \"logprobs\": " + JoinLogprobs(logprobs) : std::string()) + "}";
 }
 
 void InferFlowResponseChunk::ToJsonOpenAI(std::string &out, bool is_chunk, const std::string &id) const
@@ -39,7 +56,8 @@ void InferFlowResponseChunk::ToJsonOpenAI(std::string &out, bool is_chunk, const
     if (failed) { out = "{\"error\": {\"message\": \"" + ret_code + "\", \"type\": \"invalid_request_error\"}}"; return; }
     const std::string finish = !is_end ? "null" : ("\"" + (finish_reason.empty() ? std::string("length") : finish_reason) + "\"");
     out = "{\"id\": \"" + id + "\", \"object\": \"" + (is_chunk ? "chat.completion.chunk" : "chat.completion") + "\", \"choices\": [{\"index\": 0, \""
-        + (is_chunk ? "delta" : "message") + "\": {\"role\": \"assistant\", \"token_ids\": " + JoinIds(token_ids) + "}, \"finish_reason\": " + finish + "}]";
+        + (is_chunk ? "delta" : "message") + "\": {\"role\": \"assistant\", \"token_ids\": " + JoinIds(token_ids) + "}, \"finish_reason\": " + finish
+        + (want_logprobs ? ", \"logprobs\": {\"content\": " + JoinLogprobs(logprobs) + "}" : std::string()) + "}]";
     if (!is_chunk) out += ", \"usage\": {\"prompt_tokens\": " + std::to_string(prompt_tokens) + ", \"completion_tokens\": " + std::to_string(token_ids.size())
         + ", \"total_tokens\": " + std::to_string(prompt_tokens + (int)token_ids.size()) + "}";
     out += "}";
@@ -78,6 +96,14 @@ bool InferFlowServiceCore::ParseRequest(InferFlowRequest &r, const std::string &
     root.GetString("decoding_alg", r.decoding_alg);
     root.GetNumber("temperature", r.temperature);
     root.GetNumber("eos_token_id", r.eos_token_id);
+    // "logprobs": true asks for the chosen token's log-probability per generated token, "top_logprobs": n (0..20) also for the n most
+    // probable tokens; n without "logprobs": true, or outside the range, is refused
+    bool want_lp = false; int top_lp = 0;
+    if (root.Get("logprobs") && !root.GetBool("logprobs", want_lp)) { if (err) *err = "error.invalid_logprobs"; return false; }
+    if (root.Get("top_logprobs")) {
+        if (!root.GetNumber("top_logprobs", top_lp) || !want_lp || top_lp < 0 || top_lp > QueryOptions::MAX_LOGPROBS) { if (err) *err = "error.invalid_logprobs"; return false; }
+    }
+    r.logprobs = want_lp ? top_lp : -1;
     return true;
 }
 
@@ -119,6 +145,7 @@ bool InferFlowServiceCore::InferOnce()
             const int id = item.next_tokens[0].id;
             QueryResult &qr = it->second;
             qr.tokens.push_back(id);
+            if (item.has_logprobs) { TokenLogprob t; t.token_id = id; t.logprob = item.chosen_logprob; t.top = item.top_logprobs; qr.lps.push_back(std::move(t)); }
             qr.produced++;
             tokens_out_++;
             QueryNextToken nt; nt.id = id;
@@ -162,6 +189,10 @@ bool InferFlowServiceCore::ProcessQuery(InferFlowResponseChunk &result, const In
     qo.random_seed = request.random_seed;
     qo.temperature = request.temperature;
     qo.max_output_len = max_len;
+    qo.logprobs = request.logprobs;
+    result.want_logprobs = request.logprobs >= 0;
+    if (request.logprobs > QueryOptions::MAX_LOGPROBS || request.logprobs < -1) { result.ret_code = "error.invalid_logprobs"; return false; }
+    if (request.logprobs >= 0 && !engine_.SupportsLogprobs()) { result.ret_code = "error.logprobs_unsupported"; return false; }
     int qid = 0;
     {
         // registered before the loop can step the query (the loop holds engine_lock_ for a whole Infer + Commit)
@@ -177,18 +208,22 @@ bool InferFlowServiceCore::ProcessQuery(InferFlowResponseChunk &result, const In
     while (!is_end && running_.load()) {
         std::this_thread::sleep_for(std::chrono::microseconds(500));
         std::vector<int> fresh;
+        std::vector<TokenLogprob> fresh_lp;
         {
             std::lock_guard<std::mutex> g(lock_);
             auto it = query_to_result_.find(qid);
             if (it == query_to_result_.end()) break;
             fresh.swap(it->second.tokens);
+            fresh_lp.swap(it->second.lps);
             is_end = it->second.is_end;
             if (is_end) { reason = it->second.reason; err = it->second.err; query_to_result_.erase(it); }
         }
         result.token_ids.insert(result.token_ids.end(), fresh.begin(), fresh.end());
+        result.logprobs.insert(result.logprobs.end(), fresh_lp.begin(), fresh_lp.end());
         if (on_chunk && (!fresh.empty() || is_end)) {
             InferFlowResponseChunk chunk;
             chunk.token_ids = fresh; chunk.is_end = is_end; chunk.finish_reason = reason;
+            chunk.want_logprobs = result.want_logprobs; chunk.logprobs = fresh_lp;
             chunk.time_cost = std::chrono::duration<float>(std::chrono::steady_clock::now() - t0).count();
             if (!(*on_chunk)(chunk)) {      // the client went away: drop the query (reference: engine_.RemoveQuery on a failed WriteChunk)
                 std::lock_guard<std::mutex> eg(engine_lock_);

@@ -36,6 +36,14 @@ struct InferFlowRequest {                 // InferFlowRequest (inferflow_service
     bool is_streaming_mode = false;
     int eos_token_id = -1;
     std::string fn;                       // "" / "process_query" | "get_stat"
+    // "logprobs": true (+ "top_logprobs": n in 0..20) in the body -> QueryOptions::logprobs = n; -1: not asked for
+    int logprobs = -1;
+};
+
+struct TokenLogprob {                     // one generated token: its log-probability and the most probable tokens of its step
+    int token_id = 0;
+    float logprob = 0;
+    std::vector<IdWeight> top;            // (id, log p), best first
 };
 
 struct InferFlowResponseChunk {           // InferFlowResponseChunk
@@ -47,6 +55,10 @@ struct InferFlowResponseChunk {           // InferFlowResponseChunk
     // why the query ended: "stop" (the request's eos_token_id was produced) | "length" (max_output_len, or the context is full)
     // | "error" (the engine step failed; ret_code says which).  The OpenAI shape reports it as finish_reason.
     std::string finish_reason;
+    // the request asked for logprobs: one entry per token of token_ids; the JSON carries them only then (without the request
+    // fields the body is what it always was)
+    bool want_logprobs = false;
+    std::vector<TokenLogprob> logprobs;
     void ToJson(std::string &out) const;
     void ToJsonOpenAI(std::string &out, bool is_chunk, const std::string &id) const;
 };
@@ -65,7 +77,7 @@ public:
     void GetStat(std::string &json) const;
 
 private:
-    struct QueryResult { std::vector<int> tokens; bool is_end = false; int max_len = 0, eos = -1, produced = 0; std::string reason, err; };
+    struct QueryResult { std::vector<int> tokens; std::vector<TokenLogprob> lps; bool is_end = false; int max_len = 0, eos = -1, produced = 0; std::string reason, err; };
     bool InferOnce();
     QueryEngine &engine_;
     std::thread loop_;

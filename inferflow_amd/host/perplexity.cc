@@ -20,7 +20,7 @@ double TokenNll(const uint16_t *row, int vocab, int token_id)
 }
 
 bool ComputePerplexity(InferenceEngine &engine, const std::vector<int> &tokens, int max_length, int stride,
-                       PerplexityResult &out, int host_threads)
+                       PerplexityResult &out, int host_threads, bool device_scoring)
 {
     out = PerplexityResult();
     if (max_length < 2 || stride < 1) { EngineSetError("perplexity: max_length must be >= 2 and stride >= 1"); return false; }
@@ -33,9 +33,30 @@ bool ComputePerplexity(InferenceEngine &engine, const std::vector<int> &tokens, 
         if (t < 0 || t >= V) { EngineSetError("perplexity: token id %d is out of range", t); return false; }
     const int n_tokens = (int)tokens.size();
     host_threads = std::max(1, std::min(host_threads, 64));
+    // on request an engine that keeps its output tensors on the device (return_output_tensors = false, one device) scores there
+    if (device_scoring && (engine.config().return_output_tensors || engine.PartitionRanks() != 1)) {
+        EngineSetError("perplexity: device scoring needs a single-device engine with return_output_tensors = false");
+        return false;
+    }
     for (int start = 0; start < n_tokens; start += stride) {
         const int end = std::min(start + max_length, n_tokens);
         const std::vector<int> window(tokens.begin() + start, tokens.begin() + end);
+        if (device_scoring) {
+            // the window's rows are reduced where they are (InferenceEngine::ScoreTokens): per row the log-sum-exp and the target's
+            // logit come back, nll = lse - logit; the same windows, double sums and statistics as below
+            const int rows = (int)window.size() - 1;
+            if (rows >= 1) {
+                std::vector<float> lp, lse, tl;
+                if (!engine.ScoreTokens(window, lp, &lse, &tl)) return false;
+                for (int i = 0; i < rows; i++) {
+                    const double v = (double)lse[(size_t)i] - (double)tl[(size_t)i];
+                    out.nll_sum += v; out.nll2_sum += v * v;
+                }
+            }
+            out.count += std::max(rows, 0);
+            out.running.push_back(out.count > 0 ? exp(out.nll_sum / (double)out.count) : 0.0);
+            continue;
+        }
         const int qid = engine.AddQuery(window, QueryOptions());
         if (qid <= 0) { if (qid == 0) EngineSetError("perplexity: engine busy"); return false; }
         InferenceResult res;

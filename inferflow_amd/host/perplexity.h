@@ -21,8 +21,11 @@ struct PerplexityResult {
 // -log softmax(logits)[token_id] of one F16 logits row, arithmetic of perplexity.cc:100-119
 double TokenNll(const uint16_t *logits_f16, int vocab, int token_id);
 
-// The engine must have been initialised with return_output_tensors = true and have no active query.
+// The engine must have no active query.  device_scoring = false (default): it must have been initialised with
+// return_output_tensors = true; every window's logits come to the host and are scored there.  device_scoring = true: a single-device
+// engine initialised with return_output_tensors = false scores every window on the device (InferenceEngine::ScoreTokens): the same
+// windows, double sums and statistics, no [T][vocab] block to the host.
 bool ComputePerplexity(InferenceEngine &engine, const std::vector<int> &tokens, int max_length, int stride,
-                       PerplexityResult &out, int host_threads = 8);
+                       PerplexityResult &out, int host_threads = 8, bool device_scoring = false);
 
 } // namespace inferflow_amd

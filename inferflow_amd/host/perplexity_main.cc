@@ -1,5 +1,5 @@
 // ifa_perplexity -- token-id counterpart of the reference's perplexity tool (src/tools/perplexity.cc:165-300,
-// bin/perplexity.ini): [main] inference_engine_config / test_data_file / max_length / stride.
+// bin/perplexity.ini): [main] inference_engine_config / test_data_file / max_length / stride / device_scoring (extension, default false).
 //   ifa_perplexity <perplexity.ini> [--section transformer_engine]
 // test_data_file holds whitespace- or comma-separated token ids (tokenizers are outside the hot path).
 #include <cstdio>
@@ -25,11 +25,13 @@ int main(int argc, char **argv)
     }
     ini.GetItem("main", "max_length", max_length);
     ini.GetItem("main", "stride", stride);
+    bool device_scoring = false;               // extension: score the windows on the device (no [T][vocab] block to the host)
+    ini.GetItem("main", "device_scoring", device_scoring);
 
     InferenceConfig cfg;
     if (!InferenceEngine::LoadConfig(cfg, engine_ini, section)) { fprintf(stderr, "Failed to load the inference configuration: %s\n", EngineLastError()); return 1; }
     cfg.max_concurrent_queries = 1;            // perplexity.cc:176
-    cfg.return_output_tensors = true;
+    cfg.return_output_tensors = !device_scoring;
     InferenceEngine engine;
     if (!engine.Init(cfg)) { fprintf(stderr, "Failed to initialize the inference engine: %s\n", EngineLastError()); return 1; }
 
@@ -43,7 +45,7 @@ int main(int argc, char **argv)
     while (in >> v) tokens.push_back((int)v);
 
     PerplexityResult r;
-    if (!ComputePerplexity(engine, tokens, max_length, stride, r)) { fprintf(stderr, "perplexity: %s\n", EngineLastError()); return 1; }
+    if (!ComputePerplexity(engine, tokens, max_length, stride, r, 8, device_scoring)) { fprintf(stderr, "perplexity: %s\n", EngineLastError()); return 1; }
     for (size_t i = 0; i < r.running.size(); i++) printf("[%zu]%.4lf\n", i, r.running[i]);
     printf("Final estimate: PPL = %.4lf +/- %.5lf\n", r.ppl, r.ppl_stderr);
     return 0;

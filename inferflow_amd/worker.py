@@ -148,6 +148,53 @@ class DecodeWorker:
                                                 vals.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p)))
         return out, [(ids[j, :cnt[j]].copy(), vals[j, :cnt[j]].copy()) for j in range(sel.size)]
 
+    def pool_lse(self, cap=256):
+        """The log-sum-exp of every row the LAST pool step pooled (option "pool_lse" = 1; empty with it off): float32 [n_sel].
+        log p(pool id) = float(pool value) - lse."""
+        out, n = np.zeros(cap, np.float32), C.c_int(0)
+        check(lib().ifa_model_pool_lse(self._h, out.ctypes.data_as(C.c_void_p), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def decode_pool_lse(self, token, pos, k):
+        """decode_pool with the row's log-sum-exp (sets option "pool_lse" for this step): (next, ids, F16 bits, lse)"""
+        self.set_option("pool_lse", 1)
+        try:
+            nxt, ids, vals = self.decode_pool(token, pos, k)
+            return nxt, ids, vals, float(self.pool_lse()[0])
+        finally:
+            self.set_option("pool_lse", 0)
+
+    def forward_pool_lse(self, tokens, prefix_len, k, logits_out=None):
+        """forward_pool with the last row's log-sum-exp: (next, ids, F16 bits, lse)"""
+        self.set_option("pool_lse", 1)
+        try:
+            nxt, ids, vals = self.forward_pool(tokens, prefix_len, k, logits_out)
+            return nxt, ids, vals, float(self.pool_lse()[0])
+        finally:
+            self.set_option("pool_lse", 0)
+
+    def decode_batch_pool_lse(self, tokens, positions, slots, k, rows_sel):
+        """decode_batch_pool with the selected rows' log-sum-exp: (next tokens, pools, lse float32 [n_sel])"""
+        self.set_option("pool_lse", 1)
+        try:
+            out, pools = self.decode_batch_pool(tokens, positions, slots, k, rows_sel)
+            return out, pools, self.pool_lse(max(len(pools), 1))
+        finally:
+            self.set_option("pool_lse", 0)
+
+    def forward_score(self, tokens, prefix_len, targets):
+        """A scoring prompt (ifa_model_forward_score): per row the log-sum-exp of its logits and its logit at targets[i] (NaN for a
+        target below 0), without a [T][vocab] block leaving the worker.  Returns (next token, lse float32 [T], target logit float32 [T]);
+        log p(targets[i] | tokens[:i + 1]) = target_logit[i] - lse[i]."""
+        toks = np.ascontiguousarray(tokens, np.int32)
+        tg = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        assert tg.size == toks.size, (tg.size, toks.size)
+        lse, tl = np.zeros(toks.size, np.float32), np.zeros(toks.size, np.float32)
+        nxt = C.c_int(-1)
+        check(lib().ifa_model_forward_score(self._h, toks.ctypes.data_as(C.c_void_p), toks.size, int(prefix_len), tg.ctypes.data_as(C.c_void_p),
+                                            lse.ctypes.data_as(C.c_void_p), tl.ctypes.data_as(C.c_void_p), C.byref(nxt)))
+        return nxt.value, lse, tl
+
     def decode_prepare(self, start_pos, n_steps):
         """Set up (capture) what decode(., start_pos, n_steps) replays, without running a step."""
         check(lib().ifa_model_decode_prepare(self._h, int(start_pos), int(n_steps)))
@@ -263,6 +310,29 @@ def topk_pool(logits, k, excluded_bits=None, stream=None):
                               C.c_void_p(excluded_bits.data_ptr()) if excluded_bits is not None else None,
                               C.c_void_p(ids.data_ptr()), C.c_void_p(vals.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
     return ids, vals, cnt
+
+
+def logsumexp_rows(logits, n=None, row_idx=None, targets=None, split=True, stream=None):
+    """ifa_logsumexp_rows over a torch cuda F16 tensor [rows_avail][stride] (or [n]): the log-sum-exp of the first n entries
+    (default: all) of rows row_idx (torch cuda int32; default every row) and, with targets (torch cuda int32, one per row), the
+    row's value at the target (NaN below 0).  split=False withholds the workspace (one workgroup per row).
+    Returns torch cuda float32 (lse [rows], target logit [rows] or None); enqueue-only."""
+    import torch
+    if logits.dim() == 1:
+        logits = logits.reshape(1, -1)
+    stride = logits.stride(0)
+    n = logits.shape[1] if n is None else int(n)
+    rows = logits.shape[0] if row_idx is None else row_idx.numel()
+    lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    tl = torch.empty(rows, dtype=torch.float32, device=logits.device) if targets is not None else None
+    ws_bytes = lib().ifa_logsumexp_workspace(rows, n) if split else 0
+    ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=logits.device) if ws_bytes else None
+    check(lib().ifa_logsumexp_rows(C.c_void_p(logits.data_ptr()), stride, C.c_void_p(row_idx.data_ptr()) if row_idx is not None else None,
+                                   rows, n, C.c_void_p(targets.data_ptr()) if targets is not None else None, C.c_void_p(lse.data_ptr()),
+                                   C.c_void_p(tl.data_ptr()) if tl is not None else None, C.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                   C.c_void_p(stream)))
+    lse._ifa_workspace = ws      # (alive as long as the result: the launches are only enqueued)
+    return lse, tl
 
 
 class TpTopology(C.Structure):
