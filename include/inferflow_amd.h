@@ -308,6 +308,13 @@ int ifa_model_reset(ifa_model *m);
  * makes one of them the cache that forward()/decode() read and write (each slot keeps its own captured graph). */
 int ifa_model_kv_slots(ifa_model *m, int n_slots);
 int ifa_model_select_kv(ifa_model *m, int slot);
+/* Rows [0, n_rows) of the K and V cache of every layer from slot src_slot to slot dst_slot -- what a prompt prefix cache needs
+ * when the slot that holds a prompt's leading rows belongs to a running query (the engine's `prefix_cache` key).  ONE launch on
+ * the model's stream for all 2 * layers segments (csrc/ifa_kv_copy.hip), ordered with the steps around it, no host
+ * synchronisation; either slot may be the selected one.  The copy is byte for byte: a step on the destination behind the copied
+ * rows computes what it would on the source.  n_rows = 0 is IFA_OK without a launch.  IFA_ERR_ARG: src_slot == dst_slot, a slot
+ * outside ifa_model_kv_slots, n_rows outside 0..max_ctx, a model that is not finalized; IFA_ERR_STATE: a stream under capture. */
+int ifa_model_kv_copy(ifa_model *m, int src_slot, int dst_slot, int n_rows);
 int ifa_model_set_option(ifa_model *m, const char *name, int value);
 /* up to 3 token ids the worker's greedy argmax (forward / decode / decode_batch) never selects: the unk id and
  * Invalid-type tokens GetSortedTopK skips (sampling_strategy.cc:281-297).  None by default at this level; the engine

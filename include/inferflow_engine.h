@@ -100,8 +100,22 @@ double ifa_perplexity_token_nll(const uint16_t *logits_f16, int vocab, int token
  * "decoder_kv_heads", "max_context_len", "device_weight_data_type", "device_kv_cache_data_type", "partition_ranks"
  * (workers of the multi-GPU partition; 1 = single device), "device_sampling_pool" (the .ini key, 0 / 1), "sampled_fused_steps"
  * (single-token steps of sampled queries served by the worker's decode step + device pool so far, one per query per step;
- * stays 0 on the host path); -1 if unknown */
+ * stays 0 on the host path), "prefix_cache" (0 / 1: the prompt prefix cache is ACTIVE -- the .ini key `prefix_cache = true` on a
+ * single-device engine with return_output_tensors = false; elsewhere the key is accepted and this stays 0), "prefix_cache_hits"
+ * (queries that started behind reused rows), "prefix_cache_tokens" (the rows they reused in all), "prefix_cache_copies" (the hits
+ * whose rows sat in a busy slot and were copied on the device, ifa_model_kv_copy); -1 if unknown */
 int ifa_engine_model_info(ifa_engine *e, const char *key);
+/* prompt prefix cache: the leading prompt tokens of query_id whose K/V rows AddQuery found in a slot (the query's first Infer runs
+ * only the rest; QueryInferenceResult::prefix_len reports the same number); 0 without a hit or with the cache off, -1 unknown id */
+int ifa_engine_query_cached_tokens(ifa_engine *e, int query_id);
+/* host-only: the cache's slot / reuse policy (host/prefix_cache.h).  Slot i holds the rows of record_lens[i] token ids -- the
+ * records lie back to back in records_flat --, is busy (busy[i] != 0: a running query owns it) or free, and was last used at
+ * stamps[i].  Match = common prefix of prompt and record, at most n_prompt - 1; the longest wins (ties: free before busy, then the
+ * lower index).  Below min_tokens: no reuse, the slot is the lowest free one with an empty record, else the free one with the
+ * oldest stamp.  Best slot free: in place.  Best slot busy: that destination + a copy.  out3 = {slot, src_slot (-1: no copy),
+ * reuse_len}.  0, or -1 (bad arguments, no free slot). */
+int ifa_prefix_cache_plan(const int *records_flat, const int *record_lens, const int *busy, const long long *stamps, int n_slots,
+                          const int *prompt, int n_prompt, int min_tokens, int *out3);
 
 /* the per-device worker of partition rank `rank` (an ifa_model * for the ifa_model_* calls of inferflow_amd.h; rank 0 of a
  * single-device engine) and its place in the partition {stage, n_stages, tp_rank, tp_size, layer0, layer1}: the counterpart of

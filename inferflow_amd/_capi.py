@@ -112,6 +112,7 @@ SIGNATURES = {
     "ifa_add_by_row_index": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "ifa_model_kv_slots": (_i, [_vp, _i]),
     "ifa_model_select_kv": (_i, [_vp, _i]),
+    "ifa_model_kv_copy": (_i, [_vp, _i, _i, _i]),
     "ifa_model_decode_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ifa_model_set_pool_excluded": (_i, [_vp, _vp, _i]),
     "ifa_model_decode_pool": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -188,6 +189,8 @@ ENGINE_SIGNATURES = {
     "ifa_engine_perplexity_device": (_i, [_vp, _ip, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "ifa_perplexity_token_nll": (C.c_double, [_vp, _i, _i]),
     "ifa_engine_model_info": (_i, [_vp, C.c_char_p]),
+    "ifa_engine_query_cached_tokens": (_i, [_vp, _i]),
+    "ifa_prefix_cache_plan": (_i, [_ip, _ip, _ip, C.POINTER(C.c_longlong), _i, _ip, _i, _i, _ip]),
     "ifa_engine_worker": (_vp, [_vp, _i]),
     "ifa_engine_worker_plan": (_i, [_vp, _i, _ip]),
     "ifa_service_parse_request": (_i, [C.c_char_p, _i, C.c_char_p, _sz]),

@@ -326,6 +326,7 @@ int ifa_model_destroy(ifa_model *m)
     if (m->st_counter) (void)hipFree(m->st_counter);
     pool_free(m);
     score_free(m);
+    kv_copy_free(m);
     if (m->stream) (void)ifa_gemm_release_stream((ifa_stream)m->stream);
     if (m->stream && m->own_stream) (void)hipStreamDestroy(m->stream);
     if (m->side_stream) (void)hipStreamDestroy(m->side_stream);

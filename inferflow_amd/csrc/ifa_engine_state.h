@@ -7,6 +7,7 @@
 //   ifa_engine_moe.hip      mixture of experts: the router on the device, grouped expert launches of a batch, the host-routed fallback
 //   ifa_engine_exact.hip    option exact_order: single-token steps in the reference kernels' summation order (parity instrument)
 //   ifa_engine_tp.hip       tensor / layer partitions: per-seam entry points and the multi-GPU step driven from C
+//   ifa_kv_copy.hip         cache rows from one query slot to another in one launch (the engine's prompt prefix cache)
 #pragma once
 #include <chrono>
 #include <cstdlib>
@@ -219,6 +220,14 @@ struct ifa_model {
     int *score_tgt_dev = nullptr, *score_tgt_pin = nullptr;     // [cap] target ids
     float *score_dev = nullptr, *score_pin = nullptr;           // lse [cap] | target logit [cap]
     size_t score_cap = 0;
+    // Slot-to-slot copy of cache rows (ifa_model_kv_copy, ifa_kv_copy.hip): the K and V buffers of EVERY slot as one device table
+    // [slot][layer: k, v], staged once through kvc_tab_pin on the model's stream and rebuilt only when a slot's buffers are not the
+    // ones it lists (more slots).  A slot's buffers are its own for good -- select_kv moves pointers between the layers and the
+    // parked slot, never between slots -- so a call is ONE launch that indexes the table.  A replaced table is parked in
+    // kvc_retired until the model goes: an earlier launch may still read it and nothing here waits for the stream.
+    void **kvc_tab_dev = nullptr, **kvc_tab_pin = nullptr;
+    std::vector<void *> kvc_tab_host;          // what the device table holds
+    std::vector<void *> kvc_retired;           // device / pinned blocks of replaced tables, alternating
     static constexpr int RING = 1024;
 };
 
@@ -372,6 +381,8 @@ int lse_part_reserve(ifa_model *m);
 // the last row the copy of the 2 * n floats into pinned staging.  A no-op otherwise.
 int score_enqueue(ifa_model *m, const half_t *logits, int n_rows);
 void score_free(ifa_model *m);
+// ---- ifa_kv_copy.hip
+void kv_copy_free(ifa_model *m);
 // ---- ifa_engine_moe.hip
 int launch_moe_router(ifa_model *m, int l);
 // Mixture of experts (ProcessGpuLayer_Moe, inference_worker.cc:1924-2146): router GEMV -> softmax -> D2H ->

@@ -138,6 +138,14 @@ class InferenceEngine:
     def model_info(self, key):
         return _capi.lib().ifa_engine_model_info(self._h, key.encode())
 
+    def query_cached_tokens(self, query_id):
+        """Leading prompt tokens whose K/V rows add_query found in a slot (prefix_cache = true in the .ini); -1: unknown id"""
+        return _capi.lib().ifa_engine_query_cached_tokens(self._h, int(query_id))
+
+    def prefix_cache_stats(self):
+        """{active, hits, tokens, copies} of the prompt prefix cache (model_info keys prefix_cache*)"""
+        return {k: self.model_info("prefix_cache" + ("_" + k if k != "active" else "")) for k in ("active", "hits", "tokens", "copies")}
+
     def worker_plan(self, rank):
         """{stage, n_stages, tp_rank, tp_size, layer0, layer1} of partition rank `rank` (None: no such rank)"""
         out = (C.c_int * 6)()
@@ -177,6 +185,22 @@ def sampling_choose(logits_f16, strategy_id, max_k=8, top_p=0.9, pool_size=50, t
     if n < 0:
         raise EngineError(_capi.lib().ifa_engine_last_error().decode(errors="replace"))
     return [ids[i] for i in range(n_draws)], [pr[i] for i in range(n_draws)], [pid[i] for i in range(min(n, 256))], [ppr[i] for i in range(min(n, 256))]
+
+
+def prefix_cache_plan(records, busy, stamps, prompt, min_tokens=16):
+    """Host-only: the prefix cache's plan for `prompt` over slots holding `records` (lists of token ids): (slot, src_slot, reuse_len),
+    src_slot -1 when nothing is copied; None on bad arguments / no free slot (ifa_prefix_cache_plan)."""
+    n = len(records)
+    flat = [int(t) for r in records for t in r]
+    fl = (C.c_int * max(1, len(flat)))(*flat)
+    lens = (C.c_int * max(1, n))(*[len(r) for r in records])
+    bz = (C.c_int * max(1, n))(*[int(bool(b)) for b in busy])
+    st = (C.c_longlong * max(1, n))(*[int(v) for v in stamps])
+    pr = (C.c_int * max(1, len(prompt)))(*[int(t) for t in prompt])
+    out = (C.c_int * 3)()
+    if _capi.lib().ifa_prefix_cache_plan(fl, lens, bz, st, n, pr, len(prompt), int(min_tokens), out) != 0:
+        return None
+    return out[0], out[1], out[2]
 
 
 def sampling_choose_ex(logits_f16, strategy_id, temperature=1.0, seed=1, n_draws=1, mu=None, max_k=8, top_p=0.9, pool_size=50, min_p=0.05,

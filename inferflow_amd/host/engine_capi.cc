@@ -10,6 +10,7 @@
 #include "inference_engine.h"
 #include "inferflow_service.h"
 #include "perplexity.h"
+#include "prefix_cache.h"
 #include "half_bits.h"
 
 using namespace inferflow_amd;
@@ -271,7 +272,32 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "partition_ranks") return e->engine.PartitionRanks();
     if (k == "device_sampling_pool") return e->engine.config().device_sampling_pool ? 1 : 0;
     if (k == "sampled_fused_steps") return (int)std::min<long long>(e->engine.sampled_fused_steps(), 0x7FFFFFFF);
+    if (k == "prefix_cache") return e->engine.prefix_cache_active() ? 1 : 0;
+    if (k == "prefix_cache_hits") return (int)std::min<long long>(e->engine.prefix_cache_hits(), 0x7FFFFFFF);
+    if (k == "prefix_cache_tokens") return (int)std::min<long long>(e->engine.prefix_cache_tokens(), 0x7FFFFFFF);
+    if (k == "prefix_cache_copies") return (int)std::min<long long>(e->engine.prefix_cache_copies(), 0x7FFFFFFF);
     return -1;
+}
+
+int ifa_engine_query_cached_tokens(ifa_engine *e, int query_id) { return e ? e->engine.QueryCachedTokens(query_id) : -1; }
+
+// host-only: the slot / reuse plan of the prompt prefix cache (host/prefix_cache.h)
+int ifa_prefix_cache_plan(const int *records_flat, const int *record_lens, const int *busy, const long long *stamps, int n_slots,
+                          const int *prompt, int n_prompt, int min_tokens, int *out3)
+{
+    if (!record_lens || !busy || !stamps || n_slots < 1 || !prompt || n_prompt < 1 || min_tokens < 1 || !out3) { EngineSetError("ifa_prefix_cache_plan: bad arguments"); return -1; }
+    std::vector<PrefixSlotView> views((size_t)n_slots);
+    size_t off = 0;
+    for (int i = 0; i < n_slots; i++) {
+        if (record_lens[i] < 0 || (record_lens[i] > 0 && !records_flat)) { EngineSetError("ifa_prefix_cache_plan: record %d", i); return -1; }
+        views[(size_t)i].record = records_flat ? records_flat + off : nullptr; views[(size_t)i].record_len = record_lens[i];
+        views[(size_t)i].busy = busy[i] != 0; views[(size_t)i].stamp = stamps[i];
+        off += (size_t)record_lens[i];
+    }
+    PrefixPlan plan;
+    if (!PlanPrefixReuse(views, prompt, n_prompt, min_tokens, plan)) { EngineSetError("ifa_prefix_cache_plan: no free slot"); return -1; }
+    out3[0] = plan.slot; out3[1] = plan.src_slot; out3[2] = plan.reuse_len;
+    return 0;
 }
 
 // the worker (ifa_model *, for the ifa_model_* calls of include/inferflow_amd.h) of partition rank `rank` and its plan

@@ -14,6 +14,7 @@
 #include "inferflow_amd.h"
 #include "inference_engine.h"
 #include "ifa_ini.h"
+#include "prefix_cache.h"
 #include "half_bits.h"
 
 namespace inferflow_amd {
@@ -126,6 +127,8 @@ void InferenceEngine::Clear()
     if (model_) { ifa_model_destroy(model_); model_ = nullptr; }
     if (logits_dev_) { ifa_free(logits_dev_); logits_dev_ = nullptr; logits_rows_ = 0; }
     queries_.clear();
+    prefix_active_ = false; slot_records_.clear();
+    use_clock_ = prefix_hits_ = prefix_tokens_ = prefix_copies_ = 0;
 }
 
 static bool LoadDeviceGroups(std::vector<std::vector<int>> &groups, const IniConfig &cfg, const std::string &section, const std::string &key)
@@ -230,6 +233,9 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "dynamic_batching_min_queries", config.dynamic_batching_min_queries);
     cfg.GetItem(section, "force_partition_path", config.force_partition_path);
     cfg.GetItem(section, "device_sampling_pool", config.device_sampling_pool);
+    cfg.GetItem(section, "prefix_cache", config.prefix_cache);
+    cfg.GetItem(section, "prefix_cache_min_tokens", config.prefix_cache_min_tokens);
+    if (config.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config.prefix_cache_min_tokens); return false; }
     cfg.GetItem(section, "is_study_mode", config.debug.is_study_mode);
     cfg.GetItem(section, "show_tensors", config.debug.show_tensors);
     return true;
@@ -296,6 +302,10 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
         for (ifa_model *mm : all)
             if (ifa_model_kv_slots(mm, kv_slots_) != IFA_OK) { EngineSetError("KV caches for %d queries: %s", kv_slots_, ifa_last_error()); Clear(); return false; }
     }
+    // prompt prefix cache: one device, and no caller that expects a logits row per prompt token
+    if (config_.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config_.prefix_cache_min_tokens); Clear(); return false; }
+    prefix_active_ = config_.prefix_cache && !multi_ && !config_.return_output_tensors;
+    if (prefix_active_) slot_records_.assign((size_t)kv_slots_, SlotRecord());
     return true;
 }
 
@@ -467,11 +477,49 @@ int InferenceEngine::AddQuery(const std::vector<int> &tokens, const QueryOptions
     if (query_options.logprobs >= 0 && PoolK(q) > IFA_POOL_MAX) {      // (its steps could not end in a device pool: no logprobs would come back)
         EngineSetError("logprobs need the query's %d sampling candidates in one device pool of at most %d", PoolK(q), IFA_POOL_MAX); return -1;
     }
-    std::vector<bool> used((size_t)kv_slots_, false);
-    for (const auto &kv : queries_) used[(size_t)kv.second.kv_slot] = true;
-    while (q.kv_slot < kv_slots_ && used[(size_t)q.kv_slot]) q.kv_slot++;
+    if (!PlaceQuery(q)) return -1;
     queries_[q.id] = q;
     return q.id;
+}
+
+bool InferenceEngine::PlaceQuery(Query &q)
+{
+    std::vector<bool> used((size_t)kv_slots_, false);
+    for (const auto &kv : queries_) used[(size_t)kv.second.kv_slot] = true;
+    if (!prefix_active_) {
+        while (q.kv_slot < kv_slots_ && used[(size_t)q.kv_slot]) q.kv_slot++;
+        return true;
+    }
+    std::vector<PrefixSlotView> views((size_t)kv_slots_);
+    for (int i = 0; i < kv_slots_; i++) {
+        const SlotRecord &r = slot_records_[(size_t)i];
+        views[(size_t)i].record = r.tokens.data(); views[(size_t)i].record_len = (int)r.tokens.size(); views[(size_t)i].stamp = r.stamp;
+    }
+    for (const auto &kv : queries_) {      // a running query's rows: what it has processed so far
+        PrefixSlotView &v = views[(size_t)kv.second.kv_slot];
+        v.busy = true; v.record = kv.second.tokens.data(); v.record_len = std::min(kv.second.processed, (int)kv.second.tokens.size());
+    }
+    PrefixPlan plan;
+    if (!PlanPrefixReuse(views, q.tokens.data(), (int)q.tokens.size(), config_.prefix_cache_min_tokens, plan)) {
+        EngineSetError("prefix cache: no slot for query %d", q.id); return false;
+    }
+    // the copy runs HERE, not at the first Infer: the source query may end and its slot be overwritten in between (the worker's
+    // stream orders it with the steps around it, the service serialises the engine's calls)
+    if (plan.src_slot >= 0 && ifa_model_kv_copy(model_, plan.src_slot, plan.slot, plan.reuse_len) != IFA_OK) {
+        EngineSetError("prefix cache: copying %d rows from slot %d to slot %d failed: %s", plan.reuse_len, plan.src_slot, plan.slot, ifa_last_error());
+        slot_records_[(size_t)plan.slot] = SlotRecord();      // (whatever the destination held, it may not hold any more)
+        return false;
+    }
+    slot_records_[(size_t)plan.slot] = SlotRecord();          // busy from here on: q.tokens[0 .. q.processed) is its record
+    q.kv_slot = plan.slot; q.processed = q.cached_tokens = plan.reuse_len;
+    if (plan.reuse_len > 0) { prefix_hits_++; prefix_tokens_ += plan.reuse_len; if (plan.src_slot >= 0) prefix_copies_++; }
+    return true;
+}
+
+int InferenceEngine::QueryCachedTokens(int query_id) const
+{
+    auto it = queries_.find(query_id);
+    return it == queries_.end() ? -1 : it->second.cached_tokens;
 }
 
 int InferenceEngine::QueryCount() const { return (int)queries_.size(); }
@@ -585,6 +633,7 @@ bool InferenceEngine::ScoreTokens(const std::vector<int> &tokens, std::vector<fl
     int slot = 0;
     while (slot < kv_slots_ && used[(size_t)slot]) slot++;
     if (slot >= kv_slots_) { EngineSetError("ScoreTokens: every KV slot is taken by a query"); return false; }
+    if (prefix_active_) slot_records_[(size_t)slot] = SlotRecord();      // the scoring prompt overwrites this free slot's rows
     if (ifa_model_select_kv(model_, slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
     std::vector<int> targets(tokens.begin() + 1, tokens.end());
     targets.push_back(-1);                   // (the last row scores nothing)
@@ -601,7 +650,16 @@ bool InferenceEngine::ScoreTokens(const std::vector<int> &tokens, std::vector<fl
 
 bool InferenceEngine::RemoveQuery(int query_id)
 {
-    return queries_.erase(query_id) != 0;
+    auto it = queries_.find(query_id);
+    if (it == queries_.end()) return false;
+    if (prefix_active_) {            // the freed slot keeps the rows of the tokens the query has processed
+        const Query &q = it->second;
+        SlotRecord &r = slot_records_[(size_t)q.kv_slot];
+        r.tokens.assign(q.tokens.begin(), q.tokens.begin() + std::min(q.processed, (int)q.tokens.size()));
+        r.stamp = ++use_clock_;
+    }
+    queries_.erase(it);
+    return true;
 }
 
 bool InferenceEngine::QueryEnded(int query_id) const

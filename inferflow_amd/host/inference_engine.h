@@ -100,6 +100,14 @@ struct InferenceConfig {
     // of the logits row.  Applies when return_output_tensors is false, the engine is a single device and pool_size <= IFA_POOL_MAX;
     // every other case keeps the host path.  The sampler's rules, draws and generator are the same code either way.
     bool device_sampling_pool = false;
+    // extension: prompt prefix cache.  The engine remembers which token ids' K/V rows every slot holds -- a running query's
+    // processed tokens, a finished query's whole context -- and AddQuery starts a prompt behind the longest run of leading tokens
+    // it finds there (host/prefix_cache.h): in place if that slot is free, through one device copy into a free slot if it is
+    // busy (ifa_model_kv_copy).  Matches below prefix_cache_min_tokens are not worth a slot's record.  Applies to a single-device
+    // engine with return_output_tensors = false (a caller of the output tensors expects one row per prompt token); elsewhere the
+    // key is accepted and the cache stays off (model_info "prefix_cache" = 0).
+    bool prefix_cache = false;
+    int prefix_cache_min_tokens = 16;
     DebugOptions debug;
 };
 
@@ -215,6 +223,13 @@ public:
     // single-token steps of sampled queries that took the worker's decode step + device pool instead of ifa_model_forward
     // (one per query per step; 0 unless device_sampling_pool is on)
     long long sampled_fused_steps() const { return sampled_fused_steps_; }
+    // prompt prefix cache (InferenceConfig::prefix_cache): whether it is active on this engine; queries that started behind reused
+    // rows, the rows they reused in all, how many of them needed the device copy; the rows query_id reused at AddQuery (-1: unknown id)
+    bool prefix_cache_active() const { return prefix_active_; }
+    long long prefix_cache_hits() const { return prefix_hits_; }
+    long long prefix_cache_tokens() const { return prefix_tokens_; }
+    long long prefix_cache_copies() const { return prefix_copies_; }
+    int QueryCachedTokens(int query_id) const;
     // worker of partition rank r and its place in the partition (stage, n_stages, tp_rank, tp_size, layer0, layer1); rank 0 of a
     // single-device engine is worker().  The tests read the ranks' weight slices back and rebuild the whole model for the oracle.
     ifa_model *worker(int rank);
@@ -228,6 +243,7 @@ private:
         QueryOptions options;
         bool ended = false;
         int kv_slot = 0;            // this query's KV cache inside the worker (ifa_model_select_kv)
+        int cached_tokens = 0;      // rows the prefix cache supplied at AddQuery (processed started there)
         SamplingStrategyId strategy = SamplingStrategyId::Greedy;
         StdSamplingConfig sampling; // per query copy, like StdQueryData::config
         JavaRandom rng;
@@ -264,6 +280,16 @@ private:
     size_t logits_rows_ = 0;
     long long sampled_fused_steps_ = 0;
     bool pool_lse_on_ = false;      // the worker's option pool_lse as last set
+    // ---- prompt prefix cache.  Record invariant: rows [0, tokens.size()) of a FREE slot's K and V hold exactly these token ids at
+    // these positions.  A busy slot's record is implicit (its query's tokens[0 .. processed)); RemoveQuery turns it into the stored
+    // one, and whatever else writes a free slot (ScoreTokens) clears that slot's record first.
+    struct SlotRecord { std::vector<int> tokens; long long stamp = 0; };
+    bool prefix_active_ = false;
+    std::vector<SlotRecord> slot_records_;      // [kv_slots_] when active
+    long long use_clock_ = 0;                   // stamps: a counter of record updates
+    long long prefix_hits_ = 0, prefix_tokens_ = 0, prefix_copies_ = 0;
+    // the new query's slot; with the cache active also q.processed / q.cached_tokens and the copy.  false: the copy failed
+    bool PlaceQuery(Query &q);
 };
 
 // error text of the last failed call on this thread (the reference logs through LogError)

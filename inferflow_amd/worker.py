@@ -88,6 +88,14 @@ class DecodeWorker:
     def select_kv(self, slot):
         check(lib().ifa_model_select_kv(self._h, int(slot)))
 
+    def kv_copy(self, src, dst, n_rows):
+        """Cache rows [0, n_rows) of every layer's K and V from slot src to slot dst: one launch on the worker's stream, enqueue-only."""
+        check(lib().ifa_model_kv_copy(self._h, int(src), int(dst), int(n_rows)))
+
+    def sync(self):
+        """Wait for everything enqueued on the worker's stream (kv_copy only enqueues; forward / decode synchronise themselves)."""
+        check(lib().ifa_stream_sync(C.c_void_p(lib().ifa_model_stream(self._h))))
+
     def decode_batch(self, tokens, positions, slots, logits_out=None):
         """One new token for each of n queries (dynamic batching); returns the n greedy next tokens."""
         toks = np.ascontiguousarray(tokens, np.int32)
