@@ -354,6 +354,16 @@ int ifa_model_decode_prepare(ifa_model *m, int start_pos, int n_steps);
  * (the weights are streamed once for all queries), attention per row on its own cache.  logits_out: optional [n][vocab] F16. */
 int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host,
                            int *next_tokens_host, void *logits_out_dev);
+/* The draft step (lookup / speculative decoding, csrc/ifa_decode_draft_kv.hip): n rows (2..8) of ONE query as one batched step on
+ * the SELECTED KV slot.  Row i is tokens_host[i] at position pos0 + i behind cache rows [0, pos0 + i): row 0 the query's last
+ * committed token (not yet in the cache), rows 1 .. n - 1 draft tokens.  next_tokens_host[i] = the masked greedy argmax of row i
+ * (exclusions and tie rule of ifa_model_decode_batch); logits_out_dev: optional [n][vocab] F16 (a call with it runs eagerly, one
+ * without replays a graph captured per n).  One synchronisation per call.  Row i is bit for bit -- logits, id, the K / V row it
+ * writes -- the row ifa_model_decode_batch computes for a query at position pos0 + i whose slot holds the same bytes in rows
+ * [0, pos0 + i).  Afterwards cache rows pos0 .. pos0 + n - 1 hold the n rows' K / V; the caller decides how many count (the
+ * leading i with next[i - 1] == tokens[i]) and later steps overwrite the others.  IFA_ERR_ARG: n outside 2..8, pos0 < 0,
+ * pos0 + n > max_ctx; IFA_ERR_STATE: a partitioned worker (tp_size > 1 or a topology), options exact_order or perf_stat. */
+int ifa_model_decode_draft(ifa_model *m, int n, const int *tokens_host, int pos0, int *next_tokens_host, void *logits_out_dev);
 /* ---- steps that end in a candidate pool (sampled decoding without the logits row on the host): ifa_topk_pool runs on the
  * step's logits on the worker's stream, in front of the step's ONE synchronisation, and (count, ids, values) come back
  * in one copy through pinned staging.  Everything after the pool -- softmax, cuts, the draw -- stays with the caller.

@@ -81,6 +81,23 @@ int ifa_engine_perf_stat(ifa_engine *e, unsigned *keys, float *ms, int capacity)
 
 /* extension: n greedy steps with device-side token feedback (graph replay); returns tokens written or -1 */
 int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_tokens, float *gpu_ms);
+/* extension: lookup decoding (prompt-lookup decoding / "predicted outputs").  Up to max_new greedy tokens like ifa_engine_generate,
+ * but a step carries the query's last token plus up to `lookup_draft_len` (.ini, default 4, 1..7) draft tokens as rows of ONE
+ * batched step on the query's KV slot (ifa_model_decode_draft); every leading draft token that equals the step's own greedy choice
+ * is a token gained without a step of its own.  Drafts: the continuation of the longest n-gram (`lookup_ngram_max` .. `lookup_ngram_min`
+ * tokens, defaults 3 .. 1) that ends the query's tokens, looked up in prediction[n_prediction] first (nullable / 0: none), then in
+ * the query's own tokens (ifa_lookup_draft); no match: one plain step.  The tokens are the greedy choices of the batched-rows
+ * arithmetic (F16 activations); ifa_engine_generate's single-row step quantises activations to int8, so the two agree wherever the
+ * top-2 logit gap exceeds that route difference.  stats5 (nullable): {steps, draft steps, draft tokens offered, draft tokens
+ * accepted, milliseconds inside the worker's steps}.  Returns the tokens written (never more than max_new) or -1: conditions of
+ * ifa_engine_generate, and model_info "lookup_decoding" = 0 (multi-GPU engine, return_output_tensors = true). */
+int ifa_engine_generate_lookup(ifa_engine *e, int query_id, int max_new, const int *prediction, int n_prediction, int *out_tokens,
+                               float *stats5);
+/* host-only: the draft rule (host/lookup_draft.h).  For g = ngram_max down to ngram_min (skipped while n_ctx < g): key = the last g
+ * tokens of ctx; in pred the LOWEST start j with pred[j .. j + g) == key and j + g < n_pred gives pred[j + g ..), else in ctx the
+ * HIGHEST start j < n_ctx - g with ctx[j .. j + g) == key gives ctx[j + g ..); the first g with a match wins, the draft is cut to k
+ * tokens and to the end of its source.  Returns the draft length 0..k (0: no match), -1 on bad arguments. */
+int ifa_lookup_draft(const int *ctx, int n_ctx, const int *pred, int n_pred, int ngram_max, int ngram_min, int k, int *draft_out);
 
 /* the reference's perplexity harness (src/tools/perplexity.cc:41-284) over a token-id stream: windows of max_length
  * every `stride` tokens, each scored from its whole-prompt logits; needs return_output_tensors = true in the .ini and
@@ -103,7 +120,8 @@ double ifa_perplexity_token_nll(const uint16_t *logits_f16, int vocab, int token
  * stays 0 on the host path), "prefix_cache" (0 / 1: the prompt prefix cache is ACTIVE -- the .ini key `prefix_cache = true` on a
  * single-device engine with return_output_tensors = false; elsewhere the key is accepted and this stays 0), "prefix_cache_hits"
  * (queries that started behind reused rows), "prefix_cache_tokens" (the rows they reused in all), "prefix_cache_copies" (the hits
- * whose rows sat in a busy slot and were copied on the device, ifa_model_kv_copy); -1 if unknown */
+ * whose rows sat in a busy slot and were copied on the device, ifa_model_kv_copy), "lookup_decoding" (0 / 1: ifa_engine_generate_lookup
+ * is available -- a single-device engine with return_output_tensors = false); -1 if unknown */
 int ifa_engine_model_info(ifa_engine *e, const char *key);
 /* prompt prefix cache: the leading prompt tokens of query_id whose K/V rows AddQuery found in a slot (the query's first Infer runs
  * only the rest; QueryInferenceResult::prefix_len reports the same number); 0 without a hit or with the cache off, -1 unknown id */

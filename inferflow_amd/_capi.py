@@ -114,6 +114,7 @@ SIGNATURES = {
     "ifa_model_select_kv": (_i, [_vp, _i]),
     "ifa_model_kv_copy": (_i, [_vp, _i, _i, _i]),
     "ifa_model_decode_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_model_decode_draft": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     "ifa_model_set_pool_excluded": (_i, [_vp, _vp, _i]),
     "ifa_model_decode_pool": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_decode_batch_pool": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
@@ -185,6 +186,8 @@ ENGINE_SIGNATURES = {
     "ifa_engine_last_logits": (_i, [_vp, _i, _vp, _sz, _ip, _ip]),
     "ifa_engine_perf_stat": (_i, [_vp, _vp, _vp, _i]),
     "ifa_engine_generate": (_i, [_vp, _i, _i, _ip, C.POINTER(_f)]),
+    "ifa_engine_generate_lookup": (_i, [_vp, _i, _i, _ip, _i, _ip, C.POINTER(_f)]),
+    "ifa_lookup_draft": (_i, [_ip, _i, _ip, _i, _i, _i, _i, _ip]),
     "ifa_engine_perplexity": (_i, [_vp, _ip, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "ifa_engine_perplexity_device": (_i, [_vp, _ip, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
     "ifa_perplexity_token_nll": (C.c_double, [_vp, _i, _i]),

@@ -25,6 +25,9 @@ struct DecAttnParams {
     // pointers and context from batch_rows[b], its RoPE pairs at rope_tab + b * head_dim, and writes out + b * heads * head_dim
     const void *batch_rows;    // DecAttnBatchRow[queries]
     int q_stride;
+    // batched step only: 1 = the rows' K / V are in the cache already (k_draft_kv_store, ifa_decode_draft_kv.hip -- several rows of ONE
+    // slot, each behind its predecessors), so no workgroup writes the cache; a row's own key / value still come from LDS as always
+    int skip_store;
 };
 struct DecAttnBatchRow { const uint8_t *kc, *vc; int n_ctx, pad; };
 
@@ -190,7 +193,8 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
     const int h = h_in, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int group = pheads / pkvh;
     const int kvh = h / group;
-    const bool writer = (h % group) == 0;
+    bool writer = (h % group) == 0;
+    if constexpr (BATCH) writer = writer && !P.skip_store;
     const int kv_dim = pkvh * HD;
     const size_t row_bytes = Q8 ? (size_t)(kv_dim / 32) * 34 : (size_t)kv_dim * 2;
     const size_t head_off = Q8 ? (size_t)((kvh * HD) / 32) * 34 : (size_t)kvh * HD * 2;

@@ -57,6 +57,8 @@ void drop_graphs(ifa_model *m)
     }
     for (auto &kv : m->batch_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
     m->batch_graphs.clear();
+    for (auto &kv : m->draft_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
+    m->draft_graphs.clear();
 }
 
 void free_tensor(Tensor &t)

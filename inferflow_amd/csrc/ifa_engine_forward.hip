@@ -498,7 +498,7 @@ bool prefill_big_ok(const ifa_model *m)
     return true;
 }
 
-int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext, const void *rows_l)
+int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext, const void *rows_l, bool draft)
 {
     const ifa_model_config &c = m->cfg;
     Layer &L = m->layers[(size_t)l];
@@ -519,7 +519,9 @@ int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext
     P.bias[0] = (const half_t *)L.t[T_WQ_B].data; P.bias[1] = (const half_t *)L.t[T_WK_B].data; P.bias[2] = (const half_t *)L.t[T_WV_B].data;
     P.Y = m->bqkv; P.ldy = (int)(QD + 2 * KVD);
     if ((rc = gemm_rows_mfma_launch(P, GM_PLAIN, norm_fused ? 1 : 0, m->stream))) return rc;
-    // 2. RoPE, KV store, attention of every query on its own cache
+    // 2. RoPE, KV store, attention of every query on its own cache.  Draft step (the n rows are consecutive positions of ONE slot): the
+    // K / V rows of all of them go to the cache in a launch of their own first, and the attention kernel leaves the cache alone
+    if (draft && (rc = draft_kv_store_launch(m, n, m->bqkv + QD, m->bqkv + QD + KVD, (int)(QD + 2 * KVD), rows_l))) return rc;
     {
         const int rope_dims = (int)(c.head_dim * c.partial_rotary + 0.5f);
         DecAttnParams A; memset(&A, 0, sizeof(A));
@@ -529,6 +531,7 @@ int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext
         A.rope_order = c.rope_order; A.rope_cols = rope_dims;
         A.alibi = c.use_alibi; A.alibi_base = c.tp_rank * c.heads; A.alibi_total = c.heads * std::max(1, c.tp_size);
         A.out = m->att; A.max_ctx = c.max_ctx; A.batch_rows = rows_l; A.q_stride = (int)(QD + 2 * KVD);
+        A.skip_store = draft ? 1 : 0;
         const size_t asmem = dec_attn_smem(c.head_dim, c.max_ctx);
         const dim3 grid((unsigned)c.heads, (unsigned)n), block(256);
 #define IFA_BATTN(HDV, Q8V) { auto kern = k_dec_attn<HDV, Q8V, true>; \
@@ -580,7 +583,7 @@ int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext
 }
 
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
-                         void *logits_out)
+                         void *logits_out, bool draft)
 {
     const ifa_model_config &c = m->cfg;
     const int n_slots = m->slots.empty() ? 1 : (int)m->slots.size();
@@ -588,7 +591,8 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     for (int r = 0; r < n; r++) {
         if (pos_host[r] < 0 || pos_host[r] >= c.max_ctx) return ifa_fail(IFA_ERR_ARG, "decode_batch: position %d outside max_ctx %d", pos_host[r], c.max_ctx);
         if (slot_host[r] < 0 || slot_host[r] >= n_slots) return ifa_fail(IFA_ERR_ARG, "decode_batch: KV slot %d of %d", slot_host[r], n_slots);
-        for (int r2 = 0; r2 < r; r2++) if (slot_host[r2] == slot_host[r]) return ifa_fail(IFA_ERR_ARG, "decode_batch: KV slot %d used twice", slot_host[r]);
+        // (draft step, ifa_model_decode_draft: every row on the same slot, row r behind rows [0, r) of this very step)
+        for (int r2 = 0; r2 < r && !draft; r2++) if (slot_host[r2] == slot_host[r]) return ifa_fail(IFA_ERR_ARG, "decode_batch: KV slot %d used twice", slot_host[r]);
         max_ctx = std::max(max_ctx, pos_host[r] + 1);
     }
     int rc = ensure_scratch(m, n);
@@ -640,9 +644,10 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     // (MoE layers of the fused step route on the device -- no host round trip -- so they are captured too)
     const bool use_graph = (m->opt_batch_graph || fused) && m->opt_graph && (!has_moe || fused) && !logits_out && !tp;
     const int attn_ctx = use_graph ? c.max_ctx : max_ctx;     // LDS sizing of the attention kernel must not depend on the step
+    std::map<int, hipGraphExec_t> &graphs = draft ? m->draft_graphs : m->batch_graphs;
     if (use_graph) {
-        auto it = m->batch_graphs.find(n);
-        if (it != m->batch_graphs.end()) {
+        auto it = graphs.find(n);
+        if (it != graphs.end()) {
             IFA_HIP_CHECK(hipGraphLaunch(it->second, m->stream));
             if ((rc = pool_enqueue(m, m->logits, n))) return rc;
             IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -669,7 +674,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     bool xn_ready = false;           // see forward_ops: every residual Add is fused with the norm that follows it
     if (fused) {
         for (int l = 0; l < c.layers; l++) {
-            if ((rc = batch_fused_layer(m, l, n, x, m->f, rows_d + (size_t)l * (size_t)n))) return rc;
+            if ((rc = batch_fused_layer(m, l, n, x, m->f, rows_d + (size_t)l * (size_t)n, draft))) return rc;
             std::swap(m->x, m->f);
             x = m->x;
         }
@@ -728,7 +733,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
         hipGraphExec_t ex = nullptr;
         IFA_HIP_CHECK(hipGraphInstantiate(&ex, gph, nullptr, nullptr, 0));
         (void)hipGraphDestroy(gph);
-        m->batch_graphs[n] = ex;
+        graphs[n] = ex;
         IFA_HIP_CHECK(hipGraphLaunch(ex, m->stream));
     } else if (rc) return rc;
     if (!tp && (rc = pool_enqueue(m, m->logits, n))) return rc;

@@ -8,6 +8,7 @@
 //   ifa_engine_exact.hip    option exact_order: single-token steps in the reference kernels' summation order (parity instrument)
 //   ifa_engine_tp.hip       tensor / layer partitions: per-seam entry points and the multi-GPU step driven from C
 //   ifa_kv_copy.hip         cache rows from one query slot to another in one launch (the engine's prompt prefix cache)
+//   ifa_decode_draft_kv.hip the draft step: n rows of ONE slot in one batched step (ifa_model_decode_draft; the engine's lookup decoding)
 #pragma once
 #include <chrono>
 #include <cstdlib>
@@ -115,6 +116,7 @@ struct ifa_model {
     void *batch_tab_dev = nullptr, *batch_tab_pin = nullptr;
     size_t batch_tab_bytes = 0;
     std::map<int, hipGraphExec_t> batch_graphs;      // captured batched step per batch size (dense models)
+    std::map<int, hipGraphExec_t> draft_graphs;      // captured draft step (ifa_model_decode_draft: n rows of ONE slot) per row count
     // long-context decode attention (keys split over workgroups): workspace, switch and the context it starts at
     DecAttnSplitWs attn_ws = {nullptr, nullptr, nullptr, 8};
     int opt_attn_unload = 1;       // 1 (default): in the 256-row bucket the heads' workgroups of the fused QKV + attention launch take no weight rows (UL kernels)
@@ -366,9 +368,11 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
 bool batch_fused_ok(const ifa_model *m, int n);
 bool prefill_big_ok(const ifa_model *m);
 bool prefill_mid_ok(ifa_model *m, int T, bool any_length);
-int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext, const void *rows_l);
+int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext, const void *rows_l, bool draft = false);
+// ifa_decode_draft_kv.hip: RoPE + cache rows of the n rows of a draft step (rows_l: the layer's AttnRowH[n]) in one launch
+int draft_kv_store_launch(ifa_model *m, int n, const half_t *k, const half_t *v, int stride, const void *rows_l);
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
-                         void *logits_out);
+                         void *logits_out, bool draft = false);      // draft: the rows share a slot (ifa_model_decode_draft)
 // ---- ifa_engine_pool.hip
 // armed (m->pool.k > 0): ifa_topk_pool over the wanted rows of `logits` ([n_rows][vocab], this step's rows) + the copy of the result
 // block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.

@@ -125,6 +125,20 @@ class InferenceEngine:
             raise EngineError("Generate failed: " + self._err())
         return [out[i] for i in range(n)], ms.value
 
+    def generate_lookup(self, query_id, max_new_tokens, prediction=None):
+        """Lookup decoding (InferenceEngine::GenerateLookup): up to max_new_tokens greedy tokens, draft tokens taken from
+        `prediction` (token ids the output is expected to repeat; None: none) and from the query's own tokens, verified in one
+        batched step per draft.  Returns (tokens, {steps, draft_steps, drafted, accepted, gpu_ms})."""
+        out = (C.c_int * max(1, max_new_tokens))()
+        st = (C.c_float * 5)()
+        pred = list(prediction) if prediction is not None else []
+        arr = (C.c_int * len(pred))(*[int(t) for t in pred]) if pred else None
+        n = _capi.lib().ifa_engine_generate_lookup(self._h, int(query_id), int(max_new_tokens), arr, len(pred), out, st)
+        if n < 0:
+            raise EngineError("GenerateLookup failed: " + self._err())
+        stats = {"steps": int(st[0]), "draft_steps": int(st[1]), "drafted": int(st[2]), "accepted": int(st[3]), "gpu_ms": float(st[4])}
+        return [out[i] for i in range(n)], stats
+
     def perplexity(self, tokens, max_length=512, stride=512, device_scoring=False):
         """(PPL, error estimate, scored tokens) of a token-id stream -- the reference's perplexity tool.  device_scoring: every
         window is scored on the device (an engine with return_output_tensors = false; the default needs it true)."""

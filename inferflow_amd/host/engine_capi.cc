@@ -11,6 +11,7 @@
 #include "inferflow_service.h"
 #include "perplexity.h"
 #include "prefix_cache.h"
+#include "lookup_draft.h"
 #include "half_bits.h"
 
 using namespace inferflow_amd;
@@ -231,6 +232,27 @@ int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_token
     return (int)toks.size();
 }
 
+int ifa_engine_generate_lookup(ifa_engine *e, int query_id, int max_new, const int *prediction, int n_prediction, int *out_tokens, float *stats5)
+{
+    if (!e || !out_tokens || n_prediction < 0 || (n_prediction > 0 && !prediction)) { EngineSetError("ifa_engine_generate_lookup: bad arguments"); return -1; }
+    std::vector<int> toks, pred;
+    if (n_prediction > 0) pred.assign(prediction, prediction + n_prediction);
+    LookupStats st;
+    const bool ok = e->engine.GenerateLookup(query_id, max_new, toks, n_prediction > 0 ? &pred : nullptr, &st);
+    if (stats5) { stats5[0] = (float)st.steps; stats5[1] = (float)st.draft_steps; stats5[2] = (float)st.drafted; stats5[3] = (float)st.accepted; stats5[4] = st.gpu_ms; }
+    if (!ok) return -1;
+    for (size_t i = 0; i < toks.size(); i++) out_tokens[i] = toks[i];
+    return (int)toks.size();
+}
+
+// host-only: the draft of lookup decoding (host/lookup_draft.h)
+int ifa_lookup_draft(const int *ctx, int n_ctx, const int *pred, int n_pred, int ngram_max, int ngram_min, int k, int *draft_out)
+{
+    const int n = LookupDraft(ctx, n_ctx, pred, n_pred, ngram_max, ngram_min, k, draft_out);
+    if (n < 0) EngineSetError("ifa_lookup_draft: bad arguments");
+    return n;
+}
+
 static int engine_perplexity(ifa_engine *e, const int *tokens, int n_tokens, int max_length, int stride, bool device_scoring,
                              double *ppl, double *ppl_stderr, long long *count)
 {
@@ -275,6 +297,7 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "prefix_cache") return e->engine.prefix_cache_active() ? 1 : 0;
     if (k == "prefix_cache_hits") return (int)std::min<long long>(e->engine.prefix_cache_hits(), 0x7FFFFFFF);
     if (k == "prefix_cache_tokens") return (int)std::min<long long>(e->engine.prefix_cache_tokens(), 0x7FFFFFFF);
+    if (k == "lookup_decoding") return e->engine.lookup_decoding_active() ? 1 : 0;
     if (k == "prefix_cache_copies") return (int)std::min<long long>(e->engine.prefix_cache_copies(), 0x7FFFFFFF);
     return -1;
 }

@@ -15,6 +15,7 @@
 #include "inference_engine.h"
 #include "ifa_ini.h"
 #include "prefix_cache.h"
+#include "lookup_draft.h"
 #include "half_bits.h"
 
 namespace inferflow_amd {
@@ -194,6 +195,16 @@ static bool LoadModelSpec(ModelSpec &spec, const IniConfig &cfg, const std::stri
     return LoadModelSpecJson(spec, is_abs ? spec.spec_file : spec.dir + spec.spec_file);
 }
 
+static bool LookupConfigOk(const InferenceConfig &c)
+{
+    if (c.lookup_draft_len < 1 || c.lookup_draft_len > 7) { EngineSetError("lookup_draft_len must be 1..7 (got %d)", c.lookup_draft_len); return false; }
+    if (c.lookup_ngram_min < 1 || c.lookup_ngram_max < c.lookup_ngram_min) {
+        EngineSetError("lookup_ngram_min must be at least 1 and lookup_ngram_max no smaller (got %d, %d)", c.lookup_ngram_min, c.lookup_ngram_max);
+        return false;
+    }
+    return true;
+}
+
 bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &config_path,
                                  const std::string &section, const std::string &data_root_dir)
 {
@@ -236,6 +247,10 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "prefix_cache", config.prefix_cache);
     cfg.GetItem(section, "prefix_cache_min_tokens", config.prefix_cache_min_tokens);
     if (config.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config.prefix_cache_min_tokens); return false; }
+    cfg.GetItem(section, "lookup_draft_len", config.lookup_draft_len);
+    cfg.GetItem(section, "lookup_ngram_max", config.lookup_ngram_max);
+    cfg.GetItem(section, "lookup_ngram_min", config.lookup_ngram_min);
+    if (!LookupConfigOk(config)) return false;
     cfg.GetItem(section, "is_study_mode", config.debug.is_study_mode);
     cfg.GetItem(section, "show_tensors", config.debug.show_tensors);
     return true;
@@ -305,6 +320,7 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
     // prompt prefix cache: one device, and no caller that expects a logits row per prompt token
     if (config_.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config_.prefix_cache_min_tokens); Clear(); return false; }
     prefix_active_ = config_.prefix_cache && !multi_ && !config_.return_output_tensors;
+    if (!LookupConfigOk(config_)) { Clear(); return false; }
     if (prefix_active_) slot_records_.assign((size_t)kv_slots_, SlotRecord());
     return true;
 }
@@ -955,6 +971,75 @@ bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_
         n_steps -= k;
     }
     if (gpu_ms) *gpu_ms = ms_total;
+    return true;
+}
+
+bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vector<int> &new_tokens, const std::vector<int> *prediction,
+                                     LookupStats *stats)
+{
+    new_tokens.clear();
+    LookupStats st;
+    if (stats) *stats = st;
+    auto it = queries_.find(query_id);
+    if (!model_ || it == queries_.end()) { EngineSetError("Query %d does not exist", query_id); return false; }
+    if (multi_) { EngineSetError("GenerateLookup: lookup decoding runs on a single-device engine (this one has %d partition ranks)", PartitionRanks()); return false; }
+    if (config_.return_output_tensors) { EngineSetError("GenerateLookup: lookup decoding is off under return_output_tensors = true (a draft step has several logits rows per step)"); return false; }
+    Query &q = it->second;
+    if (max_new_tokens <= 0) return true;
+    if (q.ended) { EngineSetError("Query %d has ended", query_id); return false; }
+    if (host_greedy_) { EngineSetError("GenerateLookup() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size()); return false; }
+    if (q.strategy != SamplingStrategyId::Greedy) { EngineSetError("GenerateLookup() decodes greedily on the device; query %d uses strategy %d (use Infer / CommitInferenceResult)", query_id, (int)q.strategy); return false; }
+    const int max_ctx = spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
+    if ((int)q.tokens.size() + max_new_tokens > max_ctx) { EngineSetError("GenerateLookup: %zu tokens + %d new tokens exceed max_context_len %d", q.tokens.size(), max_new_tokens, max_ctx); return false; }
+    if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
+    const auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    int left = max_new_tokens;
+    const int pending = (int)q.tokens.size() - q.processed;
+    if (pending > 1 || q.processed == 0) {            // prefill whatever is pending; yields the first new token
+        int next = -1;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (ifa_model_forward(model_, q.tokens.data() + q.processed, pending, q.processed, nullptr, &next) != IFA_OK) {
+            EngineSetError("forward step failed: %s", ifa_last_error()); return false;
+        }
+        st.gpu_ms += ms_since(t0); st.steps++;
+        q.processed = (int)q.tokens.size();
+        q.tokens.push_back(next); new_tokens.push_back(next);
+        left--;
+    } else if (pending == 0) { EngineSetError("Query %d has no committed token to continue from", query_id); return false; }
+    const int *pred = prediction && !prediction->empty() ? prediction->data() : nullptr;
+    const int n_pred = pred ? (int)prediction->size() : 0;
+    int row[8], next[8];
+    while (left > 0) {
+        // here q.tokens.size() == q.processed + 1: the last token is committed, its K/V row is not in the cache yet.  A draft step
+        // writes rows q.processed .. q.processed + m and may emit m + 1 tokens: m stays inside the request and the context
+        const int pos0 = q.processed;
+        const int m_max = std::min(std::min(config_.lookup_draft_len, left - 1), max_ctx - pos0 - 1);
+        const int m = m_max >= 1 ? LookupDraft(q.tokens.data(), (int)q.tokens.size(), pred, n_pred, config_.lookup_ngram_max, config_.lookup_ngram_min, m_max, row + 1) : 0;
+        if (m < 0) { EngineSetError("GenerateLookup: draft lookup failed"); return false; }
+        st.steps++;
+        if (m == 0) {                                  // nothing to guess: one plain step
+            float ms = 0;
+            if (ifa_model_decode(model_, q.tokens.back(), pos0, 1, next, &ms) != IFA_OK) { EngineSetError("decode failed: %s", ifa_last_error()); if (stats) *stats = st; return false; }
+            st.gpu_ms += ms;
+            q.tokens.push_back(next[0]); new_tokens.push_back(next[0]);
+            q.processed = pos0 + 1;
+            left--;
+            continue;
+        }
+        row[0] = q.tokens.back();
+        const auto t0 = std::chrono::steady_clock::now();
+        if (ifa_model_decode_draft(model_, m + 1, row, pos0, next, nullptr) != IFA_OK) { EngineSetError("draft step failed: %s", ifa_last_error()); if (stats) *stats = st; return false; }
+        st.gpu_ms += ms_since(t0);
+        int a = 0;
+        while (a < m && next[a] == row[a + 1]) a++;
+        st.draft_steps++; st.drafted += m; st.accepted += a;
+        // rows pos0 .. pos0 + a hold the last token and the a accepted drafts -- the tokens in front of the newest one; the rejected
+        // rows behind them lie outside tokens[0 .. processed) (the prefix cache's record) and the next step overwrites them
+        for (int i = 0; i <= a; i++) { q.tokens.push_back(next[i]); new_tokens.push_back(next[i]); }
+        q.processed = pos0 + a + 1;
+        left -= a + 1;
+    }
+    if (stats) *stats = st;
     return true;
 }
 

@@ -108,6 +108,11 @@ struct InferenceConfig {
     // key is accepted and the cache stays off (model_info "prefix_cache" = 0).
     bool prefix_cache = false;
     int prefix_cache_min_tokens = 16;
+    // extension: lookup decoding (InferenceEngine::GenerateLookup).  Up to lookup_draft_len (1..7) draft tokens per step, the
+    // continuation of the longest n-gram of lookup_ngram_max .. lookup_ngram_min tokens that ends the query's context
+    // (host/lookup_draft.h).  Applies to a single-device engine with return_output_tensors = false; elsewhere the keys are accepted
+    // and GenerateLookup is refused (model_info "lookup_decoding" = 0).
+    int lookup_draft_len = 4, lookup_ngram_max = 3, lookup_ngram_min = 1;
     DebugOptions debug;
 };
 
@@ -137,6 +142,10 @@ struct QueryInferenceResult {
 };
 
 struct QueryNextToken { int id = 0; bool is_end = false; };
+
+// what a GenerateLookup call did: worker steps in all, how many of them were draft steps (ifa_model_decode_draft), draft tokens
+// offered and draft tokens that equalled the step's own greedy choice, milliseconds spent inside the worker's step calls
+struct LookupStats { int steps = 0, draft_steps = 0, drafted = 0, accepted = 0; float gpu_ms = 0.0f; };
 
 struct InferencePerfStat { std::map<uint32_t, float> time_map; };   // key 0: the step end to end (ms); study mode: the reference's per-phase keys, (layer + 1) * 10000 + phase
 
@@ -203,6 +212,17 @@ public:
     // Extension: n greedy steps with the token fed back on the device (hipGraph replay, no host
     // round trip per token).  Equivalent to n x {Infer, CommitInferenceResult(greedy)}.
     bool Generate(int query_id, int n_steps, std::vector<int> &new_tokens, float *gpu_ms = nullptr);
+
+    // Extension: lookup decoding (prompt-lookup / "predicted outputs").  Up to max_new_tokens greedy tokens like Generate, but a step
+    // carries the query's last token PLUS draft tokens -- the continuation of the context's last n-gram in `prediction` (nullable),
+    // else in the query's own tokens -- as rows of one batched step on the query's slot (ifa_model_decode_draft); every leading
+    // draft token that equals the step's own greedy choice is a token gained without a step of its own.  The tokens are the greedy
+    // choices of the batched-rows arithmetic (F16 activations on the matrix cores); Generate's single-row step quantises its
+    // activations to int8, so the two agree wherever the top-2 logit gap exceeds that route difference.  Same
+    // conditions as Generate; single-device engines with return_output_tensors = false only (lookup_decoding_active()).
+    bool GenerateLookup(int query_id, int max_new_tokens, std::vector<int> &new_tokens, const std::vector<int> *prediction = nullptr,
+                        LookupStats *stats = nullptr);
+    bool lookup_decoding_active() const { return model_ && !multi_ && !config_.return_output_tensors; }
 
     // id of a strategy name ("sample.top_p" ...); empty: the model's own decoding_strategy
     SamplingStrategyId GetSamplingStrategyId(const std::string &str = "") const override;

@@ -107,6 +107,15 @@ class DecodeWorker:
                                            C.c_void_p(logits_out.data_ptr()) if logits_out is not None else None))
         return out
 
+    def decode_draft(self, tokens, pos0, logits_out=None):
+        """The draft step on the selected KV slot: row i is tokens[i] at position pos0 + i behind rows [0, pos0 + i) -- tokens[0] the
+        last committed token, the rest draft tokens (2..8 rows).  Returns the greedy next token of every row."""
+        toks = np.ascontiguousarray(tokens, np.int32)
+        out = np.zeros(toks.size, np.int32)
+        check(lib().ifa_model_decode_draft(self._h, toks.size, toks.ctypes.data_as(C.c_void_p), int(pos0), out.ctypes.data_as(C.c_void_p),
+                                           C.c_void_p(logits_out.data_ptr()) if logits_out is not None else None))
+        return out
+
     def decode(self, first_token, start_pos, n_steps, timed=True):
         """Greedy batch-1 decode with the fused kernels; returns (tokens, gpu_ms)."""
         out = np.zeros(n_steps, np.int32)
