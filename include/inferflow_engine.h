@@ -135,6 +135,20 @@ int ifa_engine_query_cached_tokens(ifa_engine *e, int query_id);
 int ifa_prefix_cache_plan(const int *records_flat, const int *record_lens, const int *busy, const long long *stamps, int n_slots,
                           const int *prompt, int n_prompt, int min_tokens, int *out3);
 
+/* host-only: the route of an engine step (host/step_plan.h), the rules ifa_engine_infer acts on.
+ * query: one query's step of n_new >= 1 tokens.  multi: a multi-GPU engine; pool_route: the query's candidates come from the device
+ * pool; sampled: its token is chosen on the host.  out3 = {route, logits_rows, copy}; route 0 Multi (every rank steps; the logits
+ * come over iff return_output_tensors or sampled), 1 DecodePool (pool_route, n_new == 1), 2 ForwardPool (pool_route, n_new > 1:
+ * n_new logits rows stay on the device), 3 Decode (n_new == 1, neither tensors nor sampled), 4 Forward (the rest: n_new logits rows
+ * iff return_output_tensors or sampled); copy 0 None, 1 AllRows (return_output_tensors), 2 LastRow (sampled only).
+ * batch: one batched decode step of n_rows rows, rows5[r] = {pool_route, sampled, pool_len, pool_k, wants_logprobs}.  Pool-route rows
+ * get their pools, pool_k = their largest, with_lse = one of them wants logprobs.  A sampled row off the pool route needs its logits
+ * row: without a logprobs row in the step it brings the whole block over and nobody gets a pool; next to one it takes a pool of its
+ * pool_len instead (1 .. IFA_POOL_MAX, else error_row names it).  pool_rows_out[n_rows] receives the pool rows (ascending),
+ * out5 = {number of pool rows, pool_k, with_lse, want_logits, error_row (-1: none)}.  Both: 0, or -1 (bad arguments). */
+int ifa_step_plan_query(int multi, int return_output_tensors, int pool_route, int sampled, int n_new, int *out3);
+int ifa_step_plan_batch(int return_output_tensors, const int *rows5, int n_rows, int *pool_rows_out, int *out5);
+
 /* the per-device worker of partition rank `rank` (an ifa_model * for the ifa_model_* calls of inferflow_amd.h; rank 0 of a
  * single-device engine) and its place in the partition {stage, n_stages, tp_rank, tp_size, layer0, layer1}: the counterpart of
  * reaching a GpuInferenceWorker through InferenceEngine (src/transformer/inference_engine.cc:1916-1984).  NULL / -1: no such rank. */

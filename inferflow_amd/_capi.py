@@ -194,6 +194,8 @@ ENGINE_SIGNATURES = {
     "ifa_engine_model_info": (_i, [_vp, C.c_char_p]),
     "ifa_engine_query_cached_tokens": (_i, [_vp, _i]),
     "ifa_prefix_cache_plan": (_i, [_ip, _ip, _ip, C.POINTER(C.c_longlong), _i, _ip, _i, _i, _ip]),
+    "ifa_step_plan_query": (_i, [_i, _i, _i, _i, _i, _ip]),
+    "ifa_step_plan_batch": (_i, [_i, _ip, _i, _ip, _ip]),
     "ifa_engine_worker": (_vp, [_vp, _i]),
     "ifa_engine_worker_plan": (_i, [_vp, _i, _ip]),
     "ifa_service_parse_request": (_i, [C.c_char_p, _i, C.c_char_p, _sz]),

@@ -11,6 +11,7 @@
 #include "inferflow_service.h"
 #include "perplexity.h"
 #include "prefix_cache.h"
+#include "step_plan.h"
 #include "lookup_draft.h"
 #include "half_bits.h"
 
@@ -288,7 +289,7 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "decoder_layers") return s.hyper_params.decoder_layers;
     if (k == "decoder_heads") return s.hyper_params.decoder_heads;
     if (k == "decoder_kv_heads") return s.hyper_params.decoder_kv_heads;
-    if (k == "max_context_len") return s.max_context_len > 0 ? s.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
+    if (k == "max_context_len") return e->engine.MaxContextLen();
     if (k == "device_weight_data_type") return s.device_weight_data_type;
     if (k == "device_kv_cache_data_type") return s.device_kv_cache_data_type;
     if (k == "partition_ranks") return e->engine.PartitionRanks();
@@ -320,6 +321,31 @@ int ifa_prefix_cache_plan(const int *records_flat, const int *record_lens, const
     PrefixPlan plan;
     if (!PlanPrefixReuse(views, prompt, n_prompt, min_tokens, plan)) { EngineSetError("ifa_prefix_cache_plan: no free slot"); return -1; }
     out3[0] = plan.slot; out3[1] = plan.src_slot; out3[2] = plan.reuse_len;
+    return 0;
+}
+
+// host-only: the route of an engine step (host/step_plan.h)
+int ifa_step_plan_query(int multi, int return_output_tensors, int pool_route, int sampled, int n_new, int *out3)
+{
+    if (n_new < 1 || !out3) { EngineSetError("ifa_step_plan_query: bad arguments"); return -1; }
+    const QueryStepPlan plan = PlanQueryStep(multi != 0, return_output_tensors != 0, pool_route != 0, sampled != 0, n_new);
+    out3[0] = (int)plan.route; out3[1] = plan.logits_rows; out3[2] = (int)plan.copy;
+    return 0;
+}
+
+int ifa_step_plan_batch(int return_output_tensors, const int *rows5, int n_rows, int *pool_rows_out, int *out5)
+{
+    if (!rows5 || n_rows < 1 || !pool_rows_out || !out5) { EngineSetError("ifa_step_plan_batch: bad arguments"); return -1; }
+    std::vector<BatchRow> rows((size_t)n_rows);
+    for (int r = 0; r < n_rows; r++) {
+        const int *f = rows5 + (size_t)r * 5;
+        if (f[2] < 0 || f[3] < 0) { EngineSetError("ifa_step_plan_batch: row %d", r); return -1; }
+        rows[(size_t)r].pool_route = f[0] != 0; rows[(size_t)r].sampled = f[1] != 0; rows[(size_t)r].pool_len = f[2]; rows[(size_t)r].pool_k = f[3];
+        rows[(size_t)r].wants_logprobs = f[4] != 0;
+    }
+    const BatchStepPlan plan = PlanBatchStep(return_output_tensors != 0, rows);
+    for (size_t i = 0; i < plan.pool_rows.size(); i++) pool_rows_out[i] = plan.pool_rows[i];
+    out5[0] = (int)plan.pool_rows.size(); out5[1] = plan.pool_k; out5[2] = plan.with_lse ? 1 : 0; out5[3] = plan.want_logits ? 1 : 0; out5[4] = plan.error_row;
     return 0;
 }
 

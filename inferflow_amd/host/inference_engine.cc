@@ -5,255 +5,27 @@
 // picks one and commits it with CommitInferenceResult (llm_inference.cc:345-457).
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
-#include <cstring>
-#include <functional>
-#include <mutex>
-#include <thread>
 
 #include "inferflow_amd.h"
 #include "inference_engine.h"
-#include "ifa_ini.h"
+#include "step_plan.h"
 #include "prefix_cache.h"
 #include "lookup_draft.h"
 #include "half_bits.h"
 
 namespace inferflow_amd {
 
-// ---------------------------------------------------------------------------------------------- multi-GPU partitions
-// One worker (ifa_model) and one persistent host thread per GPU.  The reference creates and joins a thread per GPU inside
-// every Infer() (inference_engine.cc:1203-1206, 1261-1283) and lets the workers rendezvous through GpuInfGlobalData's
-// mutex; here the threads live as long as the engine and every exchange is a collective of the C ABI enqueued on the
-// worker's stream (csrc/ifa_comm.hip), so a thread only ever blocks at the end of its step.
-struct InferenceEngine::MultiGpu {
-    std::vector<WorkerPlan> plans;
-    std::vector<ifa_comm *> world, tp;          // per rank (world: only with several device groups; tp: only with groups of > 1)
-    std::vector<ifa_tp_topology> topo;
-    std::vector<void *> shard_dev;              // per rank: logits shard buffer [rows][V / P] (last group only)
-    size_t shard_rows = 0;
-    int G = 1, P = 1;
-    bool force_collectives = false;
-    // thread pool
-    std::vector<std::thread> threads;
-    std::mutex mu;
-    std::condition_variable cv_job, cv_done;
-    std::function<int(int)> job;
-    uint64_t generation = 0;
-    int pending = 0;
-    bool stop = false;
-    int first_failed = -1;
-    bool broken = false;      // a rank failed inside a step: the communicators were aborted, the engine cannot continue
-    std::vector<std::string> errors;
-
-    // A rank that fails before or between the collectives of a step leaves its peers blocked in theirs (RCCL, or the
-    // loopback group's rendezvous) and Run() would never return.  The failing rank's thread aborts every communicator of
-    // the job: the peers come back with an error, Run() reports the FIRST failure.
-    void AbortGroups()
-    {
-        for (ifa_comm *c : tp) if (c) ifa_comm_abort(c);
-        for (ifa_comm *c : world) if (c) ifa_comm_abort(c);
-    }
-
-    void Start()
-    {
-        const int n = (int)plans.size();
-        errors.assign((size_t)n, std::string());
-        for (int r = 0; r < n; r++)
-            threads.emplace_back([this, r]() {
-                uint64_t seen = 0;
-                for (;;) {
-                    std::function<int(int)> fn;
-                    {
-                        std::unique_lock<std::mutex> lk(mu);
-                        cv_job.wait(lk, [&] { return stop || generation != seen; });
-                        if (stop) return;
-                        seen = generation; fn = job;
-                    }
-                    const int rc = fn(r);
-                    bool first_failure = false;
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        errors[(size_t)r] = rc == 0 ? std::string() : std::string(ifa_last_error());   // (thread-local message)
-                        if (rc != 0 && errors[(size_t)r].empty()) errors[(size_t)r] = "error " + std::to_string(rc);
-                        if (rc != 0 && !broken) { broken = true; first_failure = true; first_failed = r; }
-                    }
-                    if (first_failure && plans.size() > 1) AbortGroups();
-                    {
-                        std::lock_guard<std::mutex> lk(mu);
-                        if (--pending == 0) cv_done.notify_all();
-                    }
-                }
-            });
-    }
-    // fn(rank) on every rank's thread at once; false + message if any failed
-    bool Run(const std::function<int(int)> &fn, const char *what)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (broken) { EngineSetError("%s: the engine's device group was aborted after an earlier failure; create a new engine", what); return false; }
-            job = fn; pending = (int)plans.size(); generation++;
-        }
-        cv_job.notify_all();
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return pending == 0; });
-        if (first_failed >= 0) {      // the rank whose failure started it (the others only report the abort)
-            const size_t r = (size_t)first_failed;
-            EngineSetError("%s failed on rank %zu (device %d): %s", what, r, plans[r].device, errors[r].c_str());
-            return false;
-        }
-        for (size_t r = 0; r < errors.size(); r++)
-            if (!errors[r].empty()) { EngineSetError("%s failed on rank %zu (device %d): %s", what, r, plans[r].device, errors[r].c_str()); return false; }
-        return true;
-    }
-    ~MultiGpu()
-    {
-        { std::lock_guard<std::mutex> lk(mu); stop = true; }
-        cv_job.notify_all();
-        for (std::thread &t : threads) if (t.joinable()) t.join();
-        for (size_t r = 0; r < plans.size(); r++) {
-            if (r < shard_dev.size() && shard_dev[r]) { ifa_set_device(plans[r].device); ifa_free(shard_dev[r]); }
-            if (plans[r].model) ifa_model_destroy(plans[r].model);
-        }
-        for (ifa_comm *c : tp) if (c) ifa_comm_destroy(c);
-        for (ifa_comm *c : world) if (c) ifa_comm_destroy(c);
-    }
-};
-
 InferenceEngine::InferenceEngine() {}
 InferenceEngine::~InferenceEngine() { Clear(); }
 
 void InferenceEngine::Clear()
 {
-    if (multi_) { delete multi_; multi_ = nullptr; model_ = nullptr; }
+    if (multi_) { FreeMulti(); model_ = nullptr; }
     if (model_) { ifa_model_destroy(model_); model_ = nullptr; }
     if (logits_dev_) { ifa_free(logits_dev_); logits_dev_ = nullptr; logits_rows_ = 0; }
     queries_.clear();
     prefix_active_ = false; slot_records_.clear();
     use_clock_ = prefix_hits_ = prefix_tokens_ = prefix_copies_ = 0;
-}
-
-static bool LoadDeviceGroups(std::vector<std::vector<int>> &groups, const IniConfig &cfg, const std::string &section, const std::string &key)
-{
-    // "0;1" = two groups (by layer), "0&1" = one group of two (by tensor)  (inference_engine.cc:1738-1783)
-    groups.clear();
-    std::string str;
-    cfg.GetItem(section, key, str);
-    for (std::string tok : IniConfig::Split(str, ",;")) {
-        tok = IniConfig::Trim(tok);
-        if (tok.empty()) continue;
-        std::vector<int> sub;
-        for (std::string s : IniConfig::Split(tok, "&|")) { s = IniConfig::Trim(s); if (!s.empty()) sub.push_back(atoi(s.c_str())); }
-        groups.push_back(sub);
-    }
-    for (size_t g = 1; g < groups.size(); g++)
-        if (groups[g].size() != groups[0].size()) {
-            EngineSetError("All device groups should have the same size: %zu vs. %zu", groups[0].size(), groups[g].size());
-            return false;
-        }
-    return true;
-}
-
-static bool LoadModelSpec(ModelSpec &spec, const IniConfig &cfg, const std::string &section)
-{
-    if (!cfg.GetItem(section, "model_dir", spec.dir) || spec.dir.empty()) {
-        EngineSetError("The directory of model \"%s\" should not be empty", spec.sid.c_str()); return false;
-    }
-    if (spec.dir.back() != '/' && spec.dir.back() != '\\') spec.dir += '/';
-    if (!cfg.GetItem(section, "model_specification_file", spec.spec_file)) cfg.GetItem(section, "model_spec_file", spec.spec_file);
-    if (spec.spec_file.empty()) { EngineSetError("The specification file of model \"%s\" should not be empty", spec.sid.c_str()); return false; }
-    cfg.GetItem(section, "decoding_strategy", spec.decoding_strategy);
-    cfg.GetItem(section, "decoder_input_template", spec.decoder_input_template);
-    cfg.GetItem(section, "prompt_template", spec.decoder_input_template);
-    std::string str;
-    if (cfg.GetItem(section, "device_weight_data_type", str) && !str.empty()) {
-        const int dt = ifa_dtype_from_name(IniConfig::Lower(str).c_str());
-        if (dt < 0) { EngineSetError("Invalid device_weight_data_type for model %s", spec.sid.c_str()); return false; }
-        spec.device_weight_data_type = dt;
-    }
-    {   // device_weight_data_type.<tensor>: element size >= 2 -> F16 (inference_engine.cc:1685-1687)
-        static const struct { const char *name; int tid; } kTensors[] = {{"attn_wq", IFA_T_WQ}, {"attn_wk", IFA_T_WK}, {"attn_wv", IFA_T_WV},
-            {"attn_wo", IFA_T_WO}, {"ffn_w1", IFA_T_W1}, {"ffn_w2", IFA_T_W2}, {"ffn_w3", IFA_T_W3}};
-        for (const auto &kt : kTensors) {
-            std::string v;
-            if (!cfg.GetItem(section, std::string("device_weight_data_type.") + kt.name, v) || v.empty()) continue;
-            const int dt = ifa_dtype_from_name(IniConfig::Lower(v).c_str());
-            if (dt < 0) { EngineSetError("Invalid device_weight_data_type.%s for model %s", kt.name, spec.sid.c_str()); return false; }
-            spec.device_weight_data_types[kt.tid] = (dt == IFA_F32 || dt == IFA_F16) ? IFA_F16 : dt;
-        }
-    }
-    str.clear();
-    if (cfg.GetItem(section, "device_kv_cache_data_type", str) && !str.empty()) {
-        const int dt = ifa_dtype_from_name(IniConfig::Lower(str).c_str());
-        if (dt < 0) { EngineSetError("Invalid device_kv_cache_data_type for model %s", spec.sid.c_str()); return false; }
-        // element size >= 2 -> F16, anything smaller -> Q8_B32T2   (inference_engine.cc:1701-1703)
-        spec.device_kv_cache_data_type = (dt == IFA_F32 || dt == IFA_F16) ? IFA_F16 : IFA_Q8_B32T2;
-    }
-    cfg.GetItem(section, "tensor_quant_threshold", spec.tensor_quant_threshold);
-    if (!LoadDeviceGroups(spec.device_groups, cfg, section, "devices")) return false;
-    cfg.GetItem(section, "max_context_len", spec.max_context_len);
-    const bool is_abs = !spec.spec_file.empty() && spec.spec_file[0] == '/';
-    return LoadModelSpecJson(spec, is_abs ? spec.spec_file : spec.dir + spec.spec_file);
-}
-
-static bool LookupConfigOk(const InferenceConfig &c)
-{
-    if (c.lookup_draft_len < 1 || c.lookup_draft_len > 7) { EngineSetError("lookup_draft_len must be 1..7 (got %d)", c.lookup_draft_len); return false; }
-    if (c.lookup_ngram_min < 1 || c.lookup_ngram_max < c.lookup_ngram_min) {
-        EngineSetError("lookup_ngram_min must be at least 1 and lookup_ngram_max no smaller (got %d, %d)", c.lookup_ngram_min, c.lookup_ngram_max);
-        return false;
-    }
-    return true;
-}
-
-bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &config_path,
-                                 const std::string &section, const std::string &data_root_dir)
-{
-    IniConfig cfg; std::string err;
-    if (!cfg.Load(config_path, &err)) { EngineSetError("Failed to load the configuration file: %s", err.c_str()); return false; }
-    std::string root = data_root_dir;
-    if (root.empty()) { IniConfig probe; probe.Load(config_path); probe.GetItem("app_env.base", "data_root_dir", root); }
-    if (!root.empty()) cfg.AddMacro("data_root_dir", root);
-    config.data_dir = root;
-    std::string global_model_dir;
-    cfg.GetItem("main", "global_model_dir", global_model_dir);
-    cfg.AddMacro("global_model_dir", global_model_dir);
-    if (!cfg.HasSection(section)) { EngineSetError("Section [%s] is missing in %s", section.c_str(), config_path.c_str()); return false; }
-    if (!LoadDeviceGroups(config.device_groups, cfg, section, "devices")) return false;
-    if (config.device_groups.empty()) config.device_groups.push_back({0});
-    int cpu_layers = 0;
-    if (cfg.GetItem(section, "cpu_layer_count", cpu_layers)) config.decoder_cpu_layer_count = cpu_layers;
-    cfg.GetItem(section, "encoder_cpu_layer_count", config.encoder_cpu_layer_count);
-    cfg.GetItem(section, "decoder_cpu_layer_count", config.decoder_cpu_layer_count);
-    std::string models;
-    if (!cfg.GetItem(section, "models", models) || IniConfig::Trim(models).empty()) {
-        EngineSetError("Item \"models\" is missing in section [%s]", section.c_str()); return false;
-    }
-    config.models.clear();
-    for (std::string name : IniConfig::Split(models, ",;")) {
-        name = IniConfig::Trim(name);
-        if (name.empty()) continue;
-        ModelSpec spec; spec.sid = name;
-        cfg.AddMacro("model_name", name);
-        if (!LoadModelSpec(spec, cfg, "model." + name)) return false;
-        if (spec.device_groups.empty()) spec.device_groups = config.device_groups;
-        config.models.push_back(spec);
-    }
-    cfg.GetItem(section, "max_concurrent_queries", config.max_concurrent_queries);
-    cfg.GetItem(section, "cpu_threads", config.cpu_threads);
-    cfg.GetItem(section, "return_output_tensors", config.return_output_tensors);
-    cfg.GetItem(section, "dynamic_batching_min_queries", config.dynamic_batching_min_queries);
-    cfg.GetItem(section, "force_partition_path", config.force_partition_path);
-    cfg.GetItem(section, "device_sampling_pool", config.device_sampling_pool);
-    cfg.GetItem(section, "prefix_cache", config.prefix_cache);
-    cfg.GetItem(section, "prefix_cache_min_tokens", config.prefix_cache_min_tokens);
-    if (config.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config.prefix_cache_min_tokens); return false; }
-    cfg.GetItem(section, "lookup_draft_len", config.lookup_draft_len);
-    cfg.GetItem(section, "lookup_ngram_max", config.lookup_ngram_max);
-    cfg.GetItem(section, "lookup_ngram_min", config.lookup_ngram_min);
-    if (!LookupConfigOk(config)) return false;
-    cfg.GetItem(section, "is_study_mode", config.debug.is_study_mode);
-    cfg.GetItem(section, "show_tensors", config.debug.show_tensors);
-    return true;
 }
 
 bool InferenceEngine::Init(const InferenceConfig &cfg)
@@ -294,9 +66,7 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
         default_sampling_.excluded_ids = excl;
         host_greedy_ = excl.size() > 3;
         if (excl.size() > 3) excl.resize(3);
-        std::vector<ifa_model *> all;
-        if (multi_) for (WorkerPlan &w : multi_->plans) all.push_back(w.model); else all.push_back(model_);
-        for (ifa_model *mm : all)
+        for (ifa_model *mm : Workers())
             if (ifa_model_set_excluded_tokens(mm, excl.data(), (int)excl.size()) != IFA_OK) { EngineSetError("excluded tokens: %s", ifa_last_error()); Clear(); return false; }
         // the device pool's mask has no limit: the full list
         const std::vector<int> &full = default_sampling_.excluded_ids;
@@ -311,12 +81,8 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
     if (perf_phases_ && ifa_model_set_option(model_, "perf_stat", 1) != IFA_OK) { EngineSetError("perf_stat: %s", ifa_last_error()); Clear(); return false; }
     // one KV cache per concurrent query, like the reference's per-query LayerKVCache sets
     kv_slots_ = std::max(1, std::min(config_.max_concurrent_queries, 64));
-    {
-        std::vector<ifa_model *> all;
-        if (multi_) for (WorkerPlan &w : multi_->plans) all.push_back(w.model); else all.push_back(model_);
-        for (ifa_model *mm : all)
-            if (ifa_model_kv_slots(mm, kv_slots_) != IFA_OK) { EngineSetError("KV caches for %d queries: %s", kv_slots_, ifa_last_error()); Clear(); return false; }
-    }
+    for (ifa_model *mm : Workers())
+        if (ifa_model_kv_slots(mm, kv_slots_) != IFA_OK) { EngineSetError("KV caches for %d queries: %s", kv_slots_, ifa_last_error()); Clear(); return false; }
     // prompt prefix cache: one device, and no caller that expects a logits row per prompt token
     if (config_.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config_.prefix_cache_min_tokens); Clear(); return false; }
     prefix_active_ = config_.prefix_cache && !multi_ && !config_.return_output_tensors;
@@ -325,157 +91,11 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
     return true;
 }
 
-// devices = G groups of P: workers in the reference's order (rank = group * P + position), layer ranges by
-// SplitGpuLayers, BY_TENSOR slices inside a group (model_loader.cc), one communicator per group + one for the job
-bool InferenceEngine::InitMulti(const std::vector<std::vector<int>> &groups)
-{
-    const int G = (int)groups.size(), P = (int)groups[0].size();
-    if (P < 1) { EngineSetError("empty device group"); return false; }
-    multi_ = new MultiGpu();
-    MultiGpu &M = *multi_;
-    M.G = G; M.P = P; M.force_collectives = config_.force_partition_path;
-    std::vector<int> all_devices;
-    for (int g = 0; g < G; g++)
-        for (int r = 0; r < P; r++) {
-            WorkerPlan w;
-            w.device = groups[(size_t)g][(size_t)r]; w.stage = g; w.n_stages = G; w.tp_rank = r; w.tp_size = P;
-            M.plans.push_back(w);
-            all_devices.push_back(w.device);
-        }
-    // a device named more than once: only as "every rank on ONE device" (loopback groups of the C ABI: the multi-rank
-    // paths on a 1-GPU box, tests); anything else is a configuration mistake
-    bool dup = false, all_same = true;
-    for (size_t i = 0; i < all_devices.size(); i++) {
-        all_same = all_same && all_devices[i] == all_devices[0];
-        for (size_t j = i + 1; j < all_devices.size(); j++) dup = dup || all_devices[i] == all_devices[j];
-    }
-    if (dup && !all_same) { EngineSetError("a device appears twice in `devices`"); return false; }
-    if (!BuildWorkers(M.plans, spec_)) return false;
-    const int R = G * P;
-    M.world.assign((size_t)R, nullptr); M.tp.assign((size_t)R, nullptr);
-    if (G > 1 && ifa_comm_init_all(all_devices.data(), R, M.world.data()) != IFA_OK) { EngineSetError("job communicator: %s", ifa_last_error()); return false; }
-    if (P > 1 || M.force_collectives)
-        for (int g = 0; g < G; g++)
-            if (ifa_comm_init_all(groups[(size_t)g].data(), P, M.tp.data() + (size_t)g * P) != IFA_OK) { EngineSetError("group communicator: %s", ifa_last_error()); return false; }
-    const int V = spec_.hyper_params.vocab_size;
-    M.topo.resize((size_t)R);
-    for (int i = 0; i < R; i++) {
-        ifa_tp_topology &t = M.topo[(size_t)i];
-        memset(&t, 0, sizeof(t));
-        const int g = i / P, r = i % P;
-        t.tp = M.tp[(size_t)i]; t.world = M.world[(size_t)i];
-        t.stage = g; t.n_stages = G;
-        t.prev_rank = g > 0 ? i - P : -1; t.next_rank = g + 1 < G ? i + P : -1;
-        t.token_src = (G - 1) * P;                  // first rank of the last group announces the token
-        t.vocab_offset = r * (V / P);
-        t.force_collectives = M.force_collectives ? 1 : 0;
-    }
-    M.shard_dev.assign((size_t)R, nullptr);
-    M.Start();
-    model_ = M.plans[0].model;      // (handle for model_info-style queries; steps go through the rank threads)
-    return true;
-}
-
-// one step of one query on every rank: n_new tokens from q.processed on; `next` = the greedy next token.  want_tensor:
-// item.output_tensor receives the [n_new][vocab] logits assembled from the last group's vocabulary shards.
-bool InferenceEngine::MultiStep(Query &q, int n_new, bool want_tensor, QueryInferenceResult &item, int &next)
-{
-    MultiGpu &M = *multi_;
-    const int R = (int)M.plans.size(), P = M.P, V = spec_.hyper_params.vocab_size;
-    const size_t shard = (size_t)V / (size_t)P;
-    if (want_tensor && (size_t)n_new > M.shard_rows) {
-        for (int i = (M.G - 1) * P; i < R; i++) {
-            ifa_set_device(M.plans[(size_t)i].device);
-            if (M.shard_dev[(size_t)i]) { ifa_free(M.shard_dev[(size_t)i]); M.shard_dev[(size_t)i] = nullptr; }
-            if (ifa_malloc(&M.shard_dev[(size_t)i], (size_t)n_new * shard * 2) != IFA_OK) { EngineSetError("logits buffer: %s", ifa_last_error()); return false; }
-        }
-        M.shard_rows = (size_t)n_new;
-    }
-    std::vector<int> nexts((size_t)R, -1);
-    std::vector<std::vector<uint16_t>> host((size_t)R);
-    const int *toks = q.tokens.data() + q.processed;
-    const int start = q.processed, slot = q.kv_slot;
-    const bool ok = M.Run([&](int i) -> int {
-        ifa_model *mm = M.plans[(size_t)i].model;
-        int rc = ifa_model_select_kv(mm, slot);
-        if (rc) return rc;
-        void *lg = want_tensor ? M.shard_dev[(size_t)i] : nullptr;
-        if (n_new == 1 && !lg) rc = ifa_model_tp_decode(mm, &M.topo[(size_t)i], toks[0], start, 1, &nexts[(size_t)i], nullptr);
-        else rc = ifa_model_tp_prefill(mm, &M.topo[(size_t)i], toks, n_new, start, lg, &nexts[(size_t)i]);
-        if (rc) return rc;
-        if (lg) {
-            host[(size_t)i].resize((size_t)n_new * shard);
-            rc = ifa_memcpy_d2h(host[(size_t)i].data(), lg, (size_t)n_new * shard * 2, ifa_model_stream(mm));
-            if (!rc) rc = ifa_stream_sync(ifa_model_stream(mm));
-        }
-        return rc;
-    }, n_new == 1 ? "decode step" : "prompt step");
-    if (!ok) return false;
-    next = nexts[(size_t)(R - 1)];
-    for (int i = 0; i < R; i++)
-        if (nexts[(size_t)i] != next) { EngineSetError("ranks disagree on the next token (%d vs %d)", nexts[(size_t)i], next); return false; }
-    if (want_tensor) {
-        item.output_rows = n_new; item.output_cols = V;
-        item.output_tensor.resize((size_t)n_new * V);
-        for (int r = 0; r < P; r++) {
-            const std::vector<uint16_t> &h = host[(size_t)((M.G - 1) * P + r)];
-            for (int row = 0; row < n_new; row++)
-                memcpy(&item.output_tensor[(size_t)row * V + (size_t)r * shard], &h[(size_t)row * shard], shard * 2);
-        }
-    }
-    return true;
-}
-
-// One batched decode step of n queries over the (single) tensor-parallel device group: every rank's thread calls
-// ifa_model_tp_decode_batch with the same rows; `all` (if wanted) receives the [n][vocab] logits assembled from the ranks'
-// vocabulary shards.
-bool InferenceEngine::MultiBatchStep(const std::vector<int> &toks, const std::vector<int> &pos, const std::vector<int> &slots,
-                                     std::vector<int> &next, bool want_tensor, std::vector<uint16_t> &all)
-{
-    MultiGpu &M = *multi_;
-    const int R = (int)M.plans.size(), P = M.P, V = spec_.hyper_params.vocab_size, n = (int)toks.size();
-    const size_t shard = (size_t)V / (size_t)P;
-    if (want_tensor && (size_t)n > M.shard_rows) {
-        for (int i = (M.G - 1) * P; i < R; i++) {
-            ifa_set_device(M.plans[(size_t)i].device);
-            if (M.shard_dev[(size_t)i]) { ifa_free(M.shard_dev[(size_t)i]); M.shard_dev[(size_t)i] = nullptr; }
-            if (ifa_malloc(&M.shard_dev[(size_t)i], (size_t)n * shard * 2) != IFA_OK) { EngineSetError("logits buffer: %s", ifa_last_error()); return false; }
-        }
-        M.shard_rows = (size_t)n;
-    }
-    std::vector<std::vector<int>> nexts((size_t)R, std::vector<int>((size_t)n, -1));
-    std::vector<std::vector<uint16_t>> host((size_t)R);
-    const bool ok = M.Run([&](int i) -> int {
-        ifa_model *mm = M.plans[(size_t)i].model;
-        void *lg = want_tensor ? M.shard_dev[(size_t)i] : nullptr;
-        int rc = ifa_model_tp_decode_batch(mm, &M.topo[(size_t)i], n, toks.data(), pos.data(), slots.data(), nexts[(size_t)i].data(), lg);
-        if (rc) return rc;
-        if (lg) {
-            host[(size_t)i].resize((size_t)n * shard);
-            rc = ifa_memcpy_d2h(host[(size_t)i].data(), lg, (size_t)n * shard * 2, ifa_model_stream(mm));
-            if (!rc) rc = ifa_stream_sync(ifa_model_stream(mm));
-        }
-        return rc;
-    }, "batched decode step");
-    if (!ok) return false;
-    next = nexts[(size_t)(R - 1)];
-    for (int i = 0; i < R; i++)
-        if (nexts[(size_t)i] != next) { EngineSetError("ranks disagree on the next tokens of a batched step"); return false; }
-    if (want_tensor) {
-        all.resize((size_t)n * V);
-        for (int r = 0; r < P; r++) {
-            const std::vector<uint16_t> &h = host[(size_t)((M.G - 1) * P + r)];
-            for (int row = 0; row < n; row++) memcpy(&all[(size_t)row * V + (size_t)r * shard], &h[(size_t)row * shard], shard * 2);
-        }
-    }
-    return true;
-}
-
 int InferenceEngine::AddQuery(const std::vector<int> &tokens, const QueryOptions &query_options)
 {
     if (!model_) { EngineSetError("The engine is not initialized"); return -1; }
     if (tokens.empty()) { EngineSetError("Empty query"); return -1; }
-    const int max_ctx = spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
+    const int max_ctx = MaxContextLen();
     if ((int)tokens.size() >= max_ctx) { EngineSetError("The query has %zu tokens; max_context_len is %d", tokens.size(), max_ctx); return -1; }
     for (int t : tokens)
         if (t < 0 || t >= spec_.hyper_params.vocab_size) { EngineSetError("Token id %d is out of range", t); return -1; }
@@ -539,25 +159,6 @@ int InferenceEngine::QueryCachedTokens(int query_id) const
 }
 
 int InferenceEngine::QueryCount() const { return (int)queries_.size(); }
-int InferenceEngine::PartitionRanks() const { return multi_ ? (int)multi_->plans.size() : 1; }
-ifa_model *InferenceEngine::worker(int rank)
-{
-    if (!multi_) return rank == 0 ? model_ : nullptr;
-    return rank >= 0 && rank < (int)multi_->plans.size() ? multi_->plans[(size_t)rank].model : nullptr;
-}
-bool InferenceEngine::WorkerPlanOf(int rank, int out6[6]) const
-{
-    if (!multi_) {
-        if (rank != 0) return false;
-        out6[0] = 0; out6[1] = 1; out6[2] = 0; out6[3] = 1; out6[4] = 0; out6[5] = spec_.hyper_params.decoder_layers;
-        return true;
-    }
-    if (rank < 0 || rank >= (int)multi_->plans.size()) return false;
-    const WorkerPlan &w = multi_->plans[(size_t)rank];
-    out6[0] = w.stage; out6[1] = w.n_stages; out6[2] = w.tp_rank; out6[3] = w.tp_size; out6[4] = w.layer0; out6[5] = w.layer1;
-    return true;
-}
-
 SamplingStrategyId InferenceEngine::GetSamplingStrategyId(const std::string &str) const
 {
     if (str.empty()) return default_strategy_;
@@ -604,7 +205,7 @@ bool InferenceEngine::PoolRoute(const Query &q) const
     const int k = PoolK(q);
     if (q.options.logprobs >= 0) return k <= IFA_POOL_MAX;      // logprobs ride on the pool whatever device_sampling_pool says
     if (!config_.device_sampling_pool) return false;
-    if (q.strategy == SamplingStrategyId::Greedy && !host_greedy_) return false;      // (the device argmax serves it)
+    if (!Sampled(q)) return false;      // (the device argmax serves it)
     return k >= 1 && k <= IFA_POOL_MAX;
 }
 
@@ -639,7 +240,7 @@ bool InferenceEngine::ScoreTokens(const std::vector<int> &tokens, std::vector<fl
     if (!model_) { EngineSetError("The engine is not initialized"); return false; }
     if (multi_) { EngineSetError("ScoreTokens is not available on a multi-device engine (the vocabulary is sharded)"); return false; }
     const int n = (int)tokens.size();
-    const int max_ctx = spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
+    const int max_ctx = MaxContextLen();
     if (n < 2) { EngineSetError("ScoreTokens needs at least two tokens"); return false; }
     if (n >= max_ctx) { EngineSetError("ScoreTokens: %d tokens; max_context_len is %d", n, max_ctx); return false; }
     for (int t : tokens)
@@ -684,197 +285,187 @@ bool InferenceEngine::QueryEnded(int query_id) const
     return it == queries_.end() || it->second.ended;
 }
 
+// ---------------------------------------------------------------------------------------------- Infer
+// Infer() plans every step in pure code (step_plan.h) and runs the plan.  q.processed and the item in res.items are committed only
+// after every fallible call of the step has succeeded: a query of a failed Infer() still has its tokens pending for a retry.
+int CopyToHostSync(ifa_model *m, void *dst, const void *src, size_t bytes)
+{
+    const int rc = ifa_memcpy_d2h(dst, src, bytes, ifa_model_stream(m));
+    return rc != IFA_OK ? rc : ifa_stream_sync(ifa_model_stream(m));
+}
+
+static IdWeight OneToken(int id) { IdWeight w; w.id = id; w.weight = 1.0f; return w; }      // (the device argmax chose)
+
+bool InferenceEngine::EnsureLogitsRows(size_t n)
+{
+    if (n <= logits_rows_) return true;
+    if (logits_dev_) ifa_free(logits_dev_);
+    logits_dev_ = nullptr; logits_rows_ = 0;
+    if (ifa_malloc(&logits_dev_, n * (size_t)spec_.hyper_params.vocab_size * 2) != IFA_OK) { EngineSetError("logits buffer: %s", ifa_last_error()); return false; }
+    logits_rows_ = n;
+    return true;
+}
+
+// rows [row0, row0 + rows) of the engine's logits buffer
+bool InferenceEngine::LogitsToHost(uint16_t *dst, size_t row0, size_t rows)
+{
+    const size_t V = (size_t)spec_.hyper_params.vocab_size;
+    if (CopyToHostSync(model_, dst, (const uint16_t *)logits_dev_ + row0 * V, rows * V * 2) != IFA_OK) { EngineSetError("logits copy: %s", ifa_last_error()); return false; }
+    return true;
+}
+
+// the batched worker call of a single-device engine: the pools of plan.pool_rows and / or the [n][vocab] block come to the host
+bool InferenceEngine::BatchStep(const std::vector<int> &toks, const std::vector<int> &pos, const std::vector<int> &slots, std::vector<int> &next,
+                                const BatchStepPlan &plan, BatchPools &pools, std::vector<uint16_t> &all)
+{
+    const int n = (int)toks.size();
+    const size_t ns = plan.pool_rows.size();
+    if (plan.want_logits && !EnsureLogitsRows((size_t)n)) return false;
+    if (ns > 0) {       // no logits row leaves the device for these rows; a query reads its own prefix of the launch's sorted pool
+        pools.ids.resize(ns * (size_t)plan.pool_k); pools.vals.resize(ns * (size_t)plan.pool_k); pools.counts.resize(ns);
+        if (!SetPoolLse(plan.with_lse)) return false;
+        if (ifa_model_decode_batch_pool(model_, n, toks.data(), pos.data(), slots.data(), next.data(), plan.pool_k, plan.pool_rows.data(), (int)ns,
+                                        pools.ids.data(), pools.vals.data(), pools.counts.data()) != IFA_OK) {
+            EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
+        }
+        if (plan.with_lse) {
+            pools.lse.resize(ns); int got = 0;
+            if (ifa_model_pool_lse(model_, pools.lse.data(), (int)ns, &got) != IFA_OK || got != (int)ns) { EngineSetError("pool lse: %s", ifa_last_error()); return false; }
+        }
+        sampled_fused_steps_ += (long long)ns;
+    } else if (ifa_model_decode_batch(model_, n, toks.data(), pos.data(), slots.data(), next.data(), plan.want_logits ? logits_dev_ : nullptr) != IFA_OK) {
+        EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
+    }
+    if (plan.want_logits) all.resize((size_t)n * (size_t)spec_.hyper_params.vocab_size);
+    return !plan.want_logits || LogitsToHost(all.data(), 0, (size_t)n);
+}
+
+// dynamic batching: every query that advances by exactly one token joins ONE step -- the linear layers stream the weights once
+// for all of them (ifa_model_decode_batch); prefills and single queries take InferQuery
+bool InferenceEngine::InferBatch(const std::vector<Query *> &batch, InferenceResult &res)
+{
+    const int n = (int)batch.size(), V = spec_.hyper_params.vocab_size;
+    std::vector<int> toks((size_t)n), pos((size_t)n), slots((size_t)n), next((size_t)n, -1);
+    std::vector<BatchRow> rows((size_t)n);
+    for (int r = 0; r < n; r++) {
+        const Query &q = *batch[(size_t)r];
+        toks[(size_t)r] = q.tokens.back(); pos[(size_t)r] = q.processed; slots[(size_t)r] = q.kv_slot;
+        BatchRow &row = rows[(size_t)r];
+        row.pool_route = PoolRoute(q); row.sampled = Sampled(q); row.pool_len = PoolLen(q); row.pool_k = PoolK(q); row.wants_logprobs = q.options.logprobs >= 0;
+    }
+    const BatchStepPlan plan = PlanBatchStep(config_.return_output_tensors, rows);
+    if (plan.error_row >= 0) {
+        EngineSetError("query %d samples from %d candidates, more than a device pool holds; it cannot share a step with a logprobs query",
+                       batch[(size_t)plan.error_row]->id, rows[(size_t)plan.error_row].pool_len);
+        return false;
+    }
+    BatchPools pools; std::vector<uint16_t> all;
+    // Query batching over a tensor-parallel device group (the reference: query batching, inference_engine.cc:1054-1124,
+    // inside Infer_TensorParallelism, :1222-1296): every rank runs ONE batched step over the same queries -- merges
+    // over [n][dim], one distributed argmax per row (ifa_model_tp_decode_batch) -- and hands back its vocabulary shard
+    if (multi_ ? !MultiBatchStep(toks, pos, slots, next, plan.want_logits, all) : !BatchStep(toks, pos, slots, next, plan, pools, all)) return false;
+    // the step was ONE worker call: its rows are committed together, once the item of every row is complete
+    std::vector<QueryInferenceResult> items((size_t)n);
+    for (int r = 0; r < n; r++) {
+        Query &q = *batch[(size_t)r];
+        const BatchRow &row = rows[(size_t)r];
+        QueryInferenceResult &item = items[(size_t)r]; item.query_id = q.id; item.prefix_len = q.processed;
+        if (!all.empty() && config_.return_output_tensors) { item.output_rows = 1; item.output_cols = V; item.output_tensor.assign(all.begin() + (size_t)r * V, all.begin() + (size_t)(r + 1) * V); }
+        item.next_tokens.push_back(OneToken(next[(size_t)r]));
+        const auto pr = std::find(plan.pool_rows.begin(), plan.pool_rows.end(), r);
+        if (pr == plan.pool_rows.end()) {
+            if (row.sampled && !SampleRow(q, all.data() + (size_t)r * V, item)) return false;
+            continue;
+        }
+        const size_t j = (size_t)(pr - plan.pool_rows.begin());
+        const int *ids = pools.ids.data() + j * (size_t)plan.pool_k; const uint16_t *vals = pools.vals.data() + j * (size_t)plan.pool_k;
+        if (row.sampled && !SamplePool(q, ids, vals, std::min(pools.counts[j], row.pool_len), item)) return false;
+        if (row.wants_logprobs && !FillLogprobs(q, ids, vals, std::min(pools.counts[j], row.pool_k), pools.lse[j], item)) return false;
+    }
+    for (int r = 0; r < n; r++) { batch[(size_t)r]->processed = (int)batch[(size_t)r]->tokens.size(); res.items.push_back(std::move(items[(size_t)r])); }
+    return true;
+}
+
+// a step that ends in the candidate pool (DecodePool / ForwardPool): nothing of size V leaves the device
+bool InferenceEngine::PoolStep(Query &q, int n_new, QueryInferenceResult &item)
+{
+    const bool lp = q.options.logprobs >= 0;
+    if (!SetPoolLse(lp)) return false;
+    int ids[IFA_POOL_MAX], cnt = 0, next = -1; uint16_t vals[IFA_POOL_MAX];
+    // (a prompt keeps the forward step -- lm_head over all rows into the engine's logits buffer, so its last row is bit for
+    //  bit the row the host path samples from -- and only the pool of that row comes to the host)
+    const int rc = n_new == 1 ? ifa_model_decode_pool(model_, q.tokens.back(), q.processed, PoolK(q), &next, ids, vals, &cnt)
+                              : ifa_model_forward_pool(model_, q.tokens.data() + q.processed, n_new, q.processed, logits_dev_, PoolK(q), &next, ids, vals, &cnt);
+    if (rc != IFA_OK) { EngineSetError("%s step failed: %s", n_new == 1 ? "decode" : "forward", ifa_last_error()); return false; }
+    if (n_new == 1) sampled_fused_steps_++;
+    if (!Sampled(q)) item.next_tokens.push_back(OneToken(next));
+    else if (!SamplePool(q, ids, vals, std::min(cnt, PoolLen(q)), item)) return false;
+    if (lp) {
+        float lse = 0.0f; int got = 0;
+        if (ifa_model_pool_lse(model_, &lse, 1, &got) != IFA_OK || got != 1) { EngineSetError("pool lse: %s", ifa_last_error()); return false; }
+        if (!FillLogprobs(q, ids, vals, cnt, lse, item)) return false;
+    }
+    return true;
+}
+
+// one query's own step: the whole pending prompt, or one token outside a batch
+bool InferenceEngine::InferQuery(Query &q, InferenceResult &res)
+{
+    const int n_new = (int)q.tokens.size() - q.processed, V = spec_.hyper_params.vocab_size;
+    QueryInferenceResult item; item.query_id = q.id; item.prefix_len = q.processed;
+    const bool sampled = Sampled(q);
+    const QueryStepPlan plan = PlanQueryStep(multi_ != nullptr, config_.return_output_tensors, PoolRoute(q), sampled, n_new);
+    int next = -1;
+    if (plan.route == StepRoute::Multi) {                            // partition over several GPUs: every rank steps at once
+        if (!MultiStep(q, n_new, plan.logits_rows > 0, item, next)) return false;
+        if (sampled && !SampleRow(q, item.output_tensor.data() + (size_t)(n_new - 1) * V, item)) return false;
+        if (!config_.return_output_tensors) { item.output_tensor.clear(); item.output_rows = item.output_cols = 0; }
+    } else {
+        if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
+        if (plan.logits_rows > 0 && !EnsureLogitsRows((size_t)plan.logits_rows)) return false;
+        if (plan.route == StepRoute::DecodePool || plan.route == StepRoute::ForwardPool) {
+            if (!PoolStep(q, n_new, item)) return false;
+        } else if (plan.route == StepRoute::Decode) {                // fused graph-replayed step
+            if (ifa_model_decode(model_, q.tokens.back(), q.processed, 1, &next, nullptr) != IFA_OK) { EngineSetError("decode step failed: %s", ifa_last_error()); return false; }
+        } else if (ifa_model_forward(model_, q.tokens.data() + q.processed, n_new, q.processed, plan.logits_rows > 0 ? logits_dev_ : nullptr, &next) != IFA_OK) {
+            EngineSetError("forward step failed: %s", ifa_last_error()); return false;
+        }
+        if (plan.copy != LogitsCopy::None) {                         // every row for the caller, or the last one for the host's sampler
+            const bool every = plan.copy == LogitsCopy::AllRows;
+            const size_t rows = every ? (size_t)n_new : 1;
+            std::vector<uint16_t> last_row, &dst = every ? item.output_tensor : last_row;
+            dst.resize(rows * (size_t)V);
+            if (!LogitsToHost(dst.data(), (size_t)n_new - rows, rows)) return false;
+            if (every) { item.output_rows = n_new; item.output_cols = V; }
+            if (sampled && !SampleRow(q, dst.data() + (rows - 1) * (size_t)V, item)) return false;
+        }
+    }
+    if (item.next_tokens.empty()) item.next_tokens.push_back(OneToken(next));
+    q.processed = (int)q.tokens.size();
+    res.items.push_back(std::move(item));
+    return true;
+}
+
 bool InferenceEngine::Infer(InferenceResult &res)
 {
     res.items.clear(); res.perf_stat.time_map.clear();
     if (!model_) { EngineSetError("The engine is not initialized"); return false; }
     const auto t0 = std::chrono::steady_clock::now();
-    const int V = spec_.hyper_params.vocab_size;
-    const int max_ctx = spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
-    // dynamic batching: every query that advances by exactly one token joins ONE step -- the linear layers stream
-    // the weights once for all of them (ifa_model_decode_batch); prefills and single queries take the paths below
+    const int max_ctx = MaxContextLen();
     std::vector<Query *> batch;
-    for (auto &kv : queries_) {
-        Query &q = kv.second;
-        // (a partition with several layer groups steps its queries one by one: a batched step is one tensor-parallel group's)
-        const bool batchable = !multi_ || multi_->G == 1;
-        if (batchable && !q.ended && (int)q.tokens.size() < max_ctx && q.processed > 0 && (int)q.tokens.size() - q.processed == 1) batch.push_back(&q);
-    }
-    if ((int)batch.size() >= std::max(2, config_.dynamic_batching_min_queries)) {
-        const int n = (int)batch.size();
-        std::vector<int> toks((size_t)n), pos((size_t)n), slots((size_t)n), next((size_t)n, -1);
-        for (int r = 0; r < n; r++) { toks[(size_t)r] = batch[(size_t)r]->tokens.back(); pos[(size_t)r] = batch[(size_t)r]->processed; slots[(size_t)r] = batch[(size_t)r]->kv_slot; }
-        void *lg = nullptr;
-        bool any_sampled = false;
-        // rows whose candidates come from the device pool behind the step (device_sampling_pool): no logits row leaves the device
-        // for them; one pool length serves the launch (the longest wanted; a query reads its own prefix of the sorted pool)
-        std::vector<int> pool_rows; int pool_k = 0;
-        bool any_lp = false;
-        for (int r = 0; r < n; r++) {
-            Query *bq = batch[(size_t)r];
-            const bool smp = bq->strategy != SamplingStrategyId::Greedy || host_greedy_;
-            if (PoolRoute(*bq)) { pool_rows.push_back(r); pool_k = std::max(pool_k, PoolK(*bq)); any_lp = any_lp || bq->options.logprobs >= 0; }
-            else any_sampled = any_sampled || smp;
+    // (a partition with several layer groups steps its queries one by one: a batched step is one tensor-parallel group's)
+    if (LayerGroups() == 1)
+        for (auto &kv : queries_) {
+            Query &q = kv.second;
+            if (!q.ended && (int)q.tokens.size() < max_ctx && q.processed > 0 && (int)q.tokens.size() - q.processed == 1) batch.push_back(&q);
         }
-        // (a row that needs the host path brings the whole block over anyway)
-        if (any_sampled && !any_lp) { pool_rows.clear(); pool_k = 0; }
-        if (any_sampled && any_lp) {         // a logprobs row needs its pool and lse: the sampled rows next to it take their pools too
-            pool_rows.clear();
-            for (int r = 0; r < n; r++) {
-                Query *bq = batch[(size_t)r];
-                const bool smp = bq->strategy != SamplingStrategyId::Greedy || host_greedy_;
-                if (PoolRoute(*bq)) { pool_rows.push_back(r); continue; }
-                if (!smp) continue;
-                const int k = PoolLen(*bq);
-                if (k < 1 || k > IFA_POOL_MAX) { EngineSetError("query %d samples from %d candidates, more than a device pool holds; it cannot share a step with a logprobs query", bq->id, k); return false; }
-                pool_rows.push_back(r); pool_k = std::max(pool_k, k);
-            }
-            any_sampled = false;
-        }
-        std::vector<float> pool_lse;
-        std::vector<int> pool_ids, pool_counts; std::vector<uint16_t> pool_vals;
-        std::vector<uint16_t> all;
-        if (multi_) {
-            // Query batching over a tensor-parallel device group (the reference: query batching, inference_engine.cc:1054-1124,
-            // inside Infer_TensorParallelism, :1222-1296): every rank runs ONE batched step over the same queries -- merges
-            // over [n][dim], one distributed argmax per row (ifa_model_tp_decode_batch) -- and hands back its vocabulary shard
-            if (!MultiBatchStep(toks, pos, slots, next, config_.return_output_tensors || any_sampled, all)) return false;
-        } else {
-        if (config_.return_output_tensors || any_sampled) {
-            if ((size_t)n > logits_rows_) {
-                if (logits_dev_) ifa_free(logits_dev_);
-                logits_dev_ = nullptr; logits_rows_ = 0;
-                if (ifa_malloc(&logits_dev_, (size_t)n * V * 2) != IFA_OK) { EngineSetError("logits buffer: %s", ifa_last_error()); return false; }
-                logits_rows_ = (size_t)n;
-            }
-            lg = logits_dev_;
-        }
-        if (!pool_rows.empty()) {
-            const size_t ns = pool_rows.size();
-            pool_ids.resize(ns * (size_t)pool_k); pool_vals.resize(ns * (size_t)pool_k); pool_counts.resize(ns);
-            if (!SetPoolLse(any_lp)) return false;
-            if (ifa_model_decode_batch_pool(model_, n, toks.data(), pos.data(), slots.data(), next.data(), pool_k, pool_rows.data(), (int)ns,
-                                            pool_ids.data(), pool_vals.data(), pool_counts.data()) != IFA_OK) {
-                EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
-            }
-            if (any_lp) {
-                pool_lse.resize(ns); int got = 0;
-                if (ifa_model_pool_lse(model_, pool_lse.data(), (int)ns, &got) != IFA_OK || got != (int)ns) { EngineSetError("pool lse: %s", ifa_last_error()); return false; }
-            }
-            sampled_fused_steps_ += (long long)ns;
-        } else
-        if (ifa_model_decode_batch(model_, n, toks.data(), pos.data(), slots.data(), next.data(), lg) != IFA_OK) {
-            EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
-        }
-        if (lg) {
-            all.resize((size_t)n * V);
-            if (ifa_memcpy_d2h(all.data(), lg, all.size() * 2, ifa_model_stream(model_)) != IFA_OK || ifa_stream_sync(ifa_model_stream(model_)) != IFA_OK) {
-                EngineSetError("logits copy: %s", ifa_last_error()); return false;
-            }
-        }
-        }
-        for (int r = 0; r < n; r++) {
-            Query &q = *batch[(size_t)r];
-            QueryInferenceResult item; item.query_id = q.id; item.prefix_len = q.processed;
-            if (!all.empty() && config_.return_output_tensors) { item.output_rows = 1; item.output_cols = V; item.output_tensor.assign(all.begin() + (size_t)r * V, all.begin() + (size_t)(r + 1) * V); }
-            q.processed = (int)q.tokens.size();
-            IdWeight w; w.id = next[(size_t)r]; w.weight = 1.0f;
-            item.next_tokens.push_back(w);
-            const auto pr = std::find(pool_rows.begin(), pool_rows.end(), r);
-            if (pr != pool_rows.end()) {
-                const size_t j = (size_t)(pr - pool_rows.begin());
-                const int cnt = std::min(pool_counts[j], PoolLen(q));
-                const bool smp = q.strategy != SamplingStrategyId::Greedy || host_greedy_;      // (else: the device argmax already chose)
-                if (smp && !SamplePool(q, pool_ids.data() + j * (size_t)pool_k, pool_vals.data() + j * (size_t)pool_k, cnt, item)) return false;
-                if (q.options.logprobs >= 0 && !FillLogprobs(q, pool_ids.data() + j * (size_t)pool_k, pool_vals.data() + j * (size_t)pool_k,
-                                                             std::min(pool_counts[j], PoolK(q)), pool_lse[j], item)) return false;
-            } else
-            if ((q.strategy != SamplingStrategyId::Greedy || host_greedy_) && !SampleRow(q, all.data() + (size_t)r * V, item)) return false;
-            res.items.push_back(std::move(item));
-        }
-    }
+    if ((int)batch.size() >= std::max(2, config_.dynamic_batching_min_queries) && !InferBatch(batch, res)) return false;
     for (auto &kv : queries_) {
         Query &q = kv.second;
         if (q.ended) continue;
         if ((int)q.tokens.size() >= max_ctx) { q.ended = true; continue; }
-        const int n_new = (int)q.tokens.size() - q.processed;
-        if (n_new <= 0) continue;                                    // nothing committed since the last step
-        QueryInferenceResult item; item.query_id = q.id; item.prefix_len = q.processed;
-        int next = -1;
-        const bool sampled = q.strategy != SamplingStrategyId::Greedy || host_greedy_;
-        const bool want_tensor = config_.return_output_tensors || sampled;
-        if (multi_) {                                                // partition over several GPUs: every rank steps at once
-            if (!MultiStep(q, n_new, want_tensor, item, next)) return false;
-            if (sampled && !SampleRow(q, item.output_tensor.data() + (size_t)(n_new - 1) * V, item)) return false;
-            if (!config_.return_output_tensors) { item.output_tensor.clear(); item.output_rows = item.output_cols = 0; }
-            q.processed = (int)q.tokens.size();
-            if (item.next_tokens.empty()) { IdWeight w; w.id = next; w.weight = 1.0f; item.next_tokens.push_back(w); }
-            res.items.push_back(std::move(item));
-            continue;
-        }
-        if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
-        if (PoolRoute(q)) {                                          // the step ends in the candidate pool: nothing of size V leaves the device
-            const int k = PoolK(q);
-            const bool lp = q.options.logprobs >= 0;
-            if (!SetPoolLse(lp)) return false;
-            int ids[IFA_POOL_MAX], cnt = 0; uint16_t vals[IFA_POOL_MAX];
-            // (a prompt keeps today's forward step -- lm_head over all rows into the engine's logits buffer, so its last row is bit for
-            //  bit the row the host path samples from -- and only the pool of that row comes to the host)
-            if (n_new > 1 && (size_t)n_new > logits_rows_) {
-                if (logits_dev_) ifa_free(logits_dev_);
-                logits_dev_ = nullptr; logits_rows_ = 0;
-                if (ifa_malloc(&logits_dev_, (size_t)n_new * V * 2) != IFA_OK) { EngineSetError("logits buffer: %s", ifa_last_error()); return false; }
-                logits_rows_ = (size_t)n_new;
-            }
-            const int rc = n_new == 1 ? ifa_model_decode_pool(model_, q.tokens.back(), q.processed, k, &next, ids, vals, &cnt)
-                                      : ifa_model_forward_pool(model_, q.tokens.data() + q.processed, n_new, q.processed, logits_dev_, k, &next, ids, vals, &cnt);
-            if (rc != IFA_OK) { EngineSetError("%s step failed: %s", n_new == 1 ? "decode" : "forward", ifa_last_error()); return false; }
-            if (n_new == 1) sampled_fused_steps_++;
-            if (sampled && !SamplePool(q, ids, vals, std::min(cnt, PoolLen(q)), item)) return false;
-            if (!sampled) { IdWeight w; w.id = next; w.weight = 1.0f; item.next_tokens.push_back(w); }      // (the device argmax chose)
-            if (lp) {
-                float lse = 0.0f; int got = 0;
-                if (ifa_model_pool_lse(model_, &lse, 1, &got) != IFA_OK || got != 1) { EngineSetError("pool lse: %s", ifa_last_error()); return false; }
-                if (!FillLogprobs(q, ids, vals, cnt, lse, item)) return false;
-            }
-        } else
-        if (n_new == 1 && !want_tensor) {                            // decode: fused graph-replayed step
-            if (ifa_model_decode(model_, q.tokens.back(), q.processed, 1, &next, nullptr) != IFA_OK) {
-                EngineSetError("decode step failed: %s", ifa_last_error()); return false;
-            }
-        } else {
-            void *lg = nullptr;
-            if (want_tensor) {
-                if ((size_t)n_new > logits_rows_) {
-                    if (logits_dev_) ifa_free(logits_dev_);
-                    logits_dev_ = nullptr; logits_rows_ = 0;
-                    if (ifa_malloc(&logits_dev_, (size_t)n_new * V * 2) != IFA_OK) { EngineSetError("logits buffer: %s", ifa_last_error()); return false; }
-                    logits_rows_ = (size_t)n_new;
-                }
-                lg = logits_dev_;
-            }
-            if (ifa_model_forward(model_, q.tokens.data() + q.processed, n_new, q.processed, lg, &next) != IFA_OK) {
-                EngineSetError("forward step failed: %s", ifa_last_error()); return false;
-            }
-            std::vector<uint16_t> last_row;
-            if (config_.return_output_tensors) {
-                item.output_rows = n_new; item.output_cols = V;
-                item.output_tensor.resize((size_t)n_new * V);
-                if (ifa_memcpy_d2h(item.output_tensor.data(), lg, (size_t)n_new * V * 2, ifa_model_stream(model_)) != IFA_OK
-                    || ifa_stream_sync(ifa_model_stream(model_)) != IFA_OK) { EngineSetError("logits copy: %s", ifa_last_error()); return false; }
-            } else if (sampled) {                                    // sampling only: the last row is all the host needs
-                last_row.resize((size_t)V);
-                if (ifa_memcpy_d2h(last_row.data(), (const uint16_t *)lg + (size_t)(n_new - 1) * V, (size_t)V * 2, ifa_model_stream(model_)) != IFA_OK
-                    || ifa_stream_sync(ifa_model_stream(model_)) != IFA_OK) { EngineSetError("logits copy: %s", ifa_last_error()); return false; }
-            }
-            if (sampled) {
-                const uint16_t *row = config_.return_output_tensors ? item.output_tensor.data() + (size_t)(n_new - 1) * V : last_row.data();
-                if (!SampleRow(q, row, item)) return false;
-            }
-        }
-        q.processed = (int)q.tokens.size();
-        if (item.next_tokens.empty()) { IdWeight w; w.id = next; w.weight = 1.0f; item.next_tokens.push_back(w); }
-        res.items.push_back(std::move(item));
+        if ((int)q.tokens.size() - q.processed <= 0) continue;       // nothing committed since the last step (or the batch took it)
+        if (!InferQuery(q, res)) return false;
     }
     if (perf_phases_) {
         int keys[256]; float ms[256]; int n = 0;
@@ -900,71 +491,70 @@ bool InferenceEngine::CommitInferenceResult(const std::map<int, QueryNextToken> 
     return ok;
 }
 
+// ---------------------------------------------------------------------------------------------- Generate, GenerateLookup
+InferenceEngine::Query *InferenceEngine::FindQuery(int query_id)
+{
+    auto it = queries_.find(query_id);
+    if (!model_ || it == queries_.end()) { EngineSetError("Query %d does not exist", query_id); return nullptr; }
+    return &it->second;
+}
+
+// what Generate and GenerateLookup ask of their query: not ended, greedy on the device, and the whole request fits -- nothing is
+// touched unless it does (the device token ring holds 1024 steps per call)
+bool InferenceEngine::DeviceGreedyOk(const Query &q, int n_new, bool lookup)
+{
+    if (q.ended) { EngineSetError("Query %d has ended", q.id); return false; }
+    if (host_greedy_)
+        EngineSetError(lookup ? "GenerateLookup() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)"
+                              : "Generate() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size());
+    else if (q.strategy != SamplingStrategyId::Greedy)
+        EngineSetError(lookup ? "GenerateLookup() decodes greedily on the device; query %d uses strategy %d (use Infer / CommitInferenceResult)"
+                              : "Generate() decodes greedily on the device; query %d uses strategy %d (use Infer / CommitInferenceResult)", q.id, (int)q.strategy);
+    else if ((int)q.tokens.size() + n_new > MaxContextLen())
+        EngineSetError(lookup ? "GenerateLookup: %zu tokens + %d new tokens exceed max_context_len %d" : "Generate: %zu tokens + %d steps exceed max_context_len %d", q.tokens.size(), n_new, MaxContextLen());
+    else return true;
+    return false;
+}
+
+static float MsSince(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+
+// prefill whatever is pending; yields the first new token (nothing to do if only the last committed token is pending).  st: the
+// step and its time are added to the lookup statistics
+bool InferenceEngine::PrefillPending(Query &q, std::vector<int> &new_tokens, int &left, LookupStats *st)
+{
+    const int pending = (int)q.tokens.size() - q.processed;
+    if (pending <= 0) { EngineSetError("Query %d has no committed token to continue from", q.id); return false; }
+    if (pending == 1 && q.processed > 0) return true;
+    int next = -1;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (multi_) {
+        QueryInferenceResult item;
+        if (!MultiStep(q, pending, false, item, next)) return false;
+    } else if (ifa_model_forward(model_, q.tokens.data() + q.processed, pending, q.processed, nullptr, &next) != IFA_OK) {
+        EngineSetError("forward step failed: %s", ifa_last_error()); return false;
+    }
+    if (st) { st->gpu_ms += MsSince(t0); st->steps++; }
+    q.processed = (int)q.tokens.size();
+    q.tokens.push_back(next); new_tokens.push_back(next); left--;
+    return true;
+}
+
 bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_tokens, float *gpu_ms)
 {
     new_tokens.clear();
-    auto it = queries_.find(query_id);
-    if (!model_ || it == queries_.end()) { EngineSetError("Query %d does not exist", query_id); return false; }
-    Query &q = it->second;
-    if (n_steps <= 0) return true;
-    if (q.ended) { EngineSetError("Query %d has ended", query_id); return false; }
-    if (host_greedy_) { EngineSetError("Generate() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size()); return false; }
-    if (q.strategy != SamplingStrategyId::Greedy) { EngineSetError("Generate() decodes greedily on the device; query %d uses strategy %d (use Infer / CommitInferenceResult)", query_id, (int)q.strategy); return false; }
-    {   // nothing is touched unless the whole request fits (the device token ring holds 1024 steps per call)
-        const int max_ctx = spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
-        if ((int)q.tokens.size() + n_steps > max_ctx) { EngineSetError("Generate: %zu tokens + %d steps exceed max_context_len %d", q.tokens.size(), n_steps, max_ctx); return false; }
-    }
-    if (multi_) {
-        MultiGpu &M = *multi_;
-        const int R = (int)M.plans.size();
-        const int pending = (int)q.tokens.size() - q.processed;
-        if (pending <= 0) { EngineSetError("Query %d has no committed token to continue from", query_id); return false; }
-        int next = -1;
-        if (pending > 1 || q.processed == 0) {
-            QueryInferenceResult item;
-            if (!MultiStep(q, pending, false, item, next)) return false;
-            q.processed = (int)q.tokens.size();
-            q.tokens.push_back(next); new_tokens.push_back(next);
-            n_steps--;
-        }
-        float ms_total = 0;
-        while (n_steps > 0) {
-            const int k = std::min(n_steps, 1024);
-            std::vector<std::vector<int>> outs((size_t)R, std::vector<int>((size_t)k));
-            std::vector<float> ms((size_t)R, 0.0f);
-            const int first = q.tokens.back(), start = q.processed, slot = q.kv_slot;
-            if (!M.Run([&](int i) -> int {
-                    ifa_model *mm = M.plans[(size_t)i].model;
-                    int rc = ifa_model_select_kv(mm, slot);
-                    return rc ? rc : ifa_model_tp_decode(mm, &M.topo[(size_t)i], first, start, k, outs[(size_t)i].data(), &ms[(size_t)i]);
-                }, "decode")) return false;
-            for (int t : outs[(size_t)(R - 1)]) { q.tokens.push_back(t); new_tokens.push_back(t); }
-            q.processed = (int)q.tokens.size() - 1;
-            ms_total += *std::max_element(ms.begin(), ms.end());
-            n_steps -= k;
-        }
-        if (gpu_ms) *gpu_ms = ms_total;
-        return true;
-    }
-    if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
-    int next = -1;
-    const int pending = (int)q.tokens.size() - q.processed;
-    if (pending > 1 || q.processed == 0) {            // prefill whatever is pending; yields the first new token
-        if (ifa_model_forward(model_, q.tokens.data() + q.processed, pending, q.processed, nullptr, &next) != IFA_OK) {
-            EngineSetError("forward step failed: %s", ifa_last_error()); return false;
-        }
-        q.processed = (int)q.tokens.size();
-        q.tokens.push_back(next); new_tokens.push_back(next);
-        n_steps--;
-    } else if (pending == 0) { EngineSetError("Query %d has no committed token to continue from", query_id); return false; }
+    Query *qp = FindQuery(query_id);
+    if (!qp || n_steps <= 0) return qp != nullptr;
+    Query &q = *qp;
+    if (!DeviceGreedyOk(q, n_steps, false)) return false;
+    if (!multi_ && ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
+    if (!PrefillPending(q, new_tokens, n_steps, nullptr)) return false;
     float ms_total = 0;
     while (n_steps > 0) {                              // the device token ring holds 1024 steps per call
         const int k = std::min(n_steps, 1024);
         std::vector<int> out((size_t)k);
         float ms = 0;
-        if (ifa_model_decode(model_, q.tokens.back(), q.processed, k, out.data(), &ms) != IFA_OK) {
-            EngineSetError("decode failed: %s", ifa_last_error()); return false;
-        }
+        if (multi_) { if (!MultiDecode(q, k, out.data(), &ms)) return false; }
+        else if (ifa_model_decode(model_, q.tokens.back(), q.processed, k, out.data(), &ms) != IFA_OK) { EngineSetError("decode failed: %s", ifa_last_error()); return false; }
         ms_total += ms;
         for (int t : out) { q.tokens.push_back(t); new_tokens.push_back(t); }
         q.processed = (int)q.tokens.size() - 1;
@@ -980,32 +570,17 @@ bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vect
     new_tokens.clear();
     LookupStats st;
     if (stats) *stats = st;
-    auto it = queries_.find(query_id);
-    if (!model_ || it == queries_.end()) { EngineSetError("Query %d does not exist", query_id); return false; }
+    Query *qp = FindQuery(query_id);
+    if (!qp) return false;
     if (multi_) { EngineSetError("GenerateLookup: lookup decoding runs on a single-device engine (this one has %d partition ranks)", PartitionRanks()); return false; }
     if (config_.return_output_tensors) { EngineSetError("GenerateLookup: lookup decoding is off under return_output_tensors = true (a draft step has several logits rows per step)"); return false; }
-    Query &q = it->second;
+    Query &q = *qp;
     if (max_new_tokens <= 0) return true;
-    if (q.ended) { EngineSetError("Query %d has ended", query_id); return false; }
-    if (host_greedy_) { EngineSetError("GenerateLookup() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size()); return false; }
-    if (q.strategy != SamplingStrategyId::Greedy) { EngineSetError("GenerateLookup() decodes greedily on the device; query %d uses strategy %d (use Infer / CommitInferenceResult)", query_id, (int)q.strategy); return false; }
-    const int max_ctx = spec_.max_context_len > 0 ? spec_.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
-    if ((int)q.tokens.size() + max_new_tokens > max_ctx) { EngineSetError("GenerateLookup: %zu tokens + %d new tokens exceed max_context_len %d", q.tokens.size(), max_new_tokens, max_ctx); return false; }
+    if (!DeviceGreedyOk(q, max_new_tokens, true)) return false;
     if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
-    const auto ms_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    const int max_ctx = MaxContextLen();
     int left = max_new_tokens;
-    const int pending = (int)q.tokens.size() - q.processed;
-    if (pending > 1 || q.processed == 0) {            // prefill whatever is pending; yields the first new token
-        int next = -1;
-        const auto t0 = std::chrono::steady_clock::now();
-        if (ifa_model_forward(model_, q.tokens.data() + q.processed, pending, q.processed, nullptr, &next) != IFA_OK) {
-            EngineSetError("forward step failed: %s", ifa_last_error()); return false;
-        }
-        st.gpu_ms += ms_since(t0); st.steps++;
-        q.processed = (int)q.tokens.size();
-        q.tokens.push_back(next); new_tokens.push_back(next);
-        left--;
-    } else if (pending == 0) { EngineSetError("Query %d has no committed token to continue from", query_id); return false; }
+    if (!PrefillPending(q, new_tokens, left, &st)) return false;
     const int *pred = prediction && !prediction->empty() ? prediction->data() : nullptr;
     const int n_pred = pred ? (int)prediction->size() : 0;
     int row[8], next[8];
@@ -1029,7 +604,7 @@ bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vect
         row[0] = q.tokens.back();
         const auto t0 = std::chrono::steady_clock::now();
         if (ifa_model_decode_draft(model_, m + 1, row, pos0, next, nullptr) != IFA_OK) { EngineSetError("draft step failed: %s", ifa_last_error()); if (stats) *stats = st; return false; }
-        st.gpu_ms += ms_since(t0);
+        st.gpu_ms += MsSince(t0);
         int a = 0;
         while (a < m && next[a] == row[a + 1]) a++;
         st.draft_steps++; st.drafted += m; st.accepted += a;

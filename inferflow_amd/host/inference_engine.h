@@ -25,6 +25,8 @@ struct ifa_comm;
 
 namespace inferflow_amd {
 
+struct BatchStepPlan;               // step_plan.h
+
 struct ModelHyperParams {          // ModelHyperParams, model.h:24-70
     int vocab_size = 0, output_vocab_size = 0;
     int embd_dims = 0, hidden_dim = 0;
@@ -269,6 +271,16 @@ private:
         JavaRandom rng;
         SamplingState sampling_state;   // Mirostat's mu, the FSD n-gram model, the EOS bypass count
     };
+    // ---- Infer: the route of every step is planned in pure code (step_plan.h); these run the plan
+    struct BatchPools { std::vector<int> ids, counts; std::vector<uint16_t> vals; std::vector<float> lse; };     // [pool_rows][pool_k]
+    bool InferBatch(const std::vector<Query *> &batch, InferenceResult &res);       // the queries that advance by one token, in ONE step
+    bool BatchStep(const std::vector<int> &toks, const std::vector<int> &pos, const std::vector<int> &slots, std::vector<int> &next,
+                   const BatchStepPlan &plan, BatchPools &pools, std::vector<uint16_t> &all);
+    bool InferQuery(Query &q, InferenceResult &res);                                // one query's own step
+    bool PoolStep(Query &q, int n_new, QueryInferenceResult &item);
+    bool Sampled(const Query &q) const { return q.strategy != SamplingStrategyId::Greedy || host_greedy_; }   // its token is chosen on the host
+    bool EnsureLogitsRows(size_t n);                                                // logits_dev_ holds [n][vocab] halfs
+    bool LogitsToHost(uint16_t *dst, size_t row0, size_t rows);
     bool SampleRow(Query &q, const uint16_t *logits_row, QueryInferenceResult &item);
     // the same from a device-built candidate pool (ifa_topk_pool: count entries of ids / F16 bits, best first)
     bool SamplePool(Query &q, const int *ids, const uint16_t *vals, int count, QueryInferenceResult &item);
@@ -277,14 +289,23 @@ private:
     int PoolK(const Query &q) const;            // entries asked of the device: the sampler's pool length, or more for logprobs
     bool SetPoolLse(bool on);
     bool FillLogprobs(const Query &q, const int *ids, const uint16_t *vals, int count, float lse, QueryInferenceResult &item);
+    // ---- Generate / GenerateLookup
+    Query *FindQuery(int query_id);
+    bool DeviceGreedyOk(const Query &q, int n_new, bool lookup);
+    bool PrefillPending(Query &q, std::vector<int> &new_tokens, int &left, LookupStats *st);
     // ---- multi-GPU partitions (devices = 0&1 | 0;1 | 0&1;2&3): one worker and one host thread per GPU, like the
-    // reference's Infer_TensorParallelism / Infer_Std over GpuInferenceWorker threads (inference_engine.cc:1161-1296)
+    // reference's Infer_TensorParallelism / Infer_Std over GpuInferenceWorker threads (inference_engine.cc:1161-1296).
+    // MultiGpu and everything that looks inside it: inference_engine_multi.cc
     struct MultiGpu;
     MultiGpu *multi_ = nullptr;
     bool InitMulti(const std::vector<std::vector<int>> &groups);
+    void FreeMulti();
+    int LayerGroups() const;                    // device groups holding consecutive layer ranges (1: single device, or tensor parallel only)
+    std::vector<ifa_model *> Workers() const;   // every rank's worker; the one worker of a single-device engine
     bool MultiBatchStep(const std::vector<int> &toks, const std::vector<int> &pos, const std::vector<int> &slots, std::vector<int> &next,
                         bool want_tensor, std::vector<uint16_t> &all);
     bool MultiStep(Query &q, int n_new, bool want_tensor, QueryInferenceResult &item, int &next);
+    bool MultiDecode(const Query &q, int k, int *out, float *gpu_ms);
     InferenceConfig config_;
     ModelSpec spec_;
     ifa_model *model_ = nullptr;
@@ -315,6 +336,11 @@ private:
 // error text of the last failed call on this thread (the reference logs through LogError)
 const char *EngineLastError();
 void EngineSetError(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+
+// the lookup_* settings are in range (engine_config.cc; LoadConfig and Init both ask)
+bool LookupConfigOk(const InferenceConfig &c);
+// device -> host copy on the worker's stream, then wait for it; an IFA_* code
+int CopyToHostSync(ifa_model *m, void *dst, const void *src, size_t bytes);
 
 // model loading (model_loader.cc)
 bool LoadModelSpecJson(ModelSpec &spec, const std::string &path);

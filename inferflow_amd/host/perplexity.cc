@@ -27,7 +27,7 @@ bool ComputePerplexity(InferenceEngine &engine, const std::vector<int> &tokens, 
     if (engine.QueryCount() != 0) { EngineSetError("perplexity: the engine has active queries"); return false; }
     const ModelSpec &spec = engine.model_spec();
     const int V = spec.hyper_params.vocab_size;
-    const int max_ctx = spec.max_context_len > 0 ? spec.max_context_len : ModelSpec::DEFAULT_MAX_CONTEXT_LEN;
+    const int max_ctx = engine.MaxContextLen();
     if (max_length >= max_ctx) { EngineSetError("perplexity: max_length %d does not fit max_context_len %d", max_length, max_ctx); return false; }
     for (int t : tokens)
         if (t < 0 || t >= V) { EngineSetError("perplexity: token id %d is out of range", t); return false; }

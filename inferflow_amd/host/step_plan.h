@@ -1,0 +1,48 @@
+// step_plan.h -- which worker call a step of InferenceEngine::Infer takes and what it brings to the host, as pure host functions: no
+// device calls, nothing of InferenceEngine.  The engine fills in the facts (PoolRoute, PoolLen, PoolK read the query and the config)
+// and acts on the plan; the C ABI exposes both for tests (ifa_step_plan_query, ifa_step_plan_batch).
+#pragma once
+#include <vector>
+
+namespace inferflow_amd {
+
+enum class StepRoute { Multi = 0, DecodePool = 1, ForwardPool = 2, Decode = 3, Forward = 4 };
+enum class LogitsCopy { None = 0, AllRows = 1, LastRow = 2 };
+
+struct QueryStepPlan {
+    StepRoute route = StepRoute::Forward;
+    int logits_rows = 0;                    // rows the step's logits buffer must hold (0: the step writes no logits)
+    LogitsCopy copy = LogitsCopy::None;     // what of them comes to the host
+};
+
+// One query's step of n_new >= 1 tokens.  pool_route: its candidates come from the device pool; sampled: its token is drawn on the host.
+//  1. multi:                          Multi;       the ranks' shards of all n_new rows come over iff return_output_tensors || sampled
+//  2. pool_route, n_new == 1:         DecodePool;  no logits
+//  3. pool_route, n_new > 1:          ForwardPool; n_new rows stay on the device (the pool is built from the last one)
+//  4. n_new == 1, no tensors, greedy: Decode;      no logits
+//  5. anything else:                  Forward;     n_new rows iff return_output_tensors || sampled; AllRows for the tensors, else LastRow
+QueryStepPlan PlanQueryStep(bool multi, bool return_output_tensors, bool pool_route, bool sampled, int n_new);
+
+struct BatchRow {
+    bool pool_route = false, sampled = false;
+    int pool_len = 0, pool_k = 0;           // the sampler's pool length; the entries asked of the device (more for logprobs)
+    bool wants_logprobs = false;
+};
+
+struct BatchStepPlan {
+    std::vector<int> pool_rows;             // rows whose candidate pool is built behind the step, ascending
+    int pool_k = 0;                         // one pool length serves the launch: the longest wanted (a row reads its own prefix)
+    bool with_lse = false;                  // the pools come with their rows' log-sum-exp (a logprobs row is among them)
+    bool want_logits = false;               // the [n][vocab] block comes to the host
+    int error_row = -1;                     // >= 0: this row cannot share the step (rule 4); nothing else of the plan holds
+};
+
+// One batched decode step.  A row that is sampled and not on the pool route is "host-sampled": it needs its logits row.
+//  1. pool-route rows join pool_rows; pool_k = the largest pool_k among them; with_lse: one of them wants logprobs;
+//  2. a host-sampled row and no logprobs row: the block comes over anyway, so no pools at all (pool_rows empty, pool_k 0);
+//  3. a host-sampled row next to a logprobs row (which needs its pool and lse): every host-sampled row takes a pool of its pool_len
+//     too -- 1 <= pool_len <= IFA_POOL_MAX, else error_row -- and no row is host-sampled any more;
+//  4. want_logits = return_output_tensors || a host-sampled row is left.
+BatchStepPlan PlanBatchStep(bool return_output_tensors, const std::vector<BatchRow> &rows);
+
+} // namespace inferflow_amd
