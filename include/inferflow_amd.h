@@ -235,6 +235,30 @@ size_t ifa_logsumexp_workspace(size_t rows, size_t n);
 int ifa_logsumexp_rows(const void *logits_f16, size_t row_stride, const int *row_idx_dev, size_t rows, size_t n,
                        const int *targets_dev, float *lse_out_dev, float *target_logit_out_dev, void *workspace_dev, ifa_stream stream);
 
+/* ---- logit processors (csrc/ifa_logit_adjust.hip): repetition / frequency / presence penalties and logit_bias on F16 logits rows.
+ * State per slot (one slot per query), dense over the n ids of the vocabulary, all in device memory owned by the caller:
+ *   state_dev [slots][n] u32: bit 31 = the id occurs in the prompt, bits 0..30 = how many times it has been generated;
+ *   bias_dev [slots][n] f32 (0: none, -inf bans the id); params_dev [slots][3] f32 = {rep, freq, pres}.
+ * ifa_logit_adjust_rows: out row r (compact, stride n) from input row (row_idx_dev ? row_idx_dev[r] : r) of logits_f16
+ * [.][row_stride] with the state of slot q = state_slot_dev[r].  Per id, fp32, every operation rounded on its own, in this order:
+ *   x = float(in[id]); w = state[q][id]; c = w & 0x7fffffff;
+ *   if (w != 0 && rep != 1) x = x > 0 ? x / rep : x * rep;          (the HF repetition rule: prompt + generated ids)
+ *   x = x - (freq * float(c) + (c > 0 ? pres : 0));                  (the OpenAI rule: generated ids only)
+ *   x = x + bias[q][id];
+ *   bias[q][id] == -inf: -inf; else clamp to +-65504, round to F16 (RNE); a NaN is written as 0x7E00.
+ * (Taken literally: an infinite input leaves as +-65504; -0.0 under neutral parameters leaves as +0.0.)  Pure, out of place,
+ * enqueue-only, capturable; grid (ceil(n / 2048), rows), 16-byte accesses for a row whose four bases are 16-byte aligned, else id by id; no
+ * atomics, run-to-run identical.  Slots in state_slot_dev must lie inside the three arrays. */
+int ifa_logit_adjust_rows(const void *logits_f16, size_t row_stride, const int *row_idx_dev, const int *state_slot_dev, size_t rows, size_t n,
+                          const unsigned *state_dev, const float *bias_dev, const float *params_dev, void *out_f16_dev, ifa_stream stream);
+/* clears the state and bias rows of `slot`, sets bit 31 for every prompt id (duplicates welcome), scatters the n_bias
+ * (id, value) pairs into the bias row and writes {rep, freq, pres}; ids outside 0..n-1 are skipped.  Two memsets + one launch. */
+int ifa_logit_state_reset(int slot, const int *prompt_tokens_dev, size_t n_prompt, float rep, float freq, float pres, const int *bias_ids_dev,
+                          const float *bias_vals_dev, size_t n_bias, size_t n, unsigned *state_dev, float *bias_dev, float *params_dev, ifa_stream stream);
+/* state[slots_dev[i]][tokens_dev[i]] += 1 for the n_pairs pairs in one launch (integer atomics: repeated pairs add up, the
+ * result does not depend on the order); pairs outside [0, n_slots) x [0, n) are skipped */
+int ifa_logit_state_add(const int *slots_dev, const int *tokens_dev, size_t n_pairs, size_t n, size_t n_slots, unsigned *state_dev, ifa_stream stream);
+
 /* ======================================================================== */
 /* Per-device decode worker: counterpart of GpuInferenceWorker                */
 /* (src/transformer/inference_worker.h:23-62, inference_worker.cc:234-340)    */
@@ -393,6 +417,25 @@ int ifa_model_forward_pool(ifa_model *m, const int *tokens_host, int n_tokens, i
  * steps) values, log p(pool id) = float(pool value) - lse.  With the option off the steps enqueue exactly what they did before and
  * *n_out is 0.  Changing the option keeps the captured graphs. */
 int ifa_model_pool_lse(ifa_model *m, float *lse_host, int cap, int *n_out);
+/* ---- logit processors behind the pool steps (csrc/ifa_logit_adjust.hip; state per KV slot, allocated on first use).
+ * ifa_model_logit_state_reset: the state of the query in kv_slot -- clears it, marks the n_prompt prompt ids, stores the penalties
+ * and the n_bias (id, value) logit_bias pairs (host pointers).  IFA_ERR_ARG with a message: rep not finite or <= 0, freq / pres
+ * not finite, n_bias > IFA_LOGIT_BIAS_MAX, a bias id outside the vocabulary or given twice, a bias value that is neither finite
+ * nor -inf, a prompt id outside the vocabulary, a slot outside ifa_model_kv_slots.  Synchronises the worker's stream.
+ * ifa_model_logit_state_add: one more generated occurrence for each of the n (kv slot, token) pairs (n <= 1024), enqueued on the
+ * worker's stream through pinned staging -- no synchronisation (a ring of 8 staging blocks; only a 9th call without any
+ * synchronisation of the stream in between would wait for the first).
+ * ifa_model_pool_adjust: arms the NEXT pool step (ifa_model_decode_pool / _decode_batch_pool / _forward_pool): entry j is the
+ * state slot of pooled row j (1 entry for the single-query steps), -1 for a row that stays raw.  Armed rows pass through
+ * ifa_logit_adjust_rows into the worker's buffer "logits_adj" ([pooled rows][vocab], row j at j * vocab) and the pool and the
+ * log-sum-exp read that; the exclusion mask still applies; the "logits" buffer stays raw.  The arm is consumed by that step
+ * whether it succeeds or fails; a step whose n_sel differs from n_sel here fails with IFA_ERR_ARG.  With nothing armed a step
+ * enqueues exactly what it did before.  All three: IFA_ERR_STATE on a partitioned worker (tp_size > 1). */
+#define IFA_LOGIT_BIAS_MAX 1024
+int ifa_model_logit_state_reset(ifa_model *m, int kv_slot, const int *prompt_host, int n_prompt, float rep, float freq, float pres,
+                                const int *bias_ids_host, const float *bias_vals_host, int n_bias);
+int ifa_model_logit_state_add(ifa_model *m, int n, const int *kv_slots_host, const int *tokens_host);
+int ifa_model_pool_adjust(ifa_model *m, int n_sel, const int *state_slots_host);
 /* A scoring prompt: ifa_model_forward(tokens, n_tokens, prefix_len) with the lm_head over ALL rows into the worker's own logits
  * buffer -- bit for bit the rows ifa_model_forward(..., logits_out_dev) delivers, on the same route (one pass, the two passes of a
  * 34..48-token prompt, options exact_order and perf_stat) -- then ifa_logsumexp_rows over them: lse_host[i] and
@@ -402,7 +445,7 @@ int ifa_model_pool_lse(ifa_model *m, float *lse_host, int cap, int *n_out);
  * workers (tp_size > 1, or a topology) return IFA_ERR_STATE. */
 int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, const int *targets_host,
                             float *lse_host, float *target_logit_host, int *next_token_host);
-/* debugging taps: "logits", "hidden", "kcache", "vcache" (device pointers) */
+/* debugging taps: "logits", "logits_adj" (the rows the last armed pool step adjusted; null before the first), "hidden", "kcache", "vcache" (device pointers) */
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes);
 void *ifa_model_stream(ifa_model *m);
 /* run the worker on a caller-owned stream (e.g. the one the caller's RCCL collectives are ordered on) */

@@ -33,6 +33,27 @@ int ifa_engine_add_query_ex(ifa_engine *e, const int *tokens, int n_tokens, int 
  * tokens, rules and draws are those of the same query without logprobs.  Limits: a multi-device engine, or
  * return_output_tensors = true, returns -1 with a message; any other value of logprobs too. */
 int ifa_engine_add_query_lp(ifa_engine *e, const int *tokens, int n_tokens, int strategy_id, int random_seed, float temperature, int logprobs);
+/* AddQuery with every query option, as a struct that can grow: struct_size = sizeof(ifa_query_options) of the CALLER's header
+ * (fields behind it keep their defaults; a size below the first field's end is refused).  strategy_id / random_seed / temperature /
+ * logprobs as above.  Logit processors (csrc/ifa_logit_adjust.hip), applied on the device to the step's logits row in front of the
+ * candidate pool and the log-sum-exp, in this order: repetition_penalty (> 0; 1 = off; the HF rule over prompt + generated ids:
+ * x > 0 ? x / r : x * r), then x - (frequency_penalty * count + (count > 0 ? presence_penalty : 0)) over the generated ids (the
+ * OpenAI rule; 0 = off), then + logit_bias: n_logit_bias (<= 1024) pairs (logit_bias_ids[i], logit_bias_values[i]), ids distinct and
+ * inside the vocabulary, values finite or -inf (-inf bans the id).  A query with any of them non-neutral always takes the device pool
+ * route (like a logprobs query); a greedy one receives the pool's best entry; its logprobs are those of the processed distribution
+ * at temperature 1.  -1 with a message: a multi-device engine, return_output_tensors = true, more sampling candidates than a device
+ * pool holds, a value outside the rules above.  ifa_engine_generate / _generate_lookup refuse such a query. */
+typedef struct ifa_query_options {
+    size_t struct_size;
+    int strategy_id, random_seed;
+    float temperature;
+    int logprobs;                  /* -1 off */
+    float repetition_penalty, presence_penalty, frequency_penalty;      /* 1, 0, 0 */
+    int n_logit_bias;
+    const int *logit_bias_ids;
+    const float *logit_bias_values;
+} ifa_query_options;
+int ifa_engine_add_query_opt(ifa_engine *e, const int *tokens, int n_tokens, const ifa_query_options *options);
 /* logprobs of the query's most recent step (after ifa_engine_infer): *chosen = log p of the token the step chose; ids / logprobs
  * [min(cap, *n)] = the *n most probable tokens, best first.  1 ok, 0 failure (unknown id, or a query without logprobs). */
 int ifa_engine_last_logprobs(ifa_engine *e, int query_id, float *chosen, int *ids, float *logprobs, int cap, int *n);
@@ -121,7 +142,9 @@ double ifa_perplexity_token_nll(const uint16_t *logits_f16, int vocab, int token
  * single-device engine with return_output_tensors = false; elsewhere the key is accepted and this stays 0), "prefix_cache_hits"
  * (queries that started behind reused rows), "prefix_cache_tokens" (the rows they reused in all), "prefix_cache_copies" (the hits
  * whose rows sat in a busy slot and were copied on the device, ifa_model_kv_copy), "lookup_decoding" (0 / 1: ifa_engine_generate_lookup
- * is available -- a single-device engine with return_output_tensors = false); -1 if unknown */
+ * is available -- a single-device engine with return_output_tensors = false), "logit_processors" (0 / 1: ifa_engine_add_query_opt accepts
+ * penalties and a logit_bias -- the same condition), "processed_steps" (steps, one per query per step, whose pool was built from a
+ * row the logit processors had rewritten); -1 if unknown */
 int ifa_engine_model_info(ifa_engine *e, const char *key);
 /* prompt prefix cache: the leading prompt tokens of query_id whose K/V rows AddQuery found in a slot (the query's first Infer runs
  * only the rest; QueryInferenceResult::prefix_len reports the same number); 0 without a hit or with the cache off, -1 unknown id */
@@ -181,7 +204,9 @@ int ifa_service_selftest_loop(int max_ctx, int max_queries, int fail_at_infer_ca
 /* host-only: one request body through the parser and the loop over the same loopback engine (which answers a query with logprobs
  * by a fixed table: candidate j of a step is (next + j) % 1000 with log p = -0.25 - j): writes {ok, ret_code, chunks: [the streamed
  * payloads], final: the final message} with time_cost zeroed.  The body's fields are the service's: prompt_token_ids, max_output_len /
- * max_tokens, is_streaming_mode / stream, "logprobs": true, "top_logprobs": n (0..20) ... */
+ * max_tokens, is_streaming_mode / stream, "logprobs": true, "top_logprobs": n (0..20), "repetition_penalty" (> 0), "presence_penalty" /
+ * "frequency_penalty" (-2..2), "logit_bias": {"<id>": value in -100..100} (at most 300 entries) ... -- the loopback engine has no
+ * logit processors: a request with them is answered "error.unsupported" */
 int ifa_service_selftest_request(const char *body, int is_openai_mode, int max_ctx, char *out_json, size_t cap);
 
 #ifdef __cplusplus

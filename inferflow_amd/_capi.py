@@ -96,6 +96,9 @@ SIGNATURES = {
     "ifa_topk_pool": (_i, [_vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "ifa_logsumexp_workspace": (_sz, [_sz, _sz]),
     "ifa_logsumexp_rows": (_i, [_vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_logit_adjust_rows": (_i, [_vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_logit_state_reset": (_i, [_i, _vp, _sz, _f, _f, _f, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "ifa_logit_state_add": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "ifa_model_create": (_i, [_vp, C.POINTER(_vp)]),
     "ifa_model_destroy": (_i, [_vp]),
     "ifa_model_set_tensor": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _sz]),
@@ -120,6 +123,9 @@ SIGNATURES = {
     "ifa_model_decode_batch_pool": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "ifa_model_forward_pool": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_pool_lse": (_i, [_vp, _vp, _i, _vp]),
+    "ifa_model_logit_state_reset": (_i, [_vp, _i, _vp, _i, _f, _f, _f, _vp, _vp, _i]),
+    "ifa_model_logit_state_add": (_i, [_vp, _i, _vp, _vp]),
+    "ifa_model_pool_adjust": (_i, [_vp, _i, _vp]),
     "ifa_model_forward_score": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_get_buffer": (_i, [_vp, C.c_char_p, _i, C.POINTER(_vp), C.POINTER(_sz)]),
     "ifa_model_stream": (_vp, [_vp]),
@@ -172,6 +178,7 @@ ENGINE_SIGNATURES = {
     "ifa_engine_add_query": (_i, [_vp, _ip, _i]),
     "ifa_engine_add_query_ex": (_i, [_vp, _ip, _i, _i, _i, _f]),
     "ifa_engine_add_query_lp": (_i, [_vp, _ip, _i, _i, _i, _f, _i]),
+    "ifa_engine_add_query_opt": (_i, [_vp, _ip, _i, _vp]),
     "ifa_engine_last_logprobs": (_i, [_vp, _i, C.POINTER(_f), _ip, C.POINTER(_f), _i, _ip]),
     "ifa_engine_score": (_i, [_vp, _ip, _i, C.POINTER(_f)]),
     "ifa_engine_strategy_id": (_i, [_vp, C.c_char_p]),
@@ -205,6 +212,14 @@ ENGINE_SIGNATURES = {
     "ifa_partition_slice": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _sz, _sz, C.POINTER(_sz)]),
     "ifa_partition_split_layers": (_i, [_i, _i, _ip, _i]),
 }
+
+
+class QueryOptions(C.Structure):
+    """ifa_query_options (include/inferflow_engine.h); struct_size is filled in by InferenceEngine.add_query"""
+    _fields_ = [("struct_size", C.c_size_t), ("strategy_id", C.c_int), ("random_seed", C.c_int), ("temperature", C.c_float),
+                ("logprobs", C.c_int), ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float),
+                ("frequency_penalty", C.c_float), ("n_logit_bias", C.c_int), ("logit_bias_ids", C.POINTER(C.c_int)),
+                ("logit_bias_values", C.POINTER(C.c_float))]
 
 
 class ModelConfig(C.Structure):

@@ -605,6 +605,7 @@ int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr,
     const ifa_model_config &c = m->cfg;
     size_t b = 0; void *p = nullptr;
     if (!strcmp(name, "logits")) { p = m->logits; b = (size_t)c.vocab * 2; }
+    else if (!strcmp(name, "logits_adj")) { p = m->la_adj; b = m->la_adj_rows * (size_t)c.vocab * 2; }
     else if (!strcmp(name, "tp_logits")) { p = m->tp_logits; b = m->tp_logits ? m->g[T_LM_HEAD].rows * 2 : 0; }
     else if (!strcmp(name, "trace")) { p = m->trace; b = m->trace ? sizeof(long long) * 2048 * 8 : 0; }
     else if (!strcmp(name, "hidden")) { p = m->xn; b = (size_t)c.dim * 2; }

@@ -204,10 +204,22 @@ struct ifa_model {
         int chunk0 = 0; bool last_chunk = true;      // batched step taken as several steps: first row / last step of this one
         int done = 0;                          // rows whose pool has been enqueued
         bool lse = false;                      // option pool_lse at arming: the rows' log-sum-exp ride in the block
+        std::vector<int> adj;                  // logit processors (ifa_model_pool_adjust): [n_sel] state slot of pooled row j, -1 raw; empty: none
     } pool;
     unsigned *pool_excl = nullptr;             // device bitmask of ids the pool never offers (null: none)
     void *pool_dev = nullptr, *pool_pin = nullptr; size_t pool_bytes = 0;      // result block, device / pinned
     int *pool_idx_dev = nullptr, *pool_idx_pin = nullptr; size_t pool_idx_cap = 0;
+    // Logit processors (ifa_logit_adjust.hip): per KV slot the u32 state row, the f32 bias row and {rep, freq, pres}, allocated for
+    // la_slots slots on the first ifa_model_logit_state_reset (regrown, contents kept, when ifa_model_kv_slots has added slots).
+    // pool_adj_next: what ifa_model_pool_adjust armed for the next pool step (moved into pool.adj by pool_arm).  la_adj: the adjusted
+    // rows of the last armed step, [la_adj_rows][vocab].  la_pin / la_stage: LA_RING staging blocks of 2 * RING ints (slots | tokens)
+    // for ifa_model_logit_state_add, block i guarded by la_ev[i]; reset's prompt / bias staging is la_reset_pin / la_reset_dev.
+    static constexpr int LA_RING = 8;
+    unsigned *la_state = nullptr; float *la_bias = nullptr, *la_params = nullptr; size_t la_slots = 0;
+    half_t *la_adj = nullptr; size_t la_adj_rows = 0;
+    std::vector<int> pool_adj_next;
+    int *la_pin = nullptr, *la_stage = nullptr; hipEvent_t la_ev[LA_RING] = {}; bool la_ev_used[LA_RING] = {}; unsigned la_calls = 0;
+    int *la_reset_pin = nullptr, *la_reset_dev = nullptr; size_t la_reset_cap = 0;
     // option pool_lse = 1: the pool steps also deliver the log-sum-exp of every pooled row (csrc/ifa_logprob.hip; log p = value - lse).
     // The block then reads counts [n_sel] | lse [n_sel] | ids | F16 bits, still one copy; ifa_model_pool_lse hands out the last step's.
     int opt_pool_lse = 0;
@@ -378,6 +390,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
 // block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.
 int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
 void pool_free(ifa_model *m);
+void logit_adjust_free(ifa_model *m);      // (called by pool_free)
 // ---- ifa_engine_score.hip
 static constexpr size_t LSE_PART_FLOATS = 256;      // rows * splits <= 128 pairs whatever the row count (ifa_logprob.hip, lse_splits)
 int lse_part_reserve(ifa_model *m);

@@ -45,10 +45,22 @@ class InferenceEngine:
         except Exception:
             pass
 
-    def add_query(self, tokens, strategy=None, seed=0, temperature=1.0, logprobs=-1):
+    def add_query(self, tokens, strategy=None, seed=0, temperature=1.0, logprobs=-1, repetition_penalty=1.0, presence_penalty=0.0,
+                  frequency_penalty=0.0, logit_bias=None):
         """strategy: None (the model's default) or a name / SamplingStrategyId ("sample.top_p", "greedy", 1 ...).
-        logprobs: -1 off; 0: the chosen token's log-probability; 1..20: also the n most probable tokens (last_logprobs)."""
+        logprobs: -1 off; 0: the chosen token's log-probability; 1..20: also the n most probable tokens (last_logprobs).
+        repetition_penalty (HF rule, prompt + generated ids), presence_penalty / frequency_penalty (OpenAI rule, generated ids),
+        logit_bias ({token id: value}, -inf bans the id): logit processors applied on the device in front of the candidate pool
+        (include/inferflow_engine.h, ifa_engine_add_query_opt); a query with any of them takes the device pool route."""
         arr = (C.c_int * len(tokens))(*[int(t) for t in tokens])
+        if repetition_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0 or logit_bias:
+            sid = 0 if strategy is None else (strategy if isinstance(strategy, int) else self.strategy_id(strategy))
+            bias = sorted((logit_bias or {}).items())
+            ids = (C.c_int * max(1, len(bias)))(*[int(k) for k, _ in bias])
+            vals = (C.c_float * max(1, len(bias)))(*[float(v) for _, v in bias])
+            opt = _capi.QueryOptions(C.sizeof(_capi.QueryOptions), int(sid), int(seed), float(temperature), int(logprobs), float(repetition_penalty),
+                                     float(presence_penalty), float(frequency_penalty), len(bias), ids, vals)
+            return _capi.lib().ifa_engine_add_query_opt(self._h, arr, len(tokens), C.byref(opt))
         if logprobs != -1:
             sid = 0 if strategy is None else (strategy if isinstance(strategy, int) else self.strategy_id(strategy))
             return _capi.lib().ifa_engine_add_query_lp(self._h, arr, len(tokens), int(sid), int(seed), float(temperature), int(logprobs))

@@ -59,6 +59,21 @@ int ifa_engine_add_query_lp(ifa_engine *e, const int *tokens, int n_tokens, int 
     return e->engine.AddQuery(std::vector<int>(tokens, tokens + n_tokens), opt);
 }
 
+int ifa_engine_add_query_opt(ifa_engine *e, const int *tokens, int n_tokens, const ifa_query_options *o)
+{
+    if (!e || !tokens || n_tokens <= 0 || !o) { EngineSetError("ifa_engine_add_query_opt: bad arguments"); return -1; }
+    if (o->struct_size < sizeof(size_t)) { EngineSetError("ifa_engine_add_query_opt: struct_size %zu", o->struct_size); return -1; }
+    ifa_query_options v;           // the caller's leading struct_size bytes over the defaults
+    memset(&v, 0, sizeof v);
+    v.temperature = 1.0f; v.logprobs = -1; v.repetition_penalty = 1.0f;
+    memcpy(&v, o, std::min(o->struct_size, sizeof v));
+    if (v.n_logit_bias < 0 || (v.n_logit_bias > 0 && (!v.logit_bias_ids || !v.logit_bias_values))) { EngineSetError("ifa_engine_add_query_opt: %d logit_bias entries without arrays", v.n_logit_bias); return -1; }
+    QueryOptions opt; opt.strategy_id = v.strategy_id; opt.random_seed = v.random_seed; opt.temperature = v.temperature; opt.logprobs = v.logprobs;
+    opt.repetition_penalty = v.repetition_penalty; opt.presence_penalty = v.presence_penalty; opt.frequency_penalty = v.frequency_penalty;
+    for (int i = 0; i < v.n_logit_bias; i++) opt.logit_bias.emplace_back(v.logit_bias_ids[i], v.logit_bias_values[i]);
+    return e->engine.AddQuery(std::vector<int>(tokens, tokens + n_tokens), opt);
+}
+
 int ifa_engine_last_logprobs(ifa_engine *e, int query_id, float *chosen, int *ids, float *logprobs, int cap, int *n)
 {
     if (!e || cap < 0 || (cap > 0 && (!ids || !logprobs))) { EngineSetError("ifa_engine_last_logprobs: bad arguments"); return 0; }
@@ -299,6 +314,8 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "prefix_cache_hits") return (int)std::min<long long>(e->engine.prefix_cache_hits(), 0x7FFFFFFF);
     if (k == "prefix_cache_tokens") return (int)std::min<long long>(e->engine.prefix_cache_tokens(), 0x7FFFFFFF);
     if (k == "lookup_decoding") return e->engine.lookup_decoding_active() ? 1 : 0;
+    if (k == "logit_processors") return e->engine.SupportsLogitProcessors() ? 1 : 0;
+    if (k == "processed_steps") return (int)std::min<long long>(e->engine.processed_steps(), 0x7FFFFFFF);
     if (k == "prefix_cache_copies") return (int)std::min<long long>(e->engine.prefix_cache_copies(), 0x7FFFFFFF);
     return -1;
 }
@@ -391,7 +408,7 @@ int ifa_service_parse_request(const char *body, int is_openai_mode, char *out_js
     const std::string js = "{\"prompt_token_ids\": " + ids + ", \"max_output_len\": " + std::to_string(r.max_output_len) + ", \"decoding_alg\": \"" + r.decoding_alg
         + "\", \"random_seed\": " + std::to_string(r.random_seed) + ", \"temperature\": " + tmp + ", \"is_streaming_mode\": " + (r.is_streaming_mode ? "true" : "false")
         + ", \"eos_token_id\": " + std::to_string(r.eos_token_id) + ", \"fn\": \"" + r.fn + "\""
-        + (r.logprobs >= 0 ? ", \"logprobs\": " + std::to_string(r.logprobs) : std::string()) + "}";
+        + (r.logprobs >= 0 ? ", \"logprobs\": " + std::to_string(r.logprobs) : std::string()) + r.ProcessorsJson() + "}";
     if (js.size() + 1 > cap) return -1;
     memcpy(out_json, js.c_str(), js.size() + 1);
     return 0;

@@ -5,6 +5,7 @@
 // picks one and commits it with CommitInferenceResult (llm_inference.cc:345-457).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 
 #include "inferflow_amd.h"
 #include "inference_engine.h"
@@ -26,6 +27,7 @@ void InferenceEngine::Clear()
     queries_.clear();
     prefix_active_ = false; slot_records_.clear();
     use_clock_ = prefix_hits_ = prefix_tokens_ = prefix_copies_ = 0;
+    processed_steps_ = 0;
 }
 
 bool InferenceEngine::Init(const InferenceConfig &cfg)
@@ -106,6 +108,22 @@ int InferenceEngine::AddQuery(const std::vector<int> &tokens, const QueryOptions
     if (query_options.logprobs < -1 || query_options.logprobs > QueryOptions::MAX_LOGPROBS) { EngineSetError("logprobs %d is outside -1..%d", query_options.logprobs, QueryOptions::MAX_LOGPROBS); return -1; }
     if (query_options.logprobs >= 0 && multi_) { EngineSetError("logprobs are not available on a multi-device engine (the vocabulary is sharded)"); return -1; }
     if (query_options.logprobs >= 0 && config_.return_output_tensors) { EngineSetError("logprobs are not available with return_output_tensors = true (take them from the output tensor)"); return -1; }
+    const bool processed = query_options.Processed();
+    if (processed && multi_) { EngineSetError("logit processors (penalties, logit_bias) are not available on a multi-device engine (the vocabulary is sharded)"); return -1; }
+    if (processed && config_.return_output_tensors) { EngineSetError("logit processors (penalties, logit_bias) are not available with return_output_tensors = true (the output tensor is the raw row)"); return -1; }
+    if (!(std::isfinite(query_options.repetition_penalty) && query_options.repetition_penalty > 0.0f)) { EngineSetError("repetition_penalty %g must be finite and above 0", (double)query_options.repetition_penalty); return -1; }
+    if (!std::isfinite(query_options.presence_penalty) || !std::isfinite(query_options.frequency_penalty)) { EngineSetError("presence_penalty %g / frequency_penalty %g must be finite", (double)query_options.presence_penalty, (double)query_options.frequency_penalty); return -1; }
+    if ((int)query_options.logit_bias.size() > QueryOptions::MAX_LOGIT_BIAS) { EngineSetError("logit_bias has %zu entries, at most %d", query_options.logit_bias.size(), QueryOptions::MAX_LOGIT_BIAS); return -1; }
+    {   // every rule of the bias here, in front of the busy answer and of PlaceQuery: a refused query costs no slot record and no counter
+        std::vector<int> seen;
+        for (const auto &b : query_options.logit_bias) {
+            if (b.first < 0 || b.first >= spec_.hyper_params.vocab_size) { EngineSetError("logit_bias id %d is outside the vocabulary", b.first); return -1; }
+            if (!(std::isfinite(b.second) || b.second == -INFINITY)) { EngineSetError("logit_bias value %g for id %d must be finite or -inf", (double)b.second, b.first); return -1; }
+            seen.push_back(b.first);
+        }
+        std::sort(seen.begin(), seen.end());
+        for (size_t i = 1; i < seen.size(); i++) if (seen[i] == seen[i - 1]) { EngineSetError("logit_bias id %d is given twice", seen[i]); return -1; }
+    }
     if ((int)queries_.size() >= std::min(config_.max_concurrent_queries, kv_slots_)) return 0;      // busy
     Query q; q.id = next_query_id_++; q.tokens = tokens; q.options = query_options;
     q.strategy = strategy; q.sampling = default_sampling_;
@@ -113,7 +131,19 @@ int InferenceEngine::AddQuery(const std::vector<int> &tokens, const QueryOptions
     if (query_options.logprobs >= 0 && PoolK(q) > IFA_POOL_MAX) {      // (its steps could not end in a device pool: no logprobs would come back)
         EngineSetError("logprobs need the query's %d sampling candidates in one device pool of at most %d", PoolK(q), IFA_POOL_MAX); return -1;
     }
+    if (processed && (PoolK(q) < 1 || PoolK(q) > IFA_POOL_MAX)) {     // (its steps could not end in a device pool: nothing would apply the processors)
+        EngineSetError("logit processors need the query's %d sampling candidates in one device pool of at most %d", PoolK(q), IFA_POOL_MAX); return -1;
+    }
     if (!PlaceQuery(q)) return -1;
+    if (processed) {     // the WHOLE prompt, however many of its rows the prefix cache supplied: the state is about ids, not cache rows
+        std::vector<int> ids; std::vector<float> vals;
+        for (const auto &b : query_options.logit_bias) { ids.push_back(b.first); vals.push_back(b.second); }
+        if (ifa_model_logit_state_reset(model_, q.kv_slot, q.tokens.data(), (int)q.tokens.size(), query_options.repetition_penalty, query_options.frequency_penalty,
+                                        query_options.presence_penalty, ids.data(), vals.data(), (int)ids.size()) != IFA_OK) {
+            EngineSetError("logit processors: %s", ifa_last_error()); return -1;
+        }
+        q.counted = (int)q.tokens.size();
+    }
     queries_[q.id] = q;
     return q.id;
 }
@@ -204,6 +234,7 @@ bool InferenceEngine::PoolRoute(const Query &q) const
     if (config_.return_output_tensors || multi_) return false;
     const int k = PoolK(q);
     if (q.options.logprobs >= 0) return k <= IFA_POOL_MAX;      // logprobs ride on the pool whatever device_sampling_pool says
+    if (q.options.Processed()) return k >= 1 && k <= IFA_POOL_MAX;      // so do the logit processors: the pool is where they apply
     if (!config_.device_sampling_pool) return false;
     if (!Sampled(q)) return false;      // (the device argmax serves it)
     return k >= 1 && k <= IFA_POOL_MAX;
@@ -316,7 +347,7 @@ bool InferenceEngine::LogitsToHost(uint16_t *dst, size_t row0, size_t rows)
 
 // the batched worker call of a single-device engine: the pools of plan.pool_rows and / or the [n][vocab] block come to the host
 bool InferenceEngine::BatchStep(const std::vector<int> &toks, const std::vector<int> &pos, const std::vector<int> &slots, std::vector<int> &next,
-                                const BatchStepPlan &plan, BatchPools &pools, std::vector<uint16_t> &all)
+                                const BatchStepPlan &plan, const std::vector<int> &adj_slots, BatchPools &pools, std::vector<uint16_t> &all)
 {
     const int n = (int)toks.size();
     const size_t ns = plan.pool_rows.size();
@@ -324,6 +355,7 @@ bool InferenceEngine::BatchStep(const std::vector<int> &toks, const std::vector<
     if (ns > 0) {       // no logits row leaves the device for these rows; a query reads its own prefix of the launch's sorted pool
         pools.ids.resize(ns * (size_t)plan.pool_k); pools.vals.resize(ns * (size_t)plan.pool_k); pools.counts.resize(ns);
         if (!SetPoolLse(plan.with_lse)) return false;
+        if (!adj_slots.empty() && ifa_model_pool_adjust(model_, (int)ns, adj_slots.data()) != IFA_OK) { EngineSetError("logit processors: %s", ifa_last_error()); return false; }
         if (ifa_model_decode_batch_pool(model_, n, toks.data(), pos.data(), slots.data(), next.data(), plan.pool_k, plan.pool_rows.data(), (int)ns,
                                         pools.ids.data(), pools.vals.data(), pools.counts.data()) != IFA_OK) {
             EngineSetError("batched decode step failed: %s", ifa_last_error()); return false;
@@ -351,19 +383,29 @@ bool InferenceEngine::InferBatch(const std::vector<Query *> &batch, InferenceRes
         const Query &q = *batch[(size_t)r];
         toks[(size_t)r] = q.tokens.back(); pos[(size_t)r] = q.processed; slots[(size_t)r] = q.kv_slot;
         BatchRow &row = rows[(size_t)r];
-        row.pool_route = PoolRoute(q); row.sampled = Sampled(q); row.pool_len = PoolLen(q); row.pool_k = PoolK(q); row.wants_logprobs = q.options.logprobs >= 0;
+        // (a processed row pins the step to the pools the way a logprobs row does -- a host-sampled neighbour takes a pool of its
+        //  own length instead of bringing the raw block over, which the processors never saw -- but asks for no lse)
+        row.pool_route = PoolRoute(q); row.sampled = Sampled(q); row.pool_len = PoolLen(q); row.pool_k = PoolK(q);
+        row.wants_logprobs = q.options.logprobs >= 0; row.must_pool = q.options.Processed();
     }
     const BatchStepPlan plan = PlanBatchStep(config_.return_output_tensors, rows);
     if (plan.error_row >= 0) {
-        EngineSetError("query %d samples from %d candidates, more than a device pool holds; it cannot share a step with a logprobs query",
+        EngineSetError("query %d samples from %d candidates, more than a device pool holds; it cannot share a step with a logprobs or processed query",
                        batch[(size_t)plan.error_row]->id, rows[(size_t)plan.error_row].pool_len);
         return false;
     }
     BatchPools pools; std::vector<uint16_t> all;
+    std::vector<int> adj_slots;
+    for (size_t j = 0; j < plan.pool_rows.size(); j++) {
+        const Query &q = *batch[(size_t)plan.pool_rows[j]];
+        if (!q.options.Processed()) continue;
+        if (adj_slots.empty()) adj_slots.assign(plan.pool_rows.size(), -1);
+        adj_slots[j] = q.kv_slot;
+    }
     // Query batching over a tensor-parallel device group (the reference: query batching, inference_engine.cc:1054-1124,
     // inside Infer_TensorParallelism, :1222-1296): every rank runs ONE batched step over the same queries -- merges
     // over [n][dim], one distributed argmax per row (ifa_model_tp_decode_batch) -- and hands back its vocabulary shard
-    if (multi_ ? !MultiBatchStep(toks, pos, slots, next, plan.want_logits, all) : !BatchStep(toks, pos, slots, next, plan, pools, all)) return false;
+    if (multi_ ? !MultiBatchStep(toks, pos, slots, next, plan.want_logits, all) : !BatchStep(toks, pos, slots, next, plan, adj_slots, pools, all)) return false;
     // the step was ONE worker call: its rows are committed together, once the item of every row is complete
     std::vector<QueryInferenceResult> items((size_t)n);
     for (int r = 0; r < n; r++) {
@@ -380,6 +422,11 @@ bool InferenceEngine::InferBatch(const std::vector<Query *> &batch, InferenceRes
         const size_t j = (size_t)(pr - plan.pool_rows.begin());
         const int *ids = pools.ids.data() + j * (size_t)plan.pool_k; const uint16_t *vals = pools.vals.data() + j * (size_t)plan.pool_k;
         if (row.sampled && !SamplePool(q, ids, vals, std::min(pools.counts[j], row.pool_len), item)) return false;
+        if (!row.sampled && q.options.Processed()) {     // the step's argmax saw the raw row: the processed greedy token is the pool's best entry
+            if (pools.counts[j] < 1) { EngineSetError("logit processors left query %d no admissible token", q.id); return false; }
+            item.next_tokens[0] = OneToken(ids[0]);
+        }
+        if (q.options.Processed()) processed_steps_++;
         if (row.wants_logprobs && !FillLogprobs(q, ids, vals, std::min(pools.counts[j], row.pool_k), pools.lse[j], item)) return false;
     }
     for (int r = 0; r < n; r++) { batch[(size_t)r]->processed = (int)batch[(size_t)r]->tokens.size(); res.items.push_back(std::move(items[(size_t)r])); }
@@ -390,15 +437,21 @@ bool InferenceEngine::InferBatch(const std::vector<Query *> &batch, InferenceRes
 bool InferenceEngine::PoolStep(Query &q, int n_new, QueryInferenceResult &item)
 {
     const bool lp = q.options.logprobs >= 0;
+    const bool processed = q.options.Processed();
     if (!SetPoolLse(lp)) return false;
     int ids[IFA_POOL_MAX], cnt = 0, next = -1; uint16_t vals[IFA_POOL_MAX];
+    if (processed && ifa_model_pool_adjust(model_, 1, &q.kv_slot) != IFA_OK) { EngineSetError("logit processors: %s", ifa_last_error()); return false; }
     // (a prompt keeps the forward step -- lm_head over all rows into the engine's logits buffer, so its last row is bit for
     //  bit the row the host path samples from -- and only the pool of that row comes to the host)
     const int rc = n_new == 1 ? ifa_model_decode_pool(model_, q.tokens.back(), q.processed, PoolK(q), &next, ids, vals, &cnt)
                               : ifa_model_forward_pool(model_, q.tokens.data() + q.processed, n_new, q.processed, logits_dev_, PoolK(q), &next, ids, vals, &cnt);
     if (rc != IFA_OK) { EngineSetError("%s step failed: %s", n_new == 1 ? "decode" : "forward", ifa_last_error()); return false; }
     if (n_new == 1) sampled_fused_steps_++;
-    if (!Sampled(q)) item.next_tokens.push_back(OneToken(next));
+    if (processed) processed_steps_++;
+    if (processed && !Sampled(q)) {      // the step's argmax saw the raw row: the processed greedy token is the pool's best entry
+        if (cnt < 1) { EngineSetError("logit processors left query %d no admissible token", q.id); return false; }
+        item.next_tokens.push_back(OneToken(ids[0]));
+    } else if (!Sampled(q)) item.next_tokens.push_back(OneToken(next));
     else if (!SamplePool(q, ids, vals, std::min(cnt, PoolLen(q)), item)) return false;
     if (lp) {
         float lse = 0.0f; int got = 0;
@@ -446,12 +499,32 @@ bool InferenceEngine::InferQuery(Query &q, InferenceResult &res)
     return true;
 }
 
+// enqueue-only on the worker's stream, in front of this step's launches; a query's `counted` moves behind every worker call that
+// has taken its pairs, so a retried Infer() does not count a token twice
+bool InferenceEngine::CountCommitted()
+{
+    std::vector<int> slots, toks;
+    std::vector<Query *> owner;
+    for (auto &kv : queries_) {
+        Query &q = kv.second;
+        if (!q.options.Processed()) continue;
+        for (int i = q.counted; i < (int)q.tokens.size(); i++) { slots.push_back(q.kv_slot); toks.push_back(q.tokens[(size_t)i]); owner.push_back(&q); }
+    }
+    for (size_t off = 0; off < toks.size(); off += 1024) {      // (the worker takes 1024 pairs a call; a step commits one per query)
+        const size_t n = std::min<size_t>(1024, toks.size() - off);
+        if (ifa_model_logit_state_add(model_, (int)n, slots.data() + off, toks.data() + off) != IFA_OK) { EngineSetError("logit processors: %s", ifa_last_error()); return false; }
+        for (size_t i = off; i < off + n; i++) owner[i]->counted++;
+    }
+    return true;
+}
+
 bool InferenceEngine::Infer(InferenceResult &res)
 {
     res.items.clear(); res.perf_stat.time_map.clear();
     if (!model_) { EngineSetError("The engine is not initialized"); return false; }
     const auto t0 = std::chrono::steady_clock::now();
     const int max_ctx = MaxContextLen();
+    if (!CountCommitted()) return false;
     std::vector<Query *> batch;
     // (a partition with several layer groups steps its queries one by one: a batched step is one tensor-parallel group's)
     if (LayerGroups() == 1)
@@ -504,7 +577,10 @@ InferenceEngine::Query *InferenceEngine::FindQuery(int query_id)
 bool InferenceEngine::DeviceGreedyOk(const Query &q, int n_new, bool lookup)
 {
     if (q.ended) { EngineSetError("Query %d has ended", q.id); return false; }
-    if (host_greedy_)
+    if (q.options.Processed())
+        EngineSetError(lookup ? "GenerateLookup() feeds the token back on the device without logit processors; query %d has penalties or a logit_bias (use Infer / CommitInferenceResult)"
+                              : "Generate() feeds the token back on the device without logit processors; query %d has penalties or a logit_bias (use Infer / CommitInferenceResult)", q.id);
+    else if (host_greedy_)
         EngineSetError(lookup ? "GenerateLookup() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)"
                               : "Generate() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size());
     else if (q.strategy != SamplingStrategyId::Greedy)

@@ -129,6 +129,17 @@ struct QueryOptions {               // SamplingStrategy::QueryOptions (sampling_
     // Single-device engines with return_output_tensors = false only: AddQuery refuses it elsewhere.
     int logprobs = -1;
     static const int MAX_LOGPROBS = 20;
+    // extension: logit processors, applied on the device to the step's logits row in front of the candidate pool and the
+    // log-sum-exp (csrc/ifa_logit_adjust.hip; arithmetic and order in DESIGN.md "Logit processors").  repetition_penalty: the HF
+    // rule over prompt + generated ids (x > 0 ? x / r : x * r); frequency_penalty / presence_penalty: the OpenAI rule over the
+    // generated ids (x - (f * count + (count > 0 ? p : 0))); logit_bias: (id, value) pairs added last, -inf bans the id.  A query
+    // with any of them non-neutral is PROCESSED: its steps end in the device pool whatever device_sampling_pool says, a greedy one
+    // takes the pool's best entry, logprobs are those of the processed distribution at temperature 1.  Single-device engines with
+    // return_output_tensors = false only; Generate / GenerateLookup refuse a processed query.
+    float repetition_penalty = 1.0f, presence_penalty = 0.0f, frequency_penalty = 0.0f;
+    std::vector<std::pair<int, float>> logit_bias;
+    static const int MAX_LOGIT_BIAS = 1024;
+    bool Processed() const { return repetition_penalty != 1.0f || presence_penalty != 0.0f || frequency_penalty != 0.0f || !logit_bias.empty(); }
 };
 
 struct QueryInferenceResult {
@@ -176,6 +187,8 @@ public:
     virtual int VocabSize() const = 0;
     // whether AddQuery accepts QueryOptions::logprobs >= 0 (the service answers "error.unsupported" otherwise)
     virtual bool SupportsLogprobs() const { return false; }
+    // whether AddQuery accepts a processed query (QueryOptions::Processed(); the service answers "error.unsupported" otherwise)
+    virtual bool SupportsLogitProcessors() const { return false; }
 };
 
 class InferenceEngine : public QueryEngine {
@@ -203,6 +216,9 @@ public:
     std::string ModelId() const override { return spec_.sid; }
     int VocabSize() const override { return spec_.hyper_params.vocab_size; }
     bool SupportsLogprobs() const override { return model_ && !multi_ && !config_.return_output_tensors; }
+    bool SupportsLogitProcessors() const override { return model_ && !multi_ && !config_.return_output_tensors; }
+    // steps (one per query per step) whose pool was built from a row the logit processors had rewritten
+    long long processed_steps() const { return processed_steps_; }
 
     // Extension: log p(tokens[i + 1] | tokens[0..i]) for i = 0 .. n - 2 (softmax over the full vocabulary, as the perplexity tool
     // takes it) through ifa_model_forward_score on a free KV slot: the rows' log-sum-exp and target logits are reduced on the
@@ -266,6 +282,7 @@ private:
         bool ended = false;
         int kv_slot = 0;            // this query's KV cache inside the worker (ifa_model_select_kv)
         int cached_tokens = 0;      // rows the prefix cache supplied at AddQuery (processed started there)
+        int counted = 0;            // a processed query: tokens[0 .. counted) are in its device logit state (the prompt, then the generated ones)
         SamplingStrategyId strategy = SamplingStrategyId::Greedy;
         StdSamplingConfig sampling; // per query copy, like StdQueryData::config
         JavaRandom rng;
@@ -274,8 +291,10 @@ private:
     // ---- Infer: the route of every step is planned in pure code (step_plan.h); these run the plan
     struct BatchPools { std::vector<int> ids, counts; std::vector<uint16_t> vals; std::vector<float> lse; };     // [pool_rows][pool_k]
     bool InferBatch(const std::vector<Query *> &batch, InferenceResult &res);       // the queries that advance by one token, in ONE step
+    // adj_slots: empty, or per pool row of the plan the state slot of a processed query (-1: the row stays raw)
     bool BatchStep(const std::vector<int> &toks, const std::vector<int> &pos, const std::vector<int> &slots, std::vector<int> &next,
-                   const BatchStepPlan &plan, BatchPools &pools, std::vector<uint16_t> &all);
+                   const BatchStepPlan &plan, const std::vector<int> &adj_slots, BatchPools &pools, std::vector<uint16_t> &all);
+    bool CountCommitted();          // the tokens processed queries have committed since the last step -> their device counts, one call
     bool InferQuery(Query &q, InferenceResult &res);                                // one query's own step
     bool PoolStep(Query &q, int n_new, QueryInferenceResult &item);
     bool Sampled(const Query &q) const { return q.strategy != SamplingStrategyId::Greedy || host_greedy_; }   // its token is chosen on the host
@@ -319,7 +338,7 @@ private:
     std::map<int, Query> queries_;
     void *logits_dev_ = nullptr;
     size_t logits_rows_ = 0;
-    long long sampled_fused_steps_ = 0;
+    long long sampled_fused_steps_ = 0, processed_steps_ = 0;
     bool pool_lse_on_ = false;      // the worker's option pool_lse as last set
     // ---- prompt prefix cache.  Record invariant: rows [0, tokens.size()) of a FREE slot's K and V hold exactly these token ids at
     // these positions.  A busy slot's record is implicit (its query's tokens[0 .. processed)); RemoveQuery turns it into the stored

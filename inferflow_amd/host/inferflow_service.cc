@@ -10,8 +10,10 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <sstream>
 
 #include "ifa_json.h"
@@ -72,6 +74,53 @@ static bool ReadIds(const JsonValue *v, std::vector<int> &out)
     return true;
 }
 
+std::string InferFlowRequest::ProcessorsJson() const
+{
+    char buf[64];
+    std::string s;
+    auto num = [&](const char *key, float v) { snprintf(buf, sizeof buf, "%.4f", v); s += std::string(", \"") + key + "\": " + buf; };
+    if (has_repetition_penalty) num("repetition_penalty", repetition_penalty);
+    if (has_presence_penalty) num("presence_penalty", presence_penalty);
+    if (has_frequency_penalty) num("frequency_penalty", frequency_penalty);
+    if (has_logit_bias) {
+        s += ", \"logit_bias\": {";
+        for (size_t i = 0; i < logit_bias.size(); i++) {
+            snprintf(buf, sizeof buf, "%.4f", logit_bias[i].second);
+            s += std::string(i ? ", " : "") + "\"" + std::to_string(logit_bias[i].first) + "\": " + buf;
+        }
+        s += "}";
+    }
+    return s;
+}
+
+// a penalty field: absent, or a number inside [lo, hi] (lo_open: above lo)
+static bool ReadPenalty(const JsonValue &root, const char *key, float lo, float hi, bool lo_open, float &out, bool &given)
+{
+    const JsonValue *v = root.Get(key);
+    if (!v) return true;
+    if (v->type != JsonValue::Number || !std::isfinite(v->num) || v->num > hi || v->num < lo || (lo_open && v->num <= lo)) return false;
+    out = (float)v->num; given = true;
+    return true;
+}
+
+// {"<id>": value}: keys are decimal token ids (distinct), values numbers in -100..100, at most MAX_LOGIT_BIAS entries
+static bool ReadLogitBias(const JsonValue &root, InferFlowRequest &r)
+{
+    const JsonValue *v = root.Get("logit_bias");
+    if (!v) return true;
+    if (v->type != JsonValue::Object || (int)v->obj.size() > InferFlowRequest::MAX_LOGIT_BIAS) return false;
+    for (const auto &kv : v->obj) {
+        const std::string &k = kv.first;
+        if (k.empty() || k.size() > 9 || k.find_first_not_of("0123456789") != std::string::npos) return false;
+        if (kv.second.type != JsonValue::Number || !(kv.second.num >= -100.0 && kv.second.num <= 100.0)) return false;
+        const int id = atoi(k.c_str());
+        for (const auto &have : r.logit_bias) if (have.first == id) return false;
+        r.logit_bias.emplace_back(id, (float)kv.second.num);
+    }
+    r.has_logit_bias = true;
+    return true;
+}
+
 bool InferFlowServiceCore::ParseRequest(InferFlowRequest &r, const std::string &body, bool is_openai_mode, std::string *err)
 {
     JsonValue root; JsonParser parser; std::string perr;
@@ -104,6 +153,10 @@ bool InferFlowServiceCore::ParseRequest(InferFlowRequest &r, const std::string &
         if (!root.GetNumber("top_logprobs", top_lp) || !want_lp || top_lp < 0 || top_lp > QueryOptions::MAX_LOGPROBS) { if (err) *err = "error.invalid_logprobs"; return false; }
     }
     r.logprobs = want_lp ? top_lp : -1;
+    if (!ReadPenalty(root, "repetition_penalty", 0.0f, std::numeric_limits<float>::max(), true, r.repetition_penalty, r.has_repetition_penalty)
+        || !ReadPenalty(root, "presence_penalty", -2.0f, 2.0f, false, r.presence_penalty, r.has_presence_penalty)
+        || !ReadPenalty(root, "frequency_penalty", -2.0f, 2.0f, false, r.frequency_penalty, r.has_frequency_penalty)) { if (err) *err = "error.invalid_penalty"; return false; }
+    if (!ReadLogitBias(root, r)) { r.logit_bias.clear(); if (err) *err = "error.invalid_logit_bias"; return false; }
     return true;
 }
 
@@ -193,6 +246,9 @@ bool InferFlowServiceCore::ProcessQuery(InferFlowResponseChunk &result, const In
     result.want_logprobs = request.logprobs >= 0;
     if (request.logprobs > QueryOptions::MAX_LOGPROBS || request.logprobs < -1) { result.ret_code = "error.invalid_logprobs"; return false; }
     if (request.logprobs >= 0 && !engine_.SupportsLogprobs()) { result.ret_code = "error.logprobs_unsupported"; return false; }
+    qo.repetition_penalty = request.repetition_penalty; qo.presence_penalty = request.presence_penalty; qo.frequency_penalty = request.frequency_penalty;
+    qo.logit_bias = request.logit_bias;
+    if (qo.Processed() && !engine_.SupportsLogitProcessors()) { result.ret_code = "error.unsupported"; return false; }
     int qid = 0;
     {
         // registered before the loop can step the query (the loop holds engine_lock_ for a whole Infer + Commit)

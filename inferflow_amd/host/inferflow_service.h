@@ -38,6 +38,14 @@ struct InferFlowRequest {                 // InferFlowRequest (inferflow_service
     std::string fn;                       // "" / "process_query" | "get_stat"
     // "logprobs": true (+ "top_logprobs": n in 0..20) in the body -> QueryOptions::logprobs = n; -1: not asked for
     int logprobs = -1;
+    // logit processors (QueryOptions): "repetition_penalty" (> 0), "presence_penalty" / "frequency_penalty" (-2..2),
+    // "logit_bias": {"<id>": value in -100..100}, at most MAX_LOGIT_BIAS entries; has_*: the field was in the body
+    static const int MAX_LOGIT_BIAS = 300;
+    float repetition_penalty = 1.0f, presence_penalty = 0.0f, frequency_penalty = 0.0f;
+    std::vector<std::pair<int, float>> logit_bias;
+    bool has_repetition_penalty = false, has_presence_penalty = false, has_frequency_penalty = false, has_logit_bias = false;
+    // ", \"repetition_penalty\": 1.3000, ..." for the fields that were given (the parser's echo)
+    std::string ProcessorsJson() const;
 };
 
 struct TokenLogprob {                     // one generated token: its log-probability and the most probable tokens of its step

@@ -28,14 +28,16 @@ QueryStepPlan PlanQueryStep(bool multi, bool return_output_tensors, bool pool_ro
 BatchStepPlan PlanBatchStep(bool return_output_tensors, const std::vector<BatchRow> &rows)
 {
     BatchStepPlan p;
-    bool host_sampled = false;
+    bool host_sampled = false, pinned = false;      // pinned: a row that cannot do without its pool (logprobs, logit processors)
     for (size_t r = 0; r < rows.size(); r++) {
         const BatchRow &row = rows[r];
-        if (row.pool_route) { p.pool_rows.push_back((int)r); p.pool_k = std::max(p.pool_k, row.pool_k); p.with_lse = p.with_lse || row.wants_logprobs; }
-        else host_sampled = host_sampled || row.sampled;
+        if (row.pool_route) {
+            p.pool_rows.push_back((int)r); p.pool_k = std::max(p.pool_k, row.pool_k); p.with_lse = p.with_lse || row.wants_logprobs;
+            pinned = pinned || row.wants_logprobs || row.must_pool;
+        } else host_sampled = host_sampled || row.sampled;
     }
-    if (host_sampled && !p.with_lse) { p.pool_rows.clear(); p.pool_k = 0; }
-    if (host_sampled && p.with_lse) {
+    if (host_sampled && !pinned) { p.pool_rows.clear(); p.pool_k = 0; }
+    if (host_sampled && pinned) {
         for (size_t r = 0; r < rows.size(); r++) {
             const BatchRow &row = rows[r];
             if (row.pool_route || !row.sampled) continue;

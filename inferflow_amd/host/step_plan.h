@@ -27,6 +27,7 @@ struct BatchRow {
     bool pool_route = false, sampled = false;
     int pool_len = 0, pool_k = 0;           // the sampler's pool length; the entries asked of the device (more for logprobs)
     bool wants_logprobs = false;
+    bool must_pool = false;                 // a processed query (logit processors): its token exists only in its pool; no lse of its own
 };
 
 struct BatchStepPlan {
@@ -39,8 +40,9 @@ struct BatchStepPlan {
 
 // One batched decode step.  A row that is sampled and not on the pool route is "host-sampled": it needs its logits row.
 //  1. pool-route rows join pool_rows; pool_k = the largest pool_k among them; with_lse: one of them wants logprobs;
-//  2. a host-sampled row and no logprobs row: the block comes over anyway, so no pools at all (pool_rows empty, pool_k 0);
-//  3. a host-sampled row next to a logprobs row (which needs its pool and lse): every host-sampled row takes a pool of its pool_len
+//  2. a host-sampled row and no logprobs / must_pool row: the block comes over anyway, so no pools at all (pool_rows empty, pool_k 0);
+//  3. a host-sampled row next to a logprobs row (which needs its pool and lse) or a must_pool row (whose pool is built from a row
+//     the raw block does not show): every host-sampled row takes a pool of its pool_len
 //     too -- 1 <= pool_len <= IFA_POOL_MAX, else error_row -- and no row is host-sampled any more;
 //  4. want_logits = return_output_tensors || a host-sampled row is left.
 BatchStepPlan PlanBatchStep(bool return_output_tensors, const std::vector<BatchRow> &rows);

@@ -199,6 +199,29 @@ class DecodeWorker:
         finally:
             self.set_option("pool_lse", 0)
 
+    def logit_state_reset(self, kv_slot, prompt, rep=1.0, freq=0.0, pres=0.0, bias=None):
+        """The logit-processor state of the query in kv_slot (ifa_model_logit_state_reset): cleared, the prompt ids marked, the
+        penalties and the logit_bias ({id: value}, -inf bans) stored."""
+        pr = np.ascontiguousarray(prompt, np.int32).reshape(-1)
+        items = sorted((bias or {}).items())
+        ids = np.ascontiguousarray([k for k, _ in items], np.int32)
+        vals = np.ascontiguousarray([v for _, v in items], np.float32)
+        check(lib().ifa_model_logit_state_reset(self._h, int(kv_slot), pr.ctypes.data_as(C.c_void_p) if pr.size else None, pr.size, float(rep), float(freq),
+                                                float(pres), ids.ctypes.data_as(C.c_void_p) if ids.size else None,
+                                                vals.ctypes.data_as(C.c_void_p) if vals.size else None, ids.size))
+
+    def logit_state_add(self, kv_slots, tokens):
+        """One more generated occurrence for every (kv slot, token) pair; enqueue-only (ifa_model_logit_state_add)"""
+        sl = np.ascontiguousarray(kv_slots, np.int32).reshape(-1)
+        tk = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        assert sl.size == tk.size
+        check(lib().ifa_model_logit_state_add(self._h, sl.size, sl.ctypes.data_as(C.c_void_p), tk.ctypes.data_as(C.c_void_p)))
+
+    def pool_adjust(self, state_slots):
+        """Arms the NEXT pool step: entry j = the state slot whose processors rewrite pooled row j, -1 = the row stays raw"""
+        sl = np.ascontiguousarray(state_slots, np.int32).reshape(-1)
+        check(lib().ifa_model_pool_adjust(self._h, sl.size, sl.ctypes.data_as(C.c_void_p) if sl.size else None))
+
     def forward_score(self, tokens, prefix_len, targets):
         """A scoring prompt (ifa_model_forward_score): per row the log-sum-exp of its logits and its logit at targets[i] (NaN for a
         target below 0), without a [T][vocab] block leaving the worker.  Returns (next token, lse float32 [T], target logit float32 [T]);
@@ -350,6 +373,41 @@ def logsumexp_rows(logits, n=None, row_idx=None, targets=None, split=True, strea
                                    C.c_void_p(stream)))
     lse._ifa_workspace = ws      # (alive as long as the result: the launches are only enqueued)
     return lse, tl
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def logit_adjust_rows(logits, state_slots, state, bias, params, n=None, row_idx=None, stream=None):
+    """ifa_logit_adjust_rows over a torch cuda F16 tensor [rows_avail][stride] (any storage offset / stride): output row r (compact
+    [rows][n] F16) = the processors of slot state_slots[r] (torch cuda int32) applied to input row row_idx[r] (torch cuda int32;
+    default row r).  state: cuda int32 / uint32 bits [slots][n], bias: cuda float32 [slots][n], params: cuda float32 [slots][3]."""
+    import torch
+    if logits.dim() == 1:
+        logits = logits.reshape(1, -1)
+    n = logits.shape[1] if n is None else int(n)
+    rows = state_slots.numel()
+    out = torch.empty((rows, n), dtype=torch.float16, device=logits.device)
+    check(lib().ifa_logit_adjust_rows(_ptr(logits), logits.stride(0), _ptr(row_idx), _ptr(state_slots), rows, n, _ptr(state), _ptr(bias), _ptr(params),
+                                      _ptr(out), C.c_void_p(stream)))
+    return out
+
+
+def logit_state_reset(slot, prompt, rep, freq, pres, bias_ids, bias_vals, state, bias, params, stream=None):
+    """ifa_logit_state_reset on torch cuda tensors: prompt / bias_ids int32, bias_vals float32 (None: none); state [slots][n] int32
+    bits, bias [slots][n] float32, params [slots][3] float32 are updated in place; enqueue-only."""
+    n_prompt = prompt.numel() if prompt is not None else 0
+    n_bias = bias_ids.numel() if bias_ids is not None else 0
+    check(lib().ifa_logit_state_reset(int(slot), _ptr(prompt) if n_prompt else None, n_prompt, float(rep), float(freq), float(pres),
+                                      _ptr(bias_ids) if n_bias else None, _ptr(bias_vals) if n_bias else None, n_bias, state.shape[1],
+                                      _ptr(state), _ptr(bias), _ptr(params), C.c_void_p(stream)))
+
+
+def logit_state_add(slots, tokens, state, stream=None):
+    """ifa_logit_state_add: state[slots[i]][tokens[i]] += 1 for every pair (torch cuda int32) in one launch; enqueue-only"""
+    assert slots.numel() == tokens.numel()
+    check(lib().ifa_logit_state_add(_ptr(slots), _ptr(tokens), slots.numel(), state.shape[1], state.shape[0], _ptr(state), C.c_void_p(stream)))
 
 
 class TpTopology(C.Structure):
