@@ -448,6 +448,14 @@ int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, 
 /* debugging taps: "logits", "logits_adj" (the rows the last armed pool step adjusted; null before the first), "hidden", "kcache", "vcache" (device pointers) */
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes);
 void *ifa_model_stream(ifa_model *m);
+/* Test hooks over the worker's memory (every device / pinned block a model owns goes through two counted allocators,
+ * csrc/ifa_buf_hip.h).  Process-global; the countdown is not meant for concurrent use.
+ * ifa_debug_alloc_fail_at: the nth such allocation from now on reports out of memory, once, without calling HIP (its message
+ *   contains "simulated"); 0 disarms.
+ * ifa_debug_live_allocs: the blocks (and their bytes) handed out and not yet freed; either pointer may be null.  The process-level
+ *   caches of the GEMM / attention / runtime units are not counted. */
+int ifa_debug_alloc_fail_at(long long nth);
+int ifa_debug_live_allocs(long long *count, long long *bytes);
 /* run the worker on a caller-owned stream (e.g. the one the caller's RCCL collectives are ordered on) */
 int ifa_model_set_stream(ifa_model *m, ifa_stream stream);
 

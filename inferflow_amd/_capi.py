@@ -101,6 +101,8 @@ SIGNATURES = {
     "ifa_logit_state_add": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "ifa_model_create": (_i, [_vp, C.POINTER(_vp)]),
     "ifa_model_destroy": (_i, [_vp]),
+    "ifa_debug_alloc_fail_at": (_i, [C.c_longlong]),
+    "ifa_debug_live_allocs": (_i, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "ifa_model_set_tensor": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _sz]),
     "ifa_model_set_tensor_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _sz]),
     "ifa_model_finalize": (_i, [_vp]),

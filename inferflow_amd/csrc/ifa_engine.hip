@@ -1,6 +1,70 @@
 // ifa_engine.hip -- per-device decode worker, model life cycle (see ifa_engine_state.h for the layout of the worker's units):
 // tensors in (reference layout + the re-tiled / MFMA-operand-order copies), KV caches and query slots, options, debug buffers.
+#include <mutex>
+#include <unordered_map>
 #include "ifa_engine_state.h"
+
+// ------------------------------------------------ the two memory spaces of the worker's buffers (ifa_buf_hip.h)
+namespace ifa {
+
+namespace {
+struct SpaceBook {
+    std::mutex mu;
+    std::unordered_map<void *, size_t> live;      // what the two spaces have handed out and not taken back
+    long long live_bytes = 0, fail_at = 0;        // fail_at: the n-th allocation from now fails once (ifa_debug_alloc_fail_at; 0: off)
+};
+SpaceBook &book() { static SpaceBook *b = new SpaceBook(); return *b; }      // (never destroyed: buffers may go at process exit)
+
+template <class Alloc> int space_alloc(const char *call, void **p, size_t bytes, Alloc alloc)
+{
+    SpaceBook &b = book();
+    *p = nullptr;
+    {
+        std::lock_guard<std::mutex> g(b.mu);
+        if (b.fail_at > 0 && --b.fail_at == 0)
+            return ifa_fail(IFA_ERR_HIP, "%s(%zu bytes) failed: out of memory (simulated: ifa_debug_alloc_fail_at)", call, bytes);
+    }
+    const hipError_t e = alloc(p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return ifa_fail(IFA_ERR_HIP, "%s(%zu bytes) failed: %s", call, bytes, hipGetErrorString(e));
+    }
+    if (*p) { std::lock_guard<std::mutex> g(b.mu); b.live[*p] = bytes; b.live_bytes += (long long)bytes; }
+    return IFA_OK;
+}
+
+void space_forget(void *p)
+{
+    SpaceBook &b = book();
+    std::lock_guard<std::mutex> g(b.mu);
+    auto it = b.live.find(p);
+    if (it != b.live.end()) { b.live_bytes -= (long long)it->second; b.live.erase(it); }
+}
+} // namespace
+
+int DevSpace::alloc(void **p, size_t bytes) { return space_alloc("hipMalloc", p, bytes, [](void **q, size_t n) { return hipMalloc(q, n); }); }
+void DevSpace::free(void *p) { space_forget(p); (void)hipFree(p); }
+int PinSpace::alloc(void **p, size_t bytes) { return space_alloc("hipHostMalloc", p, bytes, [](void **q, size_t n) { return hipHostMalloc(q, n, hipHostMallocDefault); }); }
+void PinSpace::free(void *p) { space_forget(p); (void)hipHostFree(p); }
+
+} // namespace ifa
+
+extern "C" int ifa_debug_alloc_fail_at(long long nth)
+{
+    IFA_REQUIRE(nth >= 0, "ifa_debug_alloc_fail_at: nth %lld", nth);
+    std::lock_guard<std::mutex> g(book().mu);
+    book().fail_at = nth;
+    return IFA_OK;
+}
+
+extern "C" int ifa_debug_live_allocs(long long *count, long long *bytes)
+{
+    std::lock_guard<std::mutex> g(book().mu);
+    if (count) *count = (long long)book().live.size();
+    if (bytes) *bytes = book().live_bytes;
+    return IFA_OK;
+}
 
 namespace ifae {
 
@@ -61,74 +125,51 @@ void drop_graphs(ifa_model *m)
     m->draft_graphs.clear();
 }
 
-void free_tensor(Tensor &t)
-{
-    if (t.data) (void)hipFree(t.data);
-    if (t.tiled) (void)hipFree(t.tiled);
-    if (t.mo) (void)hipFree(t.mo);
-    if (t.x32) (void)hipFree(t.x32);
-    if (t.q3hn) (void)hipFree(t.q3hn);
-    t = Tensor();
-}
-
 // ------------------------------------------------ op-by-op forward (any T)
+// All or nothing: the new set is built aside and installed only when every allocation has succeeded; a failure leaves the model as
+// it was (old buffers, old scratch_tokens, captured steps valid).  The transient peak is the old set plus the new one.
 int ensure_scratch(ifa_model *m, int T)
 {
     if (T <= m->scratch_tokens) return IFA_OK;
     const ifa_model_config &c = m->cfg;
-    auto re = [&](half_t *&p, size_t n) -> int {
-        if (p) IFA_HIP_CHECK(hipFree(p));
-        p = nullptr;
-        IFA_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(half_t)));
-        return IFA_OK;
-    };
     const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim, F = c.ffn;
     size_t maxcols = std::max(std::max(D, QD), F);
+    Scratch n;
     int rc;
-    if ((rc = re(m->x, T * D)) || (rc = re(m->x2, T * D)) || (rc = re(m->xn, T * D)) || (rc = re(m->hn, T * D)) || (rc = re(m->pn, T * D))
-        || (rc = re(m->q, T * QD)) || (rc = re(m->k, T * KVD)) || (rc = re(m->v, T * KVD)) || (rc = re(m->att, T * QD))
-        || (rc = re(m->a, T * D)) || (rc = re(m->f, T * D)) || (rc = re(m->t1, std::max<size_t>(T, 3) * F)) || (rc = re(m->t2, T * F))
-        || (rc = re(m->logits, (size_t)T * c.vocab)))
+    if ((rc = n.x.alloc(T * D)) || (rc = n.x2.alloc(T * D)) || (rc = n.xn.alloc(T * D)) || (rc = n.hn.alloc(T * D)) || (rc = n.pn.alloc(T * D))
+        || (rc = n.q.alloc(T * QD)) || (rc = n.k.alloc(T * KVD)) || (rc = n.v.alloc(T * KVD)) || (rc = n.att.alloc(T * QD))
+        || (rc = n.a.alloc(T * D)) || (rc = n.f.alloc(T * D)) || (rc = n.t1.alloc(std::max<size_t>(T, 3) * F)) || (rc = n.t2.alloc(T * F))
+        || (rc = n.logits.alloc((size_t)T * c.vocab)))
         return rc;
-    if (!m->dqkv) IFA_HIP_CHECK(hipMalloc((void **)&m->dqkv, (QD + 2 * KVD) * sizeof(half_t)));
-    if (T <= 32 && (size_t)T > m->bqkv_rows) {
-        if (m->bqkv) IFA_HIP_CHECK(hipFree(m->bqkv));
-        if (m->brope) IFA_HIP_CHECK(hipFree(m->brope));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->bqkv, 32 * (QD + 2 * KVD) * sizeof(half_t)));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->brope, 32 * (size_t)c.head_dim * sizeof(float)));
-        m->bqkv_rows = 32;
-    }
+    if (!m->dqkv && (rc = n.dqkv.alloc(QD + 2 * KVD))) return rc;
+    if (T <= 32 && !m->bqkv && ((rc = n.bqkv.alloc(32 * (QD + 2 * KVD))) || (rc = n.brope.alloc(32 * (size_t)c.head_dim)))) return rc;
     if (c.experts > 0) {
         const size_t cap = (size_t)T * (size_t)std::max(1, c.moe_top_k);
-        if ((rc = re(m->moe_gate, (size_t)T * c.experts)) || (rc = re(m->moe_out, (size_t)T * D)) || (rc = re(m->moe_in, (size_t)T * D))
-            || (rc = re(m->moe_wdev, cap)))
+        if ((rc = n.moe_gate.alloc((size_t)T * c.experts)) || (rc = n.moe_out.alloc((size_t)T * D)) || (rc = n.moe_in.alloc((size_t)T * D))
+            || (rc = n.moe_wdev.alloc(cap)) || (rc = n.moe_idx.alloc(cap)) || (rc = n.moe_pin.alloc(cap * (sizeof(int) + 2) + 16)))
             return rc;
-        if (m->moe_idx) IFA_HIP_CHECK(hipFree(m->moe_idx));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->moe_idx, cap * sizeof(int)));
-        if (m->moe_pin) IFA_HIP_CHECK(hipHostFree(m->moe_pin));
-        IFA_HIP_CHECK(hipHostMalloc((void **)&m->moe_pin, cap * (sizeof(int) + 2) + 16, hipHostMallocDefault));
-        if (!m->moe_route) { IFA_HIP_CHECK(hipMalloc((void **)&m->moe_route, 64)); IFA_HIP_CHECK(hipMemsetAsync(m->moe_route, 0, 64, m->stream)); }
+        if (!m->moe_route) {
+            if ((rc = n.moe_route.alloc(64 / sizeof(int)))) return rc;
+            IFA_HIP_CHECK(hipMemsetAsync(n.moe_route, 0, 64, m->stream));
+        }
         // device-routed path: every expert's rows at once (cap entries)
-        void **raw[] = {(void **)&m->moe_sel, (void **)&m->moe_epos, (void **)&m->moe_counts, (void **)&m->moe_xq_in, (void **)&m->moe_xq_mid,
-                        &m->moe_tiles, &m->moe_singles, &m->moe_smalls};
-        for (void **p : raw) if (*p) { IFA_HIP_CHECK(hipFree(*p)); *p = nullptr; }
-        IFA_HIP_CHECK(hipMalloc((void **)&m->moe_sel, cap * sizeof(int)));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->moe_epos, cap * sizeof(int)));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->moe_counts, 16 * sizeof(int)));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->moe_xq_in, cap * (D / 32 + 1) * 34));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->moe_xq_mid, cap * (F / 32 + 1) * 34));
-        IFA_HIP_CHECK(hipMalloc(&m->moe_tiles, (cap / 64 + (size_t)c.experts + 1) * sizeof(MoeTile)));
-        IFA_HIP_CHECK(hipMalloc(&m->moe_singles, ((size_t)c.experts + 1) * sizeof(MoeSingle)));
-        IFA_HIP_CHECK(hipMalloc(&m->moe_smalls, ((size_t)c.experts + 1) * sizeof(MoeTile)));
-        if ((rc = re(m->moe_selw, cap)) || (rc = re(m->moe_g1, cap * F)) || (rc = re(m->moe_g3, cap * F)) || (rc = re(m->moe_gin, cap * D))
-            || (rc = re(m->moe_gout, cap * D)))
+        if ((rc = n.moe_sel.alloc(cap)) || (rc = n.moe_epos.alloc(cap)) || (rc = n.moe_counts.alloc(16))
+            || (rc = n.moe_xq_in.alloc(cap * (D / 32 + 1) * 34)) || (rc = n.moe_xq_mid.alloc(cap * (F / 32 + 1) * 34))
+            || (rc = n.moe_tiles.alloc((cap / 64 + (size_t)c.experts + 1) * sizeof(MoeTile)))
+            || (rc = n.moe_singles.alloc(((size_t)c.experts + 1) * sizeof(MoeSingle))) || (rc = n.moe_smalls.alloc(((size_t)c.experts + 1) * sizeof(MoeTile)))
+            || (rc = n.moe_selw.alloc(cap)) || (rc = n.moe_g1.alloc(cap * F)) || (rc = n.moe_g3.alloc(cap * F)) || (rc = n.moe_gin.alloc(cap * D))
+            || (rc = n.moe_gout.alloc(cap * D)))
             return rc;
     }
-    if (m->xq) IFA_HIP_CHECK(hipFree(m->xq));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->xq, (maxcols / 32 + 1) * 34));
-    if (!m->attq) IFA_HIP_CHECK(hipMalloc((void **)&m->attq, xq_image_bytes(c.heads * c.head_dim)));
-    if (m->tokens_dev) IFA_HIP_CHECK(hipFree(m->tokens_dev));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tokens_dev, sizeof(int) * (size_t)T));
+    if ((rc = n.xq.alloc((maxcols / 32 + 1) * 34))) return rc;
+    if (!m->attq && (rc = n.attq.alloc(xq_image_bytes(c.heads * c.head_dim)))) return rc;
+    if ((rc = n.tokens_dev.alloc((size_t)T))) return rc;
+    // commit (nothing below fails): what did not grow keeps its block -- captured steps and moe_route's zeroes live at those addresses
+    if (!n.dqkv) n.dqkv = std::move(m->dqkv);
+    if (!n.bqkv) { n.bqkv = std::move(m->bqkv); n.brope = std::move(m->brope); }
+    if (!n.moe_route) n.moe_route = std::move(m->moe_route);
+    if (!n.attq) n.attq = std::move(m->attq);
+    static_cast<Scratch &>(*m) = std::move(n);
     m->scratch_tokens = T;
     // buffers moved: any captured graph is stale
     drop_graphs(m);
@@ -152,9 +193,9 @@ int ensure_mo(ifa_model *m)
     if (rc == IFA_OK) return IFA_OK;
     (void)hipGetLastError();
     for (Layer &L : m->layers) {
-        for (Tensor &t : L.t) if (t.mo) { (void)hipFree(t.mo); t.mo = nullptr; }
-        for (Tensor &t : L.experts) if (t.mo) { (void)hipFree(t.mo); t.mo = nullptr; }
-        if (L.moe_table_mo) { (void)hipFree(L.moe_table_mo); L.moe_table_mo = nullptr; }
+        for (Tensor &t : L.t) t.mo.reset();
+        for (Tensor &t : L.experts) t.mo.reset();
+        L.moe_table_mo.reset();
     }
     m->opt_rows_mo = 0;
     drop_graphs(m);
@@ -174,8 +215,9 @@ int ensure_mo_build(ifa_model *m)
             if (moe && (id == T_W1 || id == T_W3 || id == T_W2)) continue;
             if (t.mo || !t.present() || !t.tiled || !rows_mo_fmt(t.dtype) || t.cols % 128 != 0) continue;
             if (m->opt_debug_mo_alloc_fail && built) return ifa_fail(IFA_ERR_HIP, "hipMalloc: out of memory (simulated: debug_mo_alloc_fail)");
-            IFA_HIP_CHECK(hipMalloc(&t.mo, gemm_rows_mo_bytes(t.rows, t.cols)));
-            int rc = gemm_rows_mo_build(t.dtype, t.tiled, t.rows, t.cols, t.mo, m->stream);
+            int rc = t.mo.alloc(gemm_rows_mo_bytes(t.rows, t.cols));
+            if (rc) return rc;
+            rc = gemm_rows_mo_build(t.dtype, t.tiled, t.rows, t.cols, t.mo, m->stream);
             if (rc) return rc;
             built = true;
         }
@@ -193,15 +235,16 @@ int ensure_mo_build(ifa_model *m)
             for (int k = 0; k < 3; k++) {
                 Tensor &t = L.experts[(size_t)e * 3 + order[k]];
                 if (!t.mo) {
-                    IFA_HIP_CHECK(hipMalloc(&t.mo, gemm_rows_mo_bytes(t.rows, t.cols)));
-                    int rc = gemm_rows_mo_build(t.dtype, t.tiled, t.rows, t.cols, t.mo, m->stream);
+                    int rc = t.mo.alloc(gemm_rows_mo_bytes(t.rows, t.cols));
+                    if (rc) return rc;
+                    rc = gemm_rows_mo_build(t.dtype, t.tiled, t.rows, t.cols, t.mo, m->stream);
                     if (rc) return rc;
                     built = true;
                 }
                 tab[(size_t)e * 4 + k] = t.mo;
             }
         }
-        IFA_HIP_CHECK(hipMalloc(&L.moe_table_mo, tab.size() * sizeof(void *)));
+        { int rc = L.moe_table_mo.alloc(tab.size()); if (rc) return rc; }
         IFA_HIP_CHECK(hipMemcpy(L.moe_table_mo, tab.data(), tab.size() * sizeof(void *), hipMemcpyHostToDevice));
     }
     if (built) IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -217,8 +260,9 @@ int ensure_x32(ifa_model *m)
         for (int id : ids) {
             Tensor &t = L.t[id];
             if (t.x32 || !t.present() || !t.tiled || (t.dtype != Q4_B64T1 && t.dtype != Q3H_B64T1) || t.cols % 64 != 0) continue;
-            IFA_HIP_CHECK(hipMalloc(&t.x32, t.rows * (t.cols / 32) * 20));
-            int rc = expand_b64_to_q4b32(t.dtype, t.tiled, t.rows, t.cols, t.x32, m->stream);
+            int rc = t.x32.alloc(t.rows * (t.cols / 32) * 20);
+            if (rc) return rc;
+            rc = expand_b64_to_q4b32(t.dtype, t.tiled, t.rows, t.cols, t.x32, m->stream);
             if (rc) return rc;
             built = true;
         }
@@ -237,8 +281,9 @@ int ensure_q3hn(ifa_model *m)
         for (int id : ids) {
             Tensor &t = L.t[id];
             if (t.q3hn || !t.present() || t.dtype != Q3H_B64T1 || t.cols % 64 != 0) continue;
-            IFA_HIP_CHECK(hipMalloc(&t.q3hn, t.rows * (t.cols / 64) * 32));
-            int rc = q3h_native_rows(t.data, t.rows, t.cols, t.q3hn, m->stream);
+            int rc = t.q3hn.alloc(t.rows * (t.cols / 64) * 32);
+            if (rc) return rc;
+            rc = q3h_native_rows(t.data, t.rows, t.cols, t.q3hn, m->stream);
             if (rc) return rc;
             built = true;
         }
@@ -281,62 +326,16 @@ int ifa_model_destroy(ifa_model *m)
     (void)hipSetDevice(m->cfg.device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     drop_graphs(m);
-    for (auto &sl : m->slots) {
-        for (void *p : sl.k) if (p) (void)hipFree(p);
-        for (void *p : sl.v) if (p) (void)hipFree(p);
-    }
-    for (Layer &L : m->layers) {
-        for (Tensor &t : L.t) free_tensor(t);
-        for (Tensor &t : L.experts) free_tensor(t);
-        if (L.moe_table) (void)hipFree(L.moe_table);
-        if (L.moe_table_aos) (void)hipFree(L.moe_table_aos);
-        if (L.moe_table_mo) (void)hipFree(L.moe_table_mo);
-        if (L.kcache) (void)hipFree(L.kcache);
-        if (L.vcache) (void)hipFree(L.vcache);
-    }
-    if (m->batch_tab_dev) (void)hipFree(m->batch_tab_dev);
-    if (m->batch_tab_pin) (void)hipHostFree(m->batch_tab_pin);
-    if (m->attn_ws.S) (void)hipFree(m->attn_ws.S);
-    if (m->attn_ws.lmax) (void)hipFree(m->attn_ws.lmax);
-    if (m->attn_ws.opart) (void)hipFree(m->attn_ws.opart);
-    for (Tensor &t : m->g) free_tensor(t);
-    half_t **bufs[] = {&m->x, &m->x2, &m->xn, &m->hn, &m->pn, &m->q, &m->k, &m->v, &m->dqkv, &m->bqkv, &m->att, &m->a, &m->f, &m->t1, &m->t2, &m->logits,
-                       &m->moe_gate, &m->moe_out, &m->moe_in, &m->moe_wdev};
-    for (half_t **b : bufs) if (*b) (void)hipFree(*b);
-    if (m->moe_idx) (void)hipFree(m->moe_idx);
-    if (m->moe_route) (void)hipFree(m->moe_route);
-    if (m->moe_pin) (void)hipHostFree(m->moe_pin);
-    if (m->trace) (void)hipFree(m->trace);
-    if (m->xq) (void)hipFree(m->xq);
-    if (m->attq) (void)hipFree(m->attq);
-    { void *mb[] = {m->moe_sel, m->moe_epos, m->moe_counts, m->moe_selw, m->moe_g1, m->moe_g3, m->moe_gin, m->moe_gout, m->moe_xq_in,
-                    m->moe_xq_mid, m->moe_tiles, m->moe_singles, m->moe_smalls};
-      for (void *b : mb) if (b) (void)hipFree(b); }
-    { void *tpb[] = {m->tp_a, m->tp_f, m->tp_hid, m->tp_logits, m->tp_best, m->tp_gather, m->tp_tok};
-      for (void *b : tpb) if (b) (void)hipFree(b); }
-    if (m->state) (void)hipFree(m->state);
-    if (m->rope_tab) (void)hipFree(m->rope_tab);
-    if (m->exact_rope_tab) (void)hipFree(m->exact_rope_tab);
-    if (m->tokens_dev) (void)hipFree(m->tokens_dev);
-    if (m->host_pinned) (void)hipHostFree(m->host_pinned);
-    if (m->qa_gran) (void)hipFree(m->qa_gran);
-    if (m->ch_gran) (void)hipFree(m->ch_gran);
-    if (m->ch_flags) (void)hipFree(m->ch_flags);
-    if (m->qa_call) (void)hipFree(m->qa_call);
-    if (m->qa_err) (void)hipFree(m->qa_err);
-    if (m->st_keys) (void)hipFree(m->st_keys);
-    if (m->st_counter) (void)hipFree(m->st_counter);
-    pool_free(m);
-    score_free(m);
-    kv_copy_free(m);
     if (m->stream) (void)ifa_gemm_release_stream((ifa_stream)m->stream);
-    if (m->stream && m->own_stream) (void)hipStreamDestroy(m->stream);
-    if (m->side_stream) (void)hipStreamDestroy(m->side_stream);
-    if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
-    if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    for (auto &r : m->perf_spans) { (void)hipEventDestroy(r.e0); (void)hipEventDestroy(r.e1); }
-    for (hipEvent_t e : m->perf_pool) (void)hipEventDestroy(e);
+    // every buffer goes with its owner, on the current device and behind the synchronisation above; then what has no owner
+    const hipStream_t stream = m->own_stream ? m->stream : nullptr, side = m->side_stream;
+    std::vector<hipEvent_t> events;
+    events.swap(m->perf_pool);
+    for (auto &r : m->perf_spans) { events.push_back(r.e0); events.push_back(r.e1); }
     delete m;
+    if (stream) (void)hipStreamDestroy(stream);
+    if (side) (void)hipStreamDestroy(side);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
     return IFA_OK;
 }
 
@@ -390,22 +389,20 @@ int ifa_model_set_tensor(ifa_model *m, int layer, int tensor_id, int expert, int
             t = &L.experts[(size_t)expert * 3 + (tensor_id == T_W1 ? 0 : (tensor_id == T_W2 ? 1 : 2))];
         } else t = &L.t[tensor_id];
     }
-    free_tensor(*t);
-    if (expert >= 0) {      // the layer's table of MO copies points into the copy just freed: ensure_mo rebuilds it
-        Layer &Lx = m->layers[(size_t)layer];
-        if (Lx.moe_table_mo) { (void)hipFree(Lx.moe_table_mo); Lx.moe_table_mo = nullptr; }
-    }
+    *t = Tensor();
+    if (expert >= 0) m->layers[(size_t)layer].moe_table_mo.reset();      // it points into the copy just freed: ensure_mo rebuilds it
     // load time: the source may have been produced on another stream (e.g. the caller's default stream)
     IFA_HIP_CHECK(hipDeviceSynchronize());
     const size_t bytes = rows * ifa_row_bytes(dtype, cols);
-    IFA_HIP_CHECK(hipMalloc(&t->data, bytes));
+    int rc = t->data.alloc(bytes);
+    if (rc) return rc;
     IFA_HIP_CHECK(hipMemcpyAsync(t->data, dev_src, bytes, hipMemcpyDeviceToDevice, m->stream));
     t->dtype = dtype; t->rows = rows; t->cols = cols;
     const bool is_matrix = (layer < 0 && tensor_id == T_LM_HEAD) || tensor_id == T_WQ || tensor_id == T_WK || tensor_id == T_WV || tensor_id == T_WO
         || tensor_id == T_W1 || tensor_id == T_W2 || tensor_id == T_W3;
     if (is_matrix && ax8_eligible(dtype)) {
-        IFA_HIP_CHECK(hipMalloc(&t->tiled, rows * ifa_tiled_row_bytes(dtype, cols)));
-        int rc = ifa_repack_weights(dtype, t->data, rows, cols, t->tiled, m->stream);
+        if ((rc = t->tiled.alloc(rows * ifa_tiled_row_bytes(dtype, cols)))) return rc;
+        rc = ifa_repack_weights(dtype, t->data, rows, cols, t->tiled, m->stream);
         if (rc) return rc;
     }
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -419,15 +416,15 @@ int ifa_model_set_tensor_f16(ifa_model *m, int layer, int tensor_id, int expert,
     IFA_REQUIRE(m && dev_src_f16, "ifa_model_set_tensor_f16: null pointer");
     if (target_dtype == F16) return ifa_model_set_tensor(m, layer, tensor_id, expert, F16, dev_src_f16, rows, cols);
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
-    void *tmp = nullptr;
+    DevBuf<void> tmp;
     const size_t bytes = rows * ifa_row_bytes(target_dtype, cols);
     IFA_REQUIRE(bytes > 0, "ifa_model_set_tensor_f16: dtype %d", target_dtype);
-    IFA_HIP_CHECK(hipMalloc(&tmp, bytes));
+    int rc = tmp.alloc(bytes);
+    if (rc) return rc;
     IFA_HIP_CHECK(hipDeviceSynchronize());   // source may come from another stream
-    int rc = ifa_quantize(target_dtype, dev_src_f16, rows, cols, tmp, m->stream);   // DeviceTensorBuilder::Build_Quant
+    rc = ifa_quantize(target_dtype, dev_src_f16, rows, cols, tmp, m->stream);   // DeviceTensorBuilder::Build_Quant
     if (rc == IFA_OK) rc = ifa_model_set_tensor(m, layer, tensor_id, expert, target_dtype, tmp, rows, cols);
-    (void)hipStreamSynchronize(m->stream);
-    (void)hipFree(tmp);
+    (void)hipStreamSynchronize(m->stream);      // (tmp goes behind the copy out of it)
     return rc;
 }
 
@@ -440,12 +437,12 @@ int ifa_model_finalize(ifa_model *m)
     const size_t KVD = (size_t)c.kv_heads * c.head_dim;
     IFA_REQUIRE(c.kv_dtype != Q8_B32T2 || KVD % 32 == 0, "Q8 KV cache needs kv_dim %% 32 == 0");
     m->kv_row_bytes = ifa_row_bytes(c.kv_dtype, KVD);
+    int rc;
     for (Layer &L : m->layers) {
         if (!L.kcache) {   // KVCache::Init (kv_cache.cc:278-319): (kv_dim, max_ctx) per layer
             // (at least DEC_ATTN_MIN_ROWS rows are allocated: the fused attention kernel requests its first 256 rows unclamped)
             const size_t kv_alloc = m->kv_row_bytes * (size_t)std::max(c.max_ctx, DEC_ATTN_MIN_ROWS);
-            IFA_HIP_CHECK(hipMalloc(&L.kcache, kv_alloc));
-            IFA_HIP_CHECK(hipMalloc(&L.vcache, kv_alloc));
+            if ((rc = L.kcache.alloc(kv_alloc)) || (rc = L.vcache.alloc(kv_alloc))) return rc;
             IFA_HIP_CHECK(hipMemsetAsync(L.kcache, 0, kv_alloc, m->stream));
             IFA_HIP_CHECK(hipMemsetAsync(L.vcache, 0, kv_alloc, m->stream));
         }
@@ -456,27 +453,26 @@ int ifa_model_finalize(ifa_model *m)
                 tab[(size_t)e * 4 + 1] = L.experts[(size_t)e * 3 + 2].tiled;
                 tab[(size_t)e * 4 + 2] = L.experts[(size_t)e * 3 + 1].tiled;
             }
-            if (!L.moe_table) IFA_HIP_CHECK(hipMalloc(&L.moe_table, tab.size() * sizeof(void *)));
+            if (!L.moe_table && (rc = L.moe_table.alloc(tab.size()))) return rc;
             IFA_HIP_CHECK(hipMemcpy(L.moe_table, tab.data(), tab.size() * sizeof(void *), hipMemcpyHostToDevice));
             std::vector<void *> aos((size_t)c.experts * 3, nullptr);
             for (int e = 0; e < c.experts; e++) for (int k3 = 0; k3 < 3; k3++) aos[(size_t)e * 3 + k3] = L.experts[(size_t)e * 3 + k3].data;
-            if (!L.moe_table_aos) IFA_HIP_CHECK(hipMalloc(&L.moe_table_aos, aos.size() * sizeof(void *)));
+            if (!L.moe_table_aos && (rc = L.moe_table_aos.alloc(aos.size()))) return rc;
             IFA_HIP_CHECK(hipMemcpy(L.moe_table_aos, aos.data(), aos.size() * sizeof(void *), hipMemcpyHostToDevice));
         }
     }
     if (!m->attn_ws.S) {
-        IFA_HIP_CHECK(hipMalloc((void **)&m->attn_ws.S, (size_t)c.heads * c.max_ctx * 2 + 64));      // (+ 64: the last row is read in whole 16-byte pieces)
-        IFA_HIP_CHECK(hipMalloc((void **)&m->attn_ws.lmax, (size_t)c.heads * DEC_ATTN_MAX_SPLITS * 4));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->attn_ws.opart, (size_t)c.heads * DEC_ATTN_MAX_SPLITS * c.head_dim * 4));
+        if ((rc = m->attn_ws_S.alloc((size_t)c.heads * c.max_ctx + 32))      // (+ 64 bytes: the last row is read in whole 16-byte pieces)
+            || (rc = m->attn_ws_lmax.alloc((size_t)c.heads * DEC_ATTN_MAX_SPLITS))
+            || (rc = m->attn_ws_opart.alloc((size_t)c.heads * DEC_ATTN_MAX_SPLITS * c.head_dim))) return rc;
+        m->attn_ws.S = m->attn_ws_S; m->attn_ws.lmax = m->attn_ws_lmax; m->attn_ws.opart = m->attn_ws_opart;
     }
     if (!m->state) {
-        IFA_HIP_CHECK(hipMalloc((void **)&m->state, sizeof(int) * (8 + ifa_model::RING)));
+        if ((rc = m->state.alloc(8 + ifa_model::RING))) return rc;
         IFA_HIP_CHECK(hipMemsetAsync(m->state, 0, sizeof(int) * (8 + ifa_model::RING), m->stream));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->rope_tab, sizeof(float) * (size_t)c.head_dim));
-        IFA_HIP_CHECK(hipHostMalloc((void **)&m->host_pinned, sizeof(int) * (16 + ifa_model::RING), hipHostMallocDefault));
+        if ((rc = m->rope_tab.alloc((size_t)c.head_dim)) || (rc = m->host_pinned.alloc(16 + ifa_model::RING))) return rc;
     }
-    int rc = ensure_scratch(m, 1);
-    if (rc) return rc;
+    if ((rc = ensure_scratch(m, 1))) return rc;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     m->finalized = true;
     return IFA_OK;
@@ -503,14 +499,14 @@ int ifa_model_kv_slots(ifa_model *m, int n_slots)
     IFA_REQUIRE((int)m->slots.size() <= n_slots, "ifa_model_kv_slots: cannot shrink below %zu slots", m->slots.size());
     const size_t bytes = m->kv_row_bytes * (size_t)std::max(m->cfg.max_ctx, DEC_ATTN_MIN_ROWS);
     while ((int)m->slots.size() < n_slots) {
-        ifa_model::KvSlot sl;
+        ifa_model::KvSlot sl;      // pushed only when complete: a failure drops what it holds (behind the memsets: freeing waits for the device)
         for (size_t l = 0; l < m->layers.size(); l++) {
-            void *k = nullptr, *v = nullptr;
-            IFA_HIP_CHECK(hipMalloc(&k, bytes));
-            IFA_HIP_CHECK(hipMalloc(&v, bytes));
+            DevBuf<void> k, v;
+            int rc;
+            if ((rc = k.alloc(bytes)) || (rc = v.alloc(bytes))) return rc;
             IFA_HIP_CHECK(hipMemsetAsync(k, 0, bytes, m->stream));
             IFA_HIP_CHECK(hipMemsetAsync(v, 0, bytes, m->stream));
-            sl.k.push_back(k); sl.v.push_back(v);
+            sl.k.push_back(std::move(k)); sl.v.push_back(std::move(v));
         }
         m->slots.push_back(std::move(sl));
     }
@@ -529,11 +525,11 @@ int ifa_model_select_kv(ifa_model *m, int slot)
     if (m->tp_graph) { (void)hipGraphDestroy(m->tp_graph); m->tp_graph = nullptr; }
     ifa_model::KvSlot &out = m->slots[(size_t)m->cur_slot], &in = m->slots[(size_t)slot];
     out.k.clear(); out.v.clear();
-    for (Layer &L : m->layers) { out.k.push_back(L.kcache); out.v.push_back(L.vcache); }
+    for (Layer &L : m->layers) { out.k.push_back(std::move(L.kcache)); out.v.push_back(std::move(L.vcache)); }
     out.graph = m->graph; out.exec = m->graph_exec;
     if (m->graph_exec_n) { (void)hipGraphExecDestroy(m->graph_exec_n); m->graph_exec_n = nullptr; }      // (the multi-step replay is not kept per slot)
     if (m->graph_n) { (void)hipGraphDestroy(m->graph_n); m->graph_n = nullptr; }
-    for (size_t l = 0; l < m->layers.size(); l++) { m->layers[l].kcache = in.k[l]; m->layers[l].vcache = in.v[l]; }
+    for (size_t l = 0; l < m->layers.size(); l++) { m->layers[l].kcache = std::move(in.k[l]); m->layers[l].vcache = std::move(in.v[l]); }
     m->graph = in.graph; m->graph_exec = in.exec;
     in.k.clear(); in.v.clear(); in.graph = nullptr; in.exec = nullptr;
     m->cur_slot = slot;
@@ -605,7 +601,7 @@ int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr,
     const ifa_model_config &c = m->cfg;
     size_t b = 0; void *p = nullptr;
     if (!strcmp(name, "logits")) { p = m->logits; b = (size_t)c.vocab * 2; }
-    else if (!strcmp(name, "logits_adj")) { p = m->la_adj; b = m->la_adj_rows * (size_t)c.vocab * 2; }
+    else if (!strcmp(name, "logits_adj")) { p = m->la_adj; b = m->la_adj ? m->la_adj.cap() / m->g[T_LM_HEAD].rows * (size_t)c.vocab * 2 : 0; }
     else if (!strcmp(name, "tp_logits")) { p = m->tp_logits; b = m->tp_logits ? m->g[T_LM_HEAD].rows * 2 : 0; }
     else if (!strcmp(name, "trace")) { p = m->trace; b = m->trace ? sizeof(long long) * 2048 * 8 : 0; }
     else if (!strcmp(name, "hidden")) { p = m->xn; b = (size_t)c.dim * 2; }

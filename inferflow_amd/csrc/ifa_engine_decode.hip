@@ -204,14 +204,13 @@ int qkv_attn_ready(ifa_model *m)
     if (want && (long long)c.kv_heads * gk > (long long)visible_cus()) want = 0;
     if (want && !m->qa_gran) {
         const size_t n = (size_t)c.layers * (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim;
-        IFA_HIP_CHECK(hipMalloc((void **)&m->qa_gran, n * 8));
-        IFA_HIP_CHECK(hipMemsetAsync(m->qa_gran, 0, n * 8, m->stream));
-        if (m->qa_call) { (void)hipFree(m->qa_call); m->qa_call = nullptr; }
-        if (m->qa_err) { (void)hipFree(m->qa_err); m->qa_err = nullptr; }
-        IFA_HIP_CHECK(hipMalloc((void **)&m->qa_call, 16));
-        IFA_HIP_CHECK(hipMemsetAsync(m->qa_call, 0, 16, m->stream));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->qa_err, 16));
-        IFA_HIP_CHECK(hipMemsetAsync(m->qa_err, 0, 16, m->stream));
+        DevBuf<unsigned long long> gran; DevBuf<unsigned> call, err;      // installed together, zeroed
+        int rc;
+        if ((rc = gran.alloc(n)) || (rc = call.alloc(4)) || (rc = err.alloc(4))) return rc;
+        IFA_HIP_CHECK(hipMemsetAsync(gran, 0, n * 8, m->stream));
+        IFA_HIP_CHECK(hipMemsetAsync(call, 0, 16, m->stream));
+        IFA_HIP_CHECK(hipMemsetAsync(err, 0, 16, m->stream));
+        m->qa_gran = std::move(gran); m->qa_call = std::move(call); m->qa_err = std::move(err);
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     }
     // the chained FFN launch: dense gated FFN behind an RMS pre-norm, sequential wiring, W1 / W3 / W2 (and Wo) of one format with an
@@ -232,12 +231,16 @@ int qkv_attn_ready(ifa_model *m)
     }
     if (want_ch && !m->ch_gran) {
         const size_t n = (size_t)c.layers * (size_t)(c.dim + (int)m->layers[0].t[T_W1].rows);
-        IFA_HIP_CHECK(hipMalloc((void **)&m->ch_gran, n * 4));
-        IFA_HIP_CHECK(hipMemsetAsync(m->ch_gran, 0, n * 4, m->stream));
-        IFA_HIP_CHECK(hipMalloc((void **)&m->ch_flags, (size_t)c.layers * 2 * 1024 * 4));
-        IFA_HIP_CHECK(hipMemsetAsync(m->ch_flags, 0, (size_t)c.layers * 2 * 1024 * 4, m->stream));
-        if (!m->qa_call) { IFA_HIP_CHECK(hipMalloc((void **)&m->qa_call, 16)); IFA_HIP_CHECK(hipMemsetAsync(m->qa_call, 0, 16, m->stream)); }
-        if (!m->qa_err) { IFA_HIP_CHECK(hipMalloc((void **)&m->qa_err, 16)); IFA_HIP_CHECK(hipMemsetAsync(m->qa_err, 0, 16, m->stream)); }
+        DevBuf<uint32_t> gran, flags; DevBuf<unsigned> call, err;      // installed together, zeroed
+        int rc;
+        if ((rc = gran.alloc(n)) || (rc = flags.alloc((size_t)c.layers * 2 * 1024))) return rc;
+        IFA_HIP_CHECK(hipMemsetAsync(gran, 0, n * 4, m->stream));
+        IFA_HIP_CHECK(hipMemsetAsync(flags, 0, (size_t)c.layers * 2 * 1024 * 4, m->stream));
+        if (!m->qa_call) { if ((rc = call.alloc(4))) return rc; IFA_HIP_CHECK(hipMemsetAsync(call, 0, 16, m->stream)); }
+        if (!m->qa_err) { if ((rc = err.alloc(4))) return rc; IFA_HIP_CHECK(hipMemsetAsync(err, 0, 16, m->stream)); }
+        m->ch_gran = std::move(gran); m->ch_flags = std::move(flags);
+        if (call) m->qa_call = std::move(call);
+        if (err) m->qa_err = std::move(err);
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     }
     if (want != m->qa_on || (want && gk != m->qa_gk) || want_ch != m->ch_on) {
@@ -440,7 +443,7 @@ int launch_wo(ifa_model *m, int l, const half_t *x, half_t *partial)
     // register image (chunked kernel) keep the in-kernel quantiser
     const bool preq = m->attq && m->opt_attn_q8 && m->cfg.head_dim % 32 == 0 && P.cols == m->cfg.heads * m->cfg.head_dim && fused_int8(L.t[T_WO].dtype)
         && dec_gemv_supported(L.t[T_WO].dtype, (size_t)P.cols);
-    if (preq) P.x = reinterpret_cast<const half_t *>(m->attq);      // NORM == 2 kernels read the quantised image through P.x
+    if (preq) P.x = reinterpret_cast<const half_t *>(m->attq.get());      // NORM == 2 kernels read the quantised image through P.x
     const int dto = native_fmt(m, L.t[T_WO], P.W0[0]);
     if (partial) {
         P.y[0] = partial;
@@ -461,7 +464,7 @@ void moe_params(ifa_model *m, Layer &L, DecGemvParams &P, int slot, int tab_off)
 {
     P.w_table = (const uint8_t *const *)L.moe_table;
     P.moe_sel = m->moe_route;
-    P.moe_w = reinterpret_cast<const half_t *>(reinterpret_cast<const char *>(m->moe_route) + 32);
+    P.moe_w = reinterpret_cast<const half_t *>(reinterpret_cast<const char *>(m->moe_route.get()) + 32);
     P.moe_acc = m->f;
     P.moe_slot = slot; P.moe_tab_off = tab_off;
 }
@@ -555,7 +558,7 @@ int launch_chain(ifa_model *m, int l, const half_t *x, half_t *xnext, unsigned t
     const bool wo = m->ch_on == 2;
     DecGemvParams PW; memset(&PW, 0, sizeof(PW));       // launch_wo's EPI_RESIDUAL / NORM 2 parameters
     if (wo) {
-        PW.x = reinterpret_cast<const half_t *>(m->attq); PW.cols = (int)L.t[T_WO].cols; PW.eps = c.eps;
+        PW.x = reinterpret_cast<const half_t *>(m->attq.get()); PW.cols = (int)L.t[T_WO].cols; PW.eps = c.eps;
         PW.W0[0] = wbytes(L.t[T_WO]); PW.rows[0] = (int)L.t[T_WO].rows;
         PW.b0[0] = (const half_t *)L.t[T_WO_B].data; PW.y[0] = m->a; PW.residual = x;
         if (scale_on(c.attn_out_scale)) PW.pre_scale = c.attn_out_scale;
@@ -605,15 +608,13 @@ int step_tail_ready(ifa_model *m)
     if (want != m->st_on) { m->st_on = want; drop_graphs(m); }
     if (!want) return IFA_OK;
     const int grid = lmhead_grid(lm_params(m, m->x, nullptr), m->opt_rpw_lm);
-    if (grid > m->st_keys_n) {
+    int rc;
+    if ((size_t)grid > m->st_keys.cap()) {
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-        if (m->st_keys) (void)hipFree(m->st_keys);
-        m->st_keys = nullptr; m->st_keys_n = 0;
-        IFA_HIP_CHECK(hipMalloc((void **)&m->st_keys, sizeof(unsigned long long) * (size_t)grid));
-        m->st_keys_n = grid;
+        if ((rc = m->st_keys.alloc((size_t)grid))) return rc;
     }
     if (!m->st_counter) {
-        IFA_HIP_CHECK(hipMalloc((void **)&m->st_counter, 16));
+        if ((rc = m->st_counter.alloc(4))) return rc;
         IFA_HIP_CHECK(hipMemsetAsync(m->st_counter, 0, 16, m->stream));
     }
     return IFA_OK;
@@ -910,7 +911,7 @@ int ifa_model_time_kernel(ifa_model *m, int which, int iters, float *avg_us)
                                                (int)(m->cfg.head_dim * m->cfg.partial_rotary + 0.5f), m->cfg.embd_scale);
     for (int i = 0; i < 3; i++) if ((rc = one(i))) return rc;
     if (m->opt_trace) {
-        if (!m->trace) IFA_HIP_CHECK(hipMalloc((void **)&m->trace, sizeof(long long) * 2048 * 8));
+        if (!m->trace && (rc = m->trace.alloc(2048 * 8))) return rc;
         IFA_HIP_CHECK(hipMemsetAsync(m->trace, 0, sizeof(long long) * 2048 * 8, s));
         g_trace_ptr = m->trace;
     }

@@ -41,7 +41,7 @@ static int exact_rope_table(ifa_model *m)
             tab[((size_t)pos * half_hd + col) * 2] = cosf(ang);
             tab[((size_t)pos * half_hd + col) * 2 + 1] = sinf(ang);
         }
-    IFA_HIP_CHECK(hipMalloc((void **)&m->exact_rope_tab, tab.size() * sizeof(float)));
+    { int rc = m->exact_rope_tab.alloc(tab.size()); if (rc) return rc; }
     IFA_HIP_CHECK(hipMemcpy(m->exact_rope_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     return IFA_OK;
 }

@@ -606,15 +606,11 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     const bool merging = tp_merging(m);
     // per-step tables: positions, and for every layer the (k cache, v cache, context) of each row's query
     const size_t tab_bytes = L_ * (size_t)n * sizeof(AttnRowH) + 2 * (size_t)n * sizeof(int);
-    if (tab_bytes > m->batch_tab_bytes) {
+    if (tab_bytes > m->batch_tab.cap()) {
         drop_graphs(m);                            // the captured steps hold the old table addresses
-        if (m->batch_tab_dev) IFA_HIP_CHECK(hipFree(m->batch_tab_dev));
-        if (m->batch_tab_pin) IFA_HIP_CHECK(hipHostFree(m->batch_tab_pin));
-        IFA_HIP_CHECK(hipMalloc(&m->batch_tab_dev, tab_bytes));
-        IFA_HIP_CHECK(hipHostMalloc(&m->batch_tab_pin, tab_bytes, hipHostMallocDefault));
-        m->batch_tab_bytes = tab_bytes;
+        if ((rc = m->batch_tab.reserve(tab_bytes))) return rc;
     }
-    AttnRowH *rows_h = (AttnRowH *)m->batch_tab_pin;
+    AttnRowH *rows_h = (AttnRowH *)m->batch_tab.pin.get();
     int *pos_pin = (int *)(rows_h + L_ * (size_t)n);
     for (size_t l = 0; l < L_; l++)
         for (int r = 0; r < n; r++) {
@@ -622,7 +618,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
             a.kc = kv_ptr(m, l, slot_host[r], false); a.vc = kv_ptr(m, l, slot_host[r], true); a.n_ctx = pos_host[r] + 1; a.pad = 0;
         }
     for (int r = 0; r < n; r++) { pos_pin[r] = pos_host[r]; pos_pin[n + r] = tokens_host[r]; }
-    const AttnRowH *rows_d = (const AttnRowH *)m->batch_tab_dev;
+    const AttnRowH *rows_d = (const AttnRowH *)m->batch_tab.dev.get();
     const int *pos_d = (const int *)(rows_d + L_ * (size_t)n);
     const int *tok_d = pos_d + n;
     // Everything the device does in a step depends on the step only through the tables above (fixed addresses), so
@@ -659,7 +655,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
         IFA_HIP_CHECK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
     }
     auto body = [&]() -> int {
-    IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab_dev, m->batch_tab_pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
+    IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab.dev, m->batch_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
     if (fused)
         k_dec_batch_gather<<<dim3(4, (unsigned)T), dim3(256), 0, m->stream>>>((const half_t *)m->g[T_EMBD].data, tok_d, pos_d, (int)D, (int)m->g[T_EMBD].rows,
                                                                               m->x, c.rope_order ? m->brope : nullptr, c.head_dim, c.rope_theta,

@@ -178,7 +178,7 @@ int launch_moe_router(ifa_model *m, int l)
         k_dec_moe_router<<<1, 512, smem, m->stream>>>(m->a, has_norm ? (const half_t *)L.t[T_FFN_NORM].data : nullptr,
                                                       has_norm ? (const half_t *)L.t[T_FFN_NORM_B].data : nullptr, c.ffn_norm_base, has_norm ? c.eps : -1.0f,
                                                       c.dim, (const half_t *)gw.data, c.experts, c.moe_top_k, c.moe_norm_topk, m->hn, m->moe_gate, m->moe_route,
-                                                      reinterpret_cast<half_t *>(reinterpret_cast<char *>(m->moe_route) + 32), 0);
+                                                      reinterpret_cast<half_t *>(reinterpret_cast<char *>(m->moe_route.get()) + 32), 0);
         IFA_LAUNCH_CHECK();
         return IFA_OK;
     }
@@ -190,7 +190,7 @@ int launch_moe_router(ifa_model *m, int l)
     if ((rc = matmul(m, ff_n, 1, L.t[T_MOE_GATE], none, m->moe_gate))) return rc;
     if ((rc = ifa_softmax(m->moe_gate, c.experts, 1, 1, -1, 1.0f, (ifa_stream)m->stream))) return rc;
     k_moe_topk<<<1, 64, 0, m->stream>>>(m->moe_gate, c.experts, c.moe_top_k, c.moe_norm_topk, m->moe_route,
-                                        reinterpret_cast<half_t *>(reinterpret_cast<char *>(m->moe_route) + 32));
+                                        reinterpret_cast<half_t *>(reinterpret_cast<char *>(m->moe_route.get()) + 32));
     IFA_LAUNCH_CHECK();
     return IFA_OK;
 }
@@ -240,7 +240,7 @@ int moe_ffn(ifa_model *m, Layer &L, const half_t *ff_n, int T)
     }
     // one upload of every (row, weight) list, experts back to back
     const size_t cap = (size_t)T * (size_t)c.moe_top_k;
-    int *pin_rows = m->moe_pin; uint16_t *pin_w = reinterpret_cast<uint16_t *>(m->moe_pin + cap);
+    int *pin_rows = (int *)m->moe_pin.get(); uint16_t *pin_w = reinterpret_cast<uint16_t *>(pin_rows + cap);
     size_t off = 0;
     std::vector<size_t> start((size_t)E, 0);
     for (int e = 0; e < E; e++) {
@@ -291,8 +291,8 @@ int ensure_side_stream(ifa_model *m)
 {
     if (m->side_stream) return IFA_OK;
     IFA_HIP_CHECK(hipStreamCreateWithFlags(&m->side_stream, hipStreamNonBlocking));
-    IFA_HIP_CHECK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-    IFA_HIP_CHECK(hipEventCreateWithFlags(&m->ev_join, hipEventDisableTiming));
+    IFA_HIP_CHECK(hipEventCreateWithFlags(&m->ev_fork.e, hipEventDisableTiming));
+    IFA_HIP_CHECK(hipEventCreateWithFlags(&m->ev_join.e, hipEventDisableTiming));
     return IFA_OK;
 }
 

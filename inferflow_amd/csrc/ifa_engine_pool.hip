@@ -23,46 +23,15 @@ namespace ifae {
 // counts [n_sel] | (with_lse: lse [n_sel] |) ids [n_sel][k] | F16 bits [n_sel][k]
 static size_t pool_block_bytes(int n_sel, int k, bool with_lse) { return (size_t)n_sel * (with_lse ? 8 : 4) + (size_t)n_sel * (size_t)k * 6; }
 
-void pool_free(ifa_model *m)
-{
-    if (m->pool_excl) (void)hipFree(m->pool_excl);
-    if (m->pool_dev) (void)hipFree(m->pool_dev);
-    if (m->pool_pin) (void)hipHostFree(m->pool_pin);
-    if (m->pool_idx_dev) (void)hipFree(m->pool_idx_dev);
-    if (m->pool_idx_pin) (void)hipHostFree(m->pool_idx_pin);
-    m->pool_excl = nullptr; m->pool_dev = m->pool_pin = nullptr; m->pool_idx_dev = m->pool_idx_pin = nullptr;
-    m->pool_bytes = 0; m->pool_idx_cap = 0;
-    logit_adjust_free(m);
-}
-
-void logit_adjust_free(ifa_model *m)
-{
-    void *dev[] = {m->la_state, m->la_bias, m->la_params, m->la_adj, m->la_stage, m->la_reset_dev};
-    for (void *p : dev) if (p) (void)hipFree(p);
-    if (m->la_pin) (void)hipHostFree(m->la_pin);
-    if (m->la_reset_pin) (void)hipHostFree(m->la_reset_pin);
-    for (int i = 0; i < ifa_model::LA_RING; i++) if (m->la_ev[i]) { (void)hipEventDestroy(m->la_ev[i]); m->la_ev[i] = nullptr; m->la_ev_used[i] = false; }
-    m->la_state = nullptr; m->la_bias = m->la_params = nullptr; m->la_slots = 0;
-    m->la_adj = nullptr; m->la_adj_rows = 0;
-    m->la_pin = m->la_stage = m->la_reset_pin = m->la_reset_dev = nullptr; m->la_reset_cap = 0;
-    m->pool_adj_next.clear();
-}
-
 // state / bias / params for every KV slot the worker has now (first use, or more slots since: the old rows are kept)
 static int logit_state_reserve(ifa_model *m)
 {
     const size_t V = m->g[T_LM_HEAD].rows, want = std::max<size_t>(m->slots.size(), 1);
     if (want <= m->la_slots) return IFA_OK;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-    unsigned *st = nullptr; float *bs = nullptr, *pr = nullptr;
-    if (hipMalloc((void **)&st, want * V * sizeof(unsigned)) != hipSuccess || hipMalloc((void **)&bs, want * V * sizeof(float)) != hipSuccess
-        || hipMalloc((void **)&pr, want * 3 * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        if (st) (void)hipFree(st);
-        if (bs) (void)hipFree(bs);
-        if (pr) (void)hipFree(pr);
+    DevBuf<unsigned> st; DevBuf<float> bs, pr;
+    if (st.alloc(want * V) || bs.alloc(want * V) || pr.alloc(want * 3))
         return ifa_fail(IFA_ERR_NOMEM, "logit processors: no memory for the state of %zu slots x %zu ids", want, V);
-    }
     // a slot nobody has reset yet reads as neutral: no counts, no bias, {1, 0, 0}
     std::vector<float> neutral(want * 3, 0.0f);
     for (size_t i = 0; i < want; i++) neutral[i * 3] = 1.0f;
@@ -75,11 +44,8 @@ static int logit_state_reserve(ifa_model *m)
         if (e == hipSuccess) e = hipMemcpy(pr, m->la_params, m->la_slots * 3 * sizeof(float), hipMemcpyDeviceToDevice);
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(st); (void)hipFree(bs); (void)hipFree(pr); return ifa_fail(IFA_ERR_HIP, "logit processors: state setup failed: %s", hipGetErrorString(e)); }
-    if (m->la_state) (void)hipFree(m->la_state);
-    if (m->la_bias) (void)hipFree(m->la_bias);
-    if (m->la_params) (void)hipFree(m->la_params);
-    m->la_state = st; m->la_bias = bs; m->la_params = pr; m->la_slots = want;
+    if (e != hipSuccess) return ifa_fail(IFA_ERR_HIP, "logit processors: state setup failed: %s", hipGetErrorString(e));
+    m->la_state = std::move(st); m->la_bias = std::move(bs); m->la_params = std::move(pr); m->la_slots = want;
     return IFA_OK;
 }
 
@@ -90,29 +56,22 @@ static int logit_partitioned(const ifa_model *m, const char *who)
     return IFA_OK;
 }
 
+// rows the index block serves: its second half holds the state slots of the armed rows
+static size_t pool_idx_rows(const ifa_model *m) { return m->pool_idx.cap() / 2; }
+
 // staging for n_sel rows of k entries (grown on demand, outside any capture; one allocation serves every later step)
 static int pool_reserve(ifa_model *m, int n_sel, int k)
 {
     const size_t bytes = pool_block_bytes(std::max(n_sel, 8), IFA_POOL_MAX >= k ? IFA_POOL_MAX : k, true);
-    if (bytes > m->pool_bytes) {
+    int rc;
+    if (bytes > m->pool_blk.cap()) {
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-        if (m->pool_dev) (void)hipFree(m->pool_dev);
-        if (m->pool_pin) (void)hipHostFree(m->pool_pin);
-        m->pool_dev = m->pool_pin = nullptr; m->pool_bytes = 0;
-        IFA_HIP_CHECK(hipMalloc(&m->pool_dev, bytes));
-        IFA_HIP_CHECK(hipHostMalloc(&m->pool_pin, bytes, hipHostMallocDefault));
-        m->pool_bytes = bytes;
+        if ((rc = m->pool_blk.reserve(bytes))) return rc;
     }
-    if ((size_t)n_sel > m->pool_idx_cap) {
+    if ((size_t)n_sel > pool_idx_rows(m)) {
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-        if (m->pool_idx_dev) (void)hipFree(m->pool_idx_dev);
-        if (m->pool_idx_pin) (void)hipHostFree(m->pool_idx_pin);
-        m->pool_idx_dev = m->pool_idx_pin = nullptr; m->pool_idx_cap = 0;
-        const size_t cap = (size_t)std::max(n_sel, 64);
         // row indices [cap] | state slots of armed rows [cap] (logit processors)
-        IFA_HIP_CHECK(hipMalloc((void **)&m->pool_idx_dev, 2 * cap * sizeof(int)));
-        IFA_HIP_CHECK(hipHostMalloc((void **)&m->pool_idx_pin, 2 * cap * sizeof(int), hipHostMallocDefault));
-        m->pool_idx_cap = cap;
+        if ((rc = m->pool_idx.reserve(2 * (size_t)std::max(n_sel, 64)))) return rc;
     }
     return IFA_OK;
 }
@@ -124,7 +83,7 @@ static int pool_rows_launch(ifa_model *m, const half_t *logits, const int *idx, 
     ifa_model::PoolReq &R = m->pool;
     const size_t V = m->g[T_LM_HEAD].rows, rows = (size_t)(jb - ja);
     const int k = R.k, n_sel = R.n_sel;
-    int *counts = (int *)m->pool_dev;
+    int *counts = (int *)m->pool_blk.dev.get();
     float *lse = R.lse ? (float *)(counts + n_sel) : nullptr;
     int *ids = counts + (R.lse ? 2 : 1) * n_sel;
     uint16_t *vals = (uint16_t *)(ids + (size_t)n_sel * k);
@@ -132,7 +91,7 @@ static int pool_rows_launch(ifa_model *m, const half_t *logits, const int *idx, 
     const void *src = logits;
     if (armed) {
         half_t *adj = m->la_adj + (size_t)ja * V;
-        if ((rc = logit_adjust_rows(logits, V, idx, m->pool_idx_dev + m->pool_idx_cap + ja, rows, V, m->la_state, m->la_bias, m->la_params, adj, m->stream))) return rc;
+        if ((rc = logit_adjust_rows(logits, V, idx, m->pool_idx.dev + pool_idx_rows(m) + ja, rows, V, m->la_state, m->la_bias, m->la_params, adj, m->stream))) return rc;
         src = adj; idx = nullptr;
     }
     if ((rc = topk_pool_rows(src, V, idx, rows, V, k, m->pool_excl, ids + (size_t)ja * k, vals + (size_t)ja * k, counts + ja, m->stream))) return rc;
@@ -146,7 +105,7 @@ int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
     if (R.k <= 0) return IFA_OK;
     const int k = R.k, n_sel = R.n_sel;
     const bool adj = !R.adj.empty();
-    int *slot_pin = m->pool_idx_pin + m->pool_idx_cap, *slot_dev = m->pool_idx_dev + m->pool_idx_cap;
+    int *slot_pin = m->pool_idx.pin + pool_idx_rows(m), *slot_dev = m->pool_idx.dev + pool_idx_rows(m);
     int rc = IFA_OK;
     if (!R.rows_sel) {                 // a single-query step: its one row
         if (adj) {
@@ -159,10 +118,10 @@ int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
         int j0 = R.done, j1 = j0;
         while (j1 < n_sel && R.rows_sel[j1] < R.chunk0 + n_rows) j1++;
         if (j1 > j0) {
-            for (int j = j0; j < j1; j++) m->pool_idx_pin[j] = R.rows_sel[j] - R.chunk0;
-            IFA_HIP_CHECK(hipMemcpyAsync(m->pool_idx_dev + j0, m->pool_idx_pin + j0, sizeof(int) * (size_t)(j1 - j0), hipMemcpyHostToDevice, m->stream));
+            for (int j = j0; j < j1; j++) m->pool_idx.pin[j] = R.rows_sel[j] - R.chunk0;
+            IFA_HIP_CHECK(hipMemcpyAsync(m->pool_idx.dev + j0, m->pool_idx.pin + j0, sizeof(int) * (size_t)(j1 - j0), hipMemcpyHostToDevice, m->stream));
             if (!adj) {
-                if ((rc = pool_rows_launch(m, logits, m->pool_idx_dev + j0, j0, j1, false))) return rc;
+                if ((rc = pool_rows_launch(m, logits, m->pool_idx.dev + j0, j0, j1, false))) return rc;
             } else {                   // runs of armed / raw rows, each run its own launches (all armed, the usual case: one run)
                 for (int j = j0; j < j1; j++) slot_pin[j] = std::max(R.adj[(size_t)j], 0);
                 IFA_HIP_CHECK(hipMemcpyAsync(slot_dev + j0, slot_pin + j0, sizeof(int) * (size_t)(j1 - j0), hipMemcpyHostToDevice, m->stream));
@@ -170,7 +129,7 @@ int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
                     const bool armed = R.adj[(size_t)ja] >= 0;
                     int jb = ja + 1;
                     while (jb < j1 && (R.adj[(size_t)jb] >= 0) == armed) jb++;
-                    if ((rc = pool_rows_launch(m, logits, m->pool_idx_dev + ja, ja, jb, armed))) return rc;
+                    if ((rc = pool_rows_launch(m, logits, m->pool_idx.dev + ja, ja, jb, armed))) return rc;
                     ja = jb;
                 }
             }
@@ -178,7 +137,7 @@ int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
         R.done = j1;
         if (!R.last_chunk) return IFA_OK;
     }
-    IFA_HIP_CHECK(hipMemcpyAsync(m->pool_pin, m->pool_dev, pool_block_bytes(n_sel, k, R.lse), hipMemcpyDeviceToHost, m->stream));
+    IFA_HIP_CHECK(hipMemcpyAsync(m->pool_blk.pin, m->pool_blk.dev, pool_block_bytes(n_sel, k, R.lse), hipMemcpyDeviceToHost, m->stream));
     return IFA_OK;
 }
 
@@ -205,13 +164,10 @@ static int pool_arm(ifa_model *m, int k, int n_sel, const int *rows_sel, const c
         const size_t V = m->g[T_LM_HEAD].rows;
         for (int s : adj)
             if (s >= 0 && (size_t)s >= m->la_slots) { m->pool = ifa_model::PoolReq(); return ifa_fail(IFA_ERR_STATE, "%s: state slot %d has no logit state (ifa_model_logit_state_reset first)", who, s); }
-        if ((size_t)n_sel > m->la_adj_rows) {
+        if ((size_t)n_sel * V > m->la_adj.cap()) {
             IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-            if (m->la_adj) (void)hipFree(m->la_adj);
-            m->la_adj = nullptr; m->la_adj_rows = 0;
             const size_t rows = (size_t)std::max(n_sel, 8);
-            if (hipMalloc((void **)&m->la_adj, rows * V * sizeof(half_t)) != hipSuccess) { (void)hipGetLastError(); m->pool = ifa_model::PoolReq(); return ifa_fail(IFA_ERR_NOMEM, "%s: no memory for %zu adjusted rows", who, rows); }
-            m->la_adj_rows = rows;
+            if (m->la_adj.alloc(rows * V)) { m->pool = ifa_model::PoolReq(); return ifa_fail(IFA_ERR_NOMEM, "%s: no memory for %zu adjusted rows", who, rows); }
         }
         m->pool.adj.swap(adj);
     }
@@ -228,7 +184,7 @@ static int pool_finish(ifa_model *m, int step_rc, int *ids_host, unsigned short 
     m->pool = ifa_model::PoolReq();
     if (step_rc) return step_rc;
     if (R.done != R.n_sel) return ifa_fail(IFA_ERR_STATE, "%s: the step served %d of %d pools", who, R.done, R.n_sel);
-    const int *counts = (const int *)m->pool_pin, *ids = counts + (R.lse ? 2 : 1) * R.n_sel;
+    const int *counts = (const int *)m->pool_blk.pin.get(), *ids = counts + (R.lse ? 2 : 1) * R.n_sel;
     if (R.lse) m->pool_lse_last.assign((const float *)(counts + R.n_sel), (const float *)(counts + R.n_sel) + R.n_sel);
     const uint16_t *vals = (const uint16_t *)(ids + (size_t)R.n_sel * R.k);
     memcpy(counts_host, counts, sizeof(int) * (size_t)R.n_sel);
@@ -250,14 +206,10 @@ int ifa_model_set_pool_excluded(ifa_model *m, const int *ids_host, int n)
     for (int i = 0; i < n; i++) IFA_REQUIRE(ids_host[i] >= 0 && (size_t)ids_host[i] < V, "ifa_model_set_pool_excluded: id %d outside the vocabulary", ids_host[i]);
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-    if (n == 0) {
-        if (m->pool_excl) (void)hipFree(m->pool_excl);
-        m->pool_excl = nullptr;
-        return IFA_OK;
-    }
+    if (n == 0) { m->pool_excl.reset(); return IFA_OK; }
     std::vector<unsigned> bits(words, 0u);
     for (int i = 0; i < n; i++) bits[(size_t)ids_host[i] >> 5] |= 1u << (ids_host[i] & 31);
-    if (!m->pool_excl) IFA_HIP_CHECK(hipMalloc((void **)&m->pool_excl, words * sizeof(unsigned)));
+    if (!m->pool_excl) { int rc = m->pool_excl.alloc(words); if (rc) return rc; }
     IFA_HIP_CHECK(hipMemcpy(m->pool_excl, bits.data(), words * sizeof(unsigned), hipMemcpyHostToDevice));
     return IFA_OK;
 }
@@ -289,23 +241,18 @@ int ifa_model_logit_state_reset(ifa_model *m, int kv_slot, const int *prompt_hos
     if ((rc = logit_state_reserve(m))) return rc;
     // staging: prompt [n_prompt] | bias ids [n_bias] | bias values [n_bias]
     const size_t need = (size_t)n_prompt + 2 * (size_t)n_bias;
-    if (need > m->la_reset_cap) {
+    if (need > m->la_reset.cap()) {
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-        if (m->la_reset_dev) (void)hipFree(m->la_reset_dev);
-        if (m->la_reset_pin) (void)hipHostFree(m->la_reset_pin);
-        m->la_reset_dev = m->la_reset_pin = nullptr; m->la_reset_cap = 0;
-        const size_t cap = std::max<size_t>(need, (size_t)m->cfg.max_ctx + 2 * IFA_LOGIT_BIAS_MAX);
-        IFA_HIP_CHECK(hipMalloc((void **)&m->la_reset_dev, cap * sizeof(int)));
-        IFA_HIP_CHECK(hipHostMalloc((void **)&m->la_reset_pin, cap * sizeof(int), hipHostMallocDefault));
-        m->la_reset_cap = cap;
+        if ((rc = m->la_reset.reserve(std::max<size_t>(need, (size_t)m->cfg.max_ctx + 2 * IFA_LOGIT_BIAS_MAX)))) return rc;
     }
-    if (n_prompt) memcpy(m->la_reset_pin, prompt_host, sizeof(int) * (size_t)n_prompt);
+    int *pin = m->la_reset.pin, *dev = m->la_reset.dev;
+    if (n_prompt) memcpy(pin, prompt_host, sizeof(int) * (size_t)n_prompt);
     if (n_bias) {
-        memcpy(m->la_reset_pin + n_prompt, bias_ids_host, sizeof(int) * (size_t)n_bias);
-        memcpy(m->la_reset_pin + n_prompt + n_bias, bias_vals_host, sizeof(float) * (size_t)n_bias);
+        memcpy(pin + n_prompt, bias_ids_host, sizeof(int) * (size_t)n_bias);
+        memcpy(pin + n_prompt + n_bias, bias_vals_host, sizeof(float) * (size_t)n_bias);
     }
-    if (need) IFA_HIP_CHECK(hipMemcpyAsync(m->la_reset_dev, m->la_reset_pin, need * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    rc = ifa_logit_state_reset(kv_slot, m->la_reset_dev, (size_t)n_prompt, rep, freq, pres, m->la_reset_dev + n_prompt, (const float *)(m->la_reset_dev + n_prompt + n_bias),
+    if (need) IFA_HIP_CHECK(hipMemcpyAsync(dev, pin, need * sizeof(int), hipMemcpyHostToDevice, m->stream));
+    rc = ifa_logit_state_reset(kv_slot, dev, (size_t)n_prompt, rep, freq, pres, dev + n_prompt, (const float *)(dev + n_prompt + n_bias),
                                (size_t)n_bias, V, m->la_state, m->la_bias, m->la_params, (ifa_stream)m->stream);
     if (rc) return rc;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));      // (the staging block is free again; a query starts once)
@@ -327,14 +274,11 @@ int ifa_model_logit_state_add(ifa_model *m, int n, const int *kv_slots_host, con
                     "%s: pair %d = (slot %d, token %d) outside %zu slots x %zu ids", who, i, kv_slots_host[i], tokens_host[i], m->la_slots, V);
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
     constexpr size_t BLOCK = 2 * (size_t)ifa_model::RING;
-    if (!m->la_pin) {
-        IFA_HIP_CHECK(hipMalloc((void **)&m->la_stage, ifa_model::LA_RING * BLOCK * sizeof(int)));
-        IFA_HIP_CHECK(hipHostMalloc((void **)&m->la_pin, ifa_model::LA_RING * BLOCK * sizeof(int), hipHostMallocDefault));
-        for (int i = 0; i < ifa_model::LA_RING; i++) IFA_HIP_CHECK(hipEventCreateWithFlags(&m->la_ev[i], hipEventDisableTiming));
-    }
+    for (int i = 0; i < ifa_model::LA_RING; i++) if (!m->la_ev[i]) IFA_HIP_CHECK(hipEventCreateWithFlags(&m->la_ev[i].e, hipEventDisableTiming));
+    if ((rc = m->la_ring.reserve(ifa_model::LA_RING * BLOCK))) return rc;
     const int b = (int)(m->la_calls++ % ifa_model::LA_RING);
     if (m->la_ev_used[b]) IFA_HIP_CHECK(hipEventSynchronize(m->la_ev[b]));      // (done long ago unless LA_RING calls are in flight)
-    int *pin = m->la_pin + (size_t)b * BLOCK, *dev = m->la_stage + (size_t)b * BLOCK;
+    int *pin = m->la_ring.pin + (size_t)b * BLOCK, *dev = m->la_ring.dev + (size_t)b * BLOCK;
     memcpy(pin, kv_slots_host, sizeof(int) * (size_t)n);
     memcpy(pin + n, tokens_host, sizeof(int) * (size_t)n);
     IFA_HIP_CHECK(hipMemcpyAsync(dev, pin, sizeof(int) * 2 * (size_t)n, hipMemcpyHostToDevice, m->stream));

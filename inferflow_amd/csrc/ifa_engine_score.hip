@@ -13,21 +13,9 @@ int lse_rows(const void *logits, size_t row_stride, const int *row_idx_dev, size
 
 namespace ifae {
 
-void score_free(ifa_model *m)
-{
-    if (m->score_tgt_dev) (void)hipFree(m->score_tgt_dev);
-    if (m->score_tgt_pin) (void)hipHostFree(m->score_tgt_pin);
-    if (m->score_dev) (void)hipFree(m->score_dev);
-    if (m->score_pin) (void)hipHostFree(m->score_pin);
-    if (m->lse_part) (void)hipFree(m->lse_part);
-    m->score_tgt_dev = m->score_tgt_pin = nullptr; m->score_dev = m->score_pin = nullptr; m->lse_part = nullptr;
-    m->score_cap = 0;
-}
-
 int lse_part_reserve(ifa_model *m)
 {
-    if (!m->lse_part) IFA_HIP_CHECK(hipMalloc((void **)&m->lse_part, LSE_PART_FLOATS * sizeof(float)));
-    return IFA_OK;
+    return m->lse_part ? IFA_OK : m->lse_part.alloc(LSE_PART_FLOATS);
 }
 
 // staging for n rows (grown on demand, outside any step)
@@ -35,19 +23,12 @@ static int score_reserve(ifa_model *m, int n)
 {
     int rc = lse_part_reserve(m);
     if (rc) return rc;
-    if ((size_t)n <= m->score_cap) return IFA_OK;
+    // (score_out, grown last, answers for both pairs: a failure in either leaves it empty)
+    if (2 * (size_t)n <= m->score_out.cap()) return IFA_OK;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-    if (m->score_tgt_dev) (void)hipFree(m->score_tgt_dev);
-    if (m->score_tgt_pin) (void)hipHostFree(m->score_tgt_pin);
-    if (m->score_dev) (void)hipFree(m->score_dev);
-    if (m->score_pin) (void)hipHostFree(m->score_pin);
-    m->score_tgt_dev = m->score_tgt_pin = nullptr; m->score_dev = m->score_pin = nullptr; m->score_cap = 0;
     const size_t cap = (size_t)std::max(n, 64);
-    IFA_HIP_CHECK(hipMalloc((void **)&m->score_tgt_dev, cap * sizeof(int)));
-    IFA_HIP_CHECK(hipHostMalloc((void **)&m->score_tgt_pin, cap * sizeof(int), hipHostMallocDefault));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->score_dev, 2 * cap * sizeof(float)));
-    IFA_HIP_CHECK(hipHostMalloc((void **)&m->score_pin, 2 * cap * sizeof(float), hipHostMallocDefault));
-    m->score_cap = cap;
+    m->score_out.reset(); m->score_tgt.reset();
+    if ((rc = m->score_tgt.reserve(cap)) || (rc = m->score_out.reserve(2 * cap))) return rc;
     return IFA_OK;
 }
 
@@ -58,12 +39,12 @@ int score_enqueue(ifa_model *m, const half_t *logits, int n_rows)
     if (n_rows <= 0 || R.done + n_rows > R.n) return ifa_fail(IFA_ERR_STATE, "score: a step of %d rows after %d of %d", n_rows, R.done, R.n);
     const size_t V = m->g[T_LM_HEAD].rows;
     // lse [n] | target logit [n]: the parts of a prompt taken in several steps land side by side
-    int rc = lse_rows(logits, V, nullptr, (size_t)n_rows, V, m->score_tgt_dev + R.done, m->score_dev + R.done, m->score_dev + R.n + R.done,
+    int rc = lse_rows(logits, V, nullptr, (size_t)n_rows, V, m->score_tgt.dev + R.done, m->score_out.dev + R.done, m->score_out.dev + R.n + R.done,
                       m->lse_part, m->stream);
     if (rc) return rc;
     R.done += n_rows;
     if (R.done == R.n)
-        IFA_HIP_CHECK(hipMemcpyAsync(m->score_pin, m->score_dev, sizeof(float) * 2 * (size_t)R.n, hipMemcpyDeviceToHost, m->stream));
+        IFA_HIP_CHECK(hipMemcpyAsync(m->score_out.pin, m->score_out.dev, sizeof(float) * 2 * (size_t)R.n, hipMemcpyDeviceToHost, m->stream));
     return IFA_OK;
 }
 
@@ -85,8 +66,8 @@ int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, 
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
     int rc = score_reserve(m, n_tokens);
     if (rc) return rc;
-    memcpy(m->score_tgt_pin, targets_host, sizeof(int) * (size_t)n_tokens);
-    IFA_HIP_CHECK(hipMemcpyAsync(m->score_tgt_dev, m->score_tgt_pin, sizeof(int) * (size_t)n_tokens, hipMemcpyHostToDevice, m->stream));
+    memcpy(m->score_tgt.pin, targets_host, sizeof(int) * (size_t)n_tokens);
+    IFA_HIP_CHECK(hipMemcpyAsync(m->score_tgt.dev, m->score_tgt.pin, sizeof(int) * (size_t)n_tokens, hipMemcpyHostToDevice, m->stream));
     m->score = ifa_model::ScoreReq();
     m->score.n = n_tokens;
     int next = -1;
@@ -95,8 +76,8 @@ int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, 
     m->score = ifa_model::ScoreReq();
     if (rc) return rc;
     if (R.done != R.n) return ifa_fail(IFA_ERR_STATE, "ifa_model_forward_score: the prompt served %d of %d rows", R.done, R.n);
-    memcpy(lse_host, m->score_pin, sizeof(float) * (size_t)n_tokens);
-    memcpy(target_logit_host, m->score_pin + n_tokens, sizeof(float) * (size_t)n_tokens);
+    memcpy(lse_host, m->score_out.pin, sizeof(float) * (size_t)n_tokens);
+    memcpy(target_logit_host, m->score_out.pin + n_tokens, sizeof(float) * (size_t)n_tokens);
     if (next_token_host) *next_token_host = next;
     return IFA_OK;
 }

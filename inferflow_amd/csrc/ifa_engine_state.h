@@ -9,6 +9,13 @@
 //   ifa_engine_tp.hip       tensor / layer partitions: per-seam entry points and the multi-GPU step driven from C
 //   ifa_kv_copy.hip         cache rows from one query slot to another in one launch (the engine's prompt prefix cache)
 //   ifa_decode_draft_kv.hip the draft step: n rows of ONE slot in one batched step (ifa_model_decode_draft; the engine's lookup decoding)
+//
+// Worker memory.  Every device or pinned block the worker owns is a DevBuf / PinBuf / DevPin member (ifa_buf.h, ifa_buf_hip.h) of
+// the struct that uses it: it is freed when its owner goes -- `delete m`, a Tensor assigned over, a KvSlot dropped -- and by nothing
+// else, so no unit keeps a free list.  The members read as plain pointers.  Growth is all-or-nothing: a unit allocates the new
+// blocks into locals (or Staged::reserve / Buf::alloc, which hold everything or nothing with capacity 0) and installs them only
+// when every allocation has succeeded; a failed growth leaves either the old state or an empty one the next call rebuilds, never a
+// size over freed memory.  Captured steps hold buffer addresses: whoever moves a buffer calls drop_graphs().
 #pragma once
 #include <chrono>
 #include <cstdlib>
@@ -17,6 +24,7 @@
 #include <string>
 #include <vector>
 #include "ifa_host.h"
+#include "ifa_buf_hip.h"
 #include "ifa_decode_kernels.h"
 #include "ifa_decode_attn.h"
 #include "ifa_decode_gemv.h"
@@ -42,11 +50,11 @@ enum { T_EMBD = 0, T_OUT_NORM = 1, T_OUT_NORM_B = 2, T_LM_HEAD = 3,
 
 struct Tensor {
     int dtype = -1;
-    void *data = nullptr;    // reference layout (AoS blocks / F16), engine-owned
-    void *tiled = nullptr;   // row-local plane layout for the fused kernels (or null)
-    void *mo = nullptr;      // MFMA-operand-order copy for the small-batch rows GEMM (ifa_gemm_rows_mfma.h), built on first use
-    void *q3hn = nullptr;    // Q3H_B64T1: the values at the format's native 32 bytes per block for the decode GEMVs (option q3h_native, built on first use)
-    void *x32 = nullptr;     // 64-weight nibble formats: the same values as Q4_B32T1A reference-layout blocks, for the large-tile prefill GEMM
+    DevBuf<void> data;       // reference layout (AoS blocks / F16), engine-owned
+    DevBuf<void> tiled;      // row-local plane layout for the fused kernels (or null)
+    DevBuf<void> mo;         // MFMA-operand-order copy for the small-batch rows GEMM (ifa_gemm_rows_mfma.h), built on first use
+    DevBuf<void> q3hn;       // Q3H_B64T1: the values at the format's native 32 bytes per block for the decode GEMVs (option q3h_native, built on first use)
+    DevBuf<void> x32;        // 64-weight nibble formats: the same values as Q4_B32T1A reference-layout blocks, for the large-tile prefill GEMM
     size_t rows = 0, cols = 0;
     bool present() const { return data != nullptr; }
 };
@@ -54,51 +62,55 @@ struct Tensor {
 struct Layer {
     Tensor t[T_MAX];
     std::vector<Tensor> experts;   // [expert][3]: w1, w2, w3 (MoE layers)
-    void *moe_table = nullptr;     // device: [expert][4] tiled pointers {w1, w3, w2, -} for the fused decode kernels
-    void *moe_table_aos = nullptr; // device: [expert][3] reference-layout pointers {w1, w2, w3} for the grouped T > 1 launches
-    void *moe_table_mo = nullptr;  // device: [expert][4] MO copies {w1, w3, w2, -} for the experts with 2..8 rows of a batched step (ensure_mo)
-    void *kcache = nullptr, *vcache = nullptr;
+    DevBuf<void *> moe_table;      // device: [expert][4] tiled pointers {w1, w3, w2, -} for the fused decode kernels
+    DevBuf<void *> moe_table_aos;  // device: [expert][3] reference-layout pointers {w1, w2, w3} for the grouped T > 1 launches
+    DevBuf<void *> moe_table_mo;   // device: [expert][4] MO copies {w1, w3, w2, -} for the experts with 2..8 rows of a batched step (ensure_mo)
+    DevBuf<void> kcache, vcache;
+};
+
+// Activation scratch, sized for scratch_tokens rows by ensure_scratch (which builds a new set and move-assigns it: all or nothing).
+// dqkv, attq and moe_route are allocated once, bqkv / brope once a step of <= 32 rows asks; those keep their address over a growth.
+struct Scratch {
+    DevBuf<half_t> x, x2, xn, hn, q, k, v;
+    DevBuf<half_t> dqkv;        // the decode step's q | k | v vector as ONE buffer (k_dec_attn addresses k and v from q's pointer)
+    DevBuf<half_t> bqkv;        // fused batched step: [32 queries][q | k | v]
+    DevBuf<float> brope;        // fused batched step: [32 queries][head_dim] (cos, sin) pairs
+    DevBuf<half_t> att, a, f, t1, t2, logits;
+    DevBuf<uint8_t> xq;
+    DevBuf<int8_t> attq;           // XqImage of the attention output (Q8_B32T2), written by the fused attention kernels for the Wo GEMV
+    DevBuf<half_t> moe_gate, moe_out;     // MoE: router probabilities [T][experts], one expert's output rows
+    DevBuf<half_t> moe_in, moe_wdev;      // MoE: one expert's gathered input rows; per-row weights
+    DevBuf<int> moe_route;                // device: fused decode routing, [0..7] expert ids, halfs at byte 32: weights
+    DevBuf<int> moe_idx; PinBuf<void> moe_pin;     // MoE: row lists of all experts, back to back (device / pinned staging)
+    // MoE over T > 1 rows without the host (moe_ffn_device): routing, lists, gathered rows of ALL experts at once
+    DevBuf<int> moe_sel, moe_epos, moe_counts;
+    DevBuf<half_t> moe_selw, moe_g1, moe_g3, moe_gin, moe_gout;
+    DevBuf<uint8_t> moe_xq_in, moe_xq_mid;
+    DevBuf<void> moe_tiles, moe_singles, moe_smalls;
+    DevBuf<int> tokens_dev;
+    DevBuf<half_t> pn;             // [tokens][dim] scratch of the post norms
 };
 
 
 } // namespace ifae
 using namespace ifae;
 
-struct ifa_model {
+struct ifa_model : Scratch {
     ifa_model_config cfg;
     std::vector<Layer> layers;
     Tensor g[10];
     hipStream_t stream = nullptr;
     // side stream + fork / join events of the batched MoE step: the single-row experts run next to the small groups (both stream
     // expert matrices nobody else reads and neither saturates the memory system alone); created on first use
-    hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; int opt_moe_overlap = 1;
+    hipStream_t side_stream = nullptr; Event ev_fork, ev_join; int opt_moe_overlap = 1;
     bool own_stream = true;
     bool finalized = false;
-    // scratch
-    half_t *x = nullptr, *x2 = nullptr, *xn = nullptr, *hn = nullptr, *q = nullptr, *k = nullptr, *v = nullptr;
-    half_t *dqkv = nullptr;     // the decode step's q | k | v vector as ONE buffer (k_dec_attn addresses k and v from q's pointer)
-    half_t *bqkv = nullptr;     // fused batched step: [queries][q | k | v]
-    float *brope = nullptr;     // fused batched step: [queries][head_dim] (cos, sin) pairs
-    size_t bqkv_rows = 0;
-    half_t *att = nullptr, *a = nullptr, *f = nullptr, *t1 = nullptr, *t2 = nullptr, *logits = nullptr;
-    uint8_t *xq = nullptr;
-    int8_t *attq = nullptr;        // XqImage of the attention output (Q8_B32T2), written by the fused attention kernels for the Wo GEMV
-    half_t *moe_gate = nullptr, *moe_out = nullptr;   // MoE: router probabilities [T][experts], one expert's output rows
-    half_t *moe_in = nullptr, *moe_wdev = nullptr;    // MoE: one expert's gathered input rows; per-row weights
-    int *moe_route = nullptr;                          // device: fused decode routing, [0..7] expert ids, halfs at byte 32: weights
-    int *moe_idx = nullptr, *moe_pin = nullptr;        // MoE: row lists of all experts, back to back (device / pinned staging)
-    // MoE over T > 1 rows without the host (moe_ffn_device): routing, lists, gathered rows of ALL experts at once
-    int *moe_sel = nullptr, *moe_epos = nullptr, *moe_counts = nullptr;
-    half_t *moe_selw = nullptr, *moe_g1 = nullptr, *moe_g3 = nullptr, *moe_gin = nullptr, *moe_gout = nullptr;
-    uint8_t *moe_xq_in = nullptr, *moe_xq_mid = nullptr;
-    void *moe_tiles = nullptr, *moe_singles = nullptr, *moe_smalls = nullptr;
     int opt_moe_device = 1;
-    int *state = nullptr;          // device: see k_dec_gather
-    float *rope_tab = nullptr;     // device: [head_dim/2][2]
-    long long *trace = nullptr;    // device: [2048][8] optional kernel phase stamps
+    DevBuf<int> state;             // device: see k_dec_gather
+    DevBuf<float> rope_tab;        // device: [head_dim/2][2]
+    DevBuf<long long> trace;       // device: [2048][8] optional kernel phase stamps
     int opt_trace = 0, opt_bench_mode = 0, opt_touch_stride = 65536;
-    int *tokens_dev = nullptr;
-    int *host_pinned = nullptr;    // pinned staging for state / tokens
+    PinBuf<int> host_pinned;       // pinned staging for state / tokens
     int scratch_tokens = 0;
     size_t kv_row_bytes = 0;
     // decode graph
@@ -113,19 +125,19 @@ struct ifa_model {
     struct PendingAdd { const half_t *x = nullptr, *add = nullptr, *bias = nullptr; half_t *out = nullptr; bool on = false; } pend;
     int opt_tp_fuse_add = 1;
     // dynamic batching tables (forward_batch)
-    void *batch_tab_dev = nullptr, *batch_tab_pin = nullptr;
-    size_t batch_tab_bytes = 0;
+    DevPin<void> batch_tab;
     std::map<int, hipGraphExec_t> batch_graphs;      // captured batched step per batch size (dense models)
     std::map<int, hipGraphExec_t> draft_graphs;      // captured draft step (ifa_model_decode_draft: n rows of ONE slot) per row count
     // long-context decode attention (keys split over workgroups): workspace, switch and the context it starts at
-    DecAttnSplitWs attn_ws = {nullptr, nullptr, nullptr, 8};
+    DecAttnSplitWs attn_ws = {nullptr, nullptr, nullptr, 8};      // (what the kernels take: filled from the three owners below)
+    DevBuf<half_t> attn_ws_S; DevBuf<float> attn_ws_lmax, attn_ws_opart;
     int opt_attn_unload = 1;       // 1 (default): in the 256-row bucket the heads' workgroups of the fused QKV + attention launch take no weight rows (UL kernels)
     int opt_attn_nsplits = 0;      // > 0: splits per head whatever the context (measurement)
     // attention as the tail of the QKV launch (ifa_decode_qkv_attn.h): granules [layers][(heads + 2 kv_heads) * head_dim], the
     // decode-call counter the tags are built from, its own error word
     int opt_fuse_attn = 1, opt_fuse_attn_timeout_us = 20000, qa_on = 0, qa_gk = 0;
-    unsigned long long *qa_gran = nullptr;
-    unsigned *qa_call = nullptr, *qa_err = nullptr, qa_calls = 0;
+    DevBuf<unsigned long long> qa_gran;
+    DevBuf<unsigned> qa_call, qa_err; unsigned qa_calls = 0;
     // consecutive GEMV ops of a layer as ONE launch with the next op's rows requested before the hand-off (ifa_decode_chain.h):
     // option fuse_ffn = 1: W1 | W3 -> W2; 2: Wo -> W1 | W3 -> W2.  ch_on = what the captured step uses.  Granules [layers][dim + ffn].
     int opt_fuse_ffn = 0, ch_on = 0, opt_chain_late_w2 = 0;
@@ -142,25 +154,25 @@ struct ifa_model {
     std::vector<hipEvent_t> perf_pool;
     std::map<int, float> perf_map;
     int opt_exact_order = 0;         // single-token steps in the reference kernels' summation order (ifa_engine_exact.hip): bit-identical to the oracle
-    float *exact_rope_tab = nullptr; // device: [max_ctx][head_dim / 2] (cos, sin) from the host libm, built on the first exact step
-    uint32_t *ch_gran = nullptr, *ch_flags = nullptr;      // flags [layers][2][CH_FLAGS]
+    DevBuf<float> exact_rope_tab;    // device: [max_ctx][head_dim / 2] (cos, sin) from the host libm, built on the first exact step
+    DevBuf<uint32_t> ch_gran, ch_flags;                    // flags [layers][2][CH_FLAGS]
     // the end of the step as one launch (ifa_decode_lmhead_tail.h): lm_head + argmax + state advance + the next step's gather.
     // st_on = what the captured step uses (F16 lm_head with the RMS / no final norm)
     int opt_step_tail = 1, st_on = 0;
-    unsigned long long *st_keys = nullptr; unsigned *st_counter = nullptr; int st_keys_n = 0;
+    DevBuf<unsigned long long> st_keys; DevBuf<unsigned> st_counter;      // (st_keys.cap(): the lm_head grid the keys serve)
     int attn_pb = 256, opt_attn_kt = 1;      // cache rows the one-workgroup decode attention requests at entry (64 / 128 / 256: the bucket the call stays inside); K rows through the LDS tile
     int attn_split = 0, opt_attn_split_ctx = -1, opt_batch_graph = 0, opt_gemm_rows = 1, opt_batch_fused = 1, opt_moe_router_fused = 1, opt_prefill_big = 1, opt_rows_mo = 1, opt_moe_singles = 1;
     // independent KV caches ("query slots", one per concurrent query like the reference's per-query
     // LayerKVCache sets): the inactive ones park their cache pointers and captured graph here
-    struct KvSlot { std::vector<void *> k, v; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
+    struct KvSlot { std::vector<DevBuf<void>> k, v; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
     std::vector<KvSlot> slots;
     int cur_slot = 0;
     // options
     int opt_attn_q8 = 1;
     // multi-GPU decode driven from C (ifa_model_tp_decode): merge buffers, the distributed argmax's scratch, the captured step
-    half_t *tp_a = nullptr, *tp_f = nullptr, *tp_hid = nullptr, *tp_logits = nullptr;
-    float *tp_best = nullptr, *tp_gather = nullptr;
-    int *tp_tok = nullptr;
+    DevBuf<half_t> tp_a, tp_f, tp_hid, tp_logits;
+    DevBuf<float> tp_best, tp_gather;      // (tp_tok.cap(): the rows the distributed-argmax scratch -- these three -- holds)
+    DevBuf<int> tp_tok;
     hipGraph_t tp_graph = nullptr;
     hipGraphExec_t tp_graph_exec = nullptr;
     // what the captured multi-GPU step was recorded with: communicator identities and every topology field its launches
@@ -172,10 +184,8 @@ struct ifa_model {
                 && oneshot == o.oneshot; }      // (oneshot: the captured collectives are the exchange or RCCL -- a switch forces a re-capture)
     } tp_key;
     const ifa_tp_topology *topo = nullptr;     // set by the partition entry points for the duration of a T > 1 / batched step
-    size_t tp_rows_cap = 0;                    // rows the distributed-argmax scratch (tp_best / tp_gather / tp_tok) holds
     // is_attn_post_as_residual (model.h:113, default true): with an attention post-norm, the FFN's residual is the NORMALISED tensor
     int opt_attn_post_as_residual = 1;
-    half_t *pn = nullptr;           // [tokens][dim] scratch of the post norms (allocated with the other activations)
     int opt_fused = 1, opt_graph = 1, opt_rpw_qkv = 0, opt_rpw_wo = 0, opt_rpw_ffn = 0, opt_rpw_w2 = 0, opt_rpw_lm = 0;
     int opt_debug_layers = 0;                  // > 0: the decode step runs only the first N layers (tools/debug_engine.py)
     // layer-wise parity tests (tests/test_gpu_layerwise_oracle.py): the fused decode step starts at layer debug_layer0 (with
@@ -206,42 +216,41 @@ struct ifa_model {
         bool lse = false;                      // option pool_lse at arming: the rows' log-sum-exp ride in the block
         std::vector<int> adj;                  // logit processors (ifa_model_pool_adjust): [n_sel] state slot of pooled row j, -1 raw; empty: none
     } pool;
-    unsigned *pool_excl = nullptr;             // device bitmask of ids the pool never offers (null: none)
-    void *pool_dev = nullptr, *pool_pin = nullptr; size_t pool_bytes = 0;      // result block, device / pinned
-    int *pool_idx_dev = nullptr, *pool_idx_pin = nullptr; size_t pool_idx_cap = 0;
+    DevBuf<unsigned> pool_excl;                // device bitmask of ids the pool never offers (null: none)
+    DevPin<void> pool_blk;                     // result block, device / pinned
+    DevPin<int> pool_idx;                      // row indices [cap / 2] | state slots of armed rows [cap / 2] (logit processors)
     // Logit processors (ifa_logit_adjust.hip): per KV slot the u32 state row, the f32 bias row and {rep, freq, pres}, allocated for
     // la_slots slots on the first ifa_model_logit_state_reset (regrown, contents kept, when ifa_model_kv_slots has added slots).
     // pool_adj_next: what ifa_model_pool_adjust armed for the next pool step (moved into pool.adj by pool_arm).  la_adj: the adjusted
-    // rows of the last armed step, [la_adj_rows][vocab].  la_pin / la_stage: LA_RING staging blocks of 2 * RING ints (slots | tokens)
-    // for ifa_model_logit_state_add, block i guarded by la_ev[i]; reset's prompt / bias staging is la_reset_pin / la_reset_dev.
+    // rows of the last armed step, [rows][vocab].  la_ring: LA_RING staging blocks of 2 * RING ints (slots | tokens)
+    // for ifa_model_logit_state_add, block i guarded by la_ev[i]; reset's prompt / bias staging is la_reset.
     static constexpr int LA_RING = 8;
-    unsigned *la_state = nullptr; float *la_bias = nullptr, *la_params = nullptr; size_t la_slots = 0;
-    half_t *la_adj = nullptr; size_t la_adj_rows = 0;
+    DevBuf<unsigned> la_state; DevBuf<float> la_bias, la_params; size_t la_slots = 0;
+    DevBuf<half_t> la_adj;
     std::vector<int> pool_adj_next;
-    int *la_pin = nullptr, *la_stage = nullptr; hipEvent_t la_ev[LA_RING] = {}; bool la_ev_used[LA_RING] = {}; unsigned la_calls = 0;
-    int *la_reset_pin = nullptr, *la_reset_dev = nullptr; size_t la_reset_cap = 0;
+    DevPin<int> la_ring; Event la_ev[LA_RING]; bool la_ev_used[LA_RING] = {}; unsigned la_calls = 0;
+    DevPin<int> la_reset;
     // option pool_lse = 1: the pool steps also deliver the log-sum-exp of every pooled row (csrc/ifa_logprob.hip; log p = value - lse).
     // The block then reads counts [n_sel] | lse [n_sel] | ids | F16 bits, still one copy; ifa_model_pool_lse hands out the last step's.
     int opt_pool_lse = 0;
     std::vector<float> pool_lse_last;
-    float *lse_part = nullptr;                 // device: (max, sum) pairs of the rows a launch splits over workgroups (LSE_PART_FLOATS)
+    DevBuf<float> lse_part;                    // device: (max, sum) pairs of the rows a launch splits over workgroups (LSE_PART_FLOATS)
     // Scoring prompt (ifa_model_forward_score, ifa_engine_score.hip): armed like `pool`; the prompt runs its lm_head over all rows
     // and every route calls score_enqueue() on the rows it has just written, in front of its synchronisation.
     struct ScoreReq {
         int n = 0;                             // > 0: armed, rows wanted in all
         int done = 0;                          // rows whose launch has been enqueued
     } score;
-    int *score_tgt_dev = nullptr, *score_tgt_pin = nullptr;     // [cap] target ids
-    float *score_dev = nullptr, *score_pin = nullptr;           // lse [cap] | target logit [cap]
-    size_t score_cap = 0;
+    DevPin<int> score_tgt;                     // [cap] target ids
+    DevPin<float> score_out;                   // lse [cap] | target logit [cap]
     // Slot-to-slot copy of cache rows (ifa_model_kv_copy, ifa_kv_copy.hip): the K and V buffers of EVERY slot as one device table
-    // [slot][layer: k, v], staged once through kvc_tab_pin on the model's stream and rebuilt only when a slot's buffers are not the
+    // [slot][layer: k, v], staged once through kvc_tab.pin on the model's stream and rebuilt only when a slot's buffers are not the
     // ones it lists (more slots).  A slot's buffers are its own for good -- select_kv moves pointers between the layers and the
     // parked slot, never between slots -- so a call is ONE launch that indexes the table.  A replaced table is parked in
     // kvc_retired until the model goes: an earlier launch may still read it and nothing here waits for the stream.
-    void **kvc_tab_dev = nullptr, **kvc_tab_pin = nullptr;
+    DevPin<void *> kvc_tab;
     std::vector<void *> kvc_tab_host;          // what the device table holds
-    std::vector<void *> kvc_retired;           // device / pinned blocks of replaced tables, alternating
+    std::vector<DevPin<void *>> kvc_retired;   // replaced tables
     static constexpr int RING = 1024;
 };
 
@@ -267,7 +276,7 @@ static inline int num_cus() { return dec_num_cus(); }
 // (k_dec_gemv_h).  wbytes() hands out the matching pointer.
 static inline bool fused_int8(int w_dtype) { return ax8_eligible(w_dtype); }
 
-static inline const uint8_t *wbytes(const Tensor &t) { return (const uint8_t *)(fused_int8(t.dtype) ? t.tiled : t.data); }
+static inline const uint8_t *wbytes(const Tensor &t) { return (const uint8_t *)(fused_int8(t.dtype) ? t.tiled.get() : t.data.get()); }
 
 
 extern "C" int ifa_add_layernorm(int kind, const void *a, const void *addend, size_t rows, size_t cols, const void *w, const void *b,
@@ -315,7 +324,7 @@ extern "C" int ifa_rope_rows(void *x, int head_dim, int heads, int tokens, const
                              float partial_rotary_factor, ifa_stream stream);
 
 // weight pointer of a rows-GEMM launch: the MO copy when it exists (all sets of a launch alike: ensure_mo builds all or none)
-static inline const uint8_t *rows_w(const ifa_model *m, const Tensor &t) { return (const uint8_t *)(m->opt_rows_mo && t.mo ? t.mo : t.tiled); }
+static inline const uint8_t *rows_w(const ifa_model *m, const Tensor &t) { return (const uint8_t *)(m->opt_rows_mo && t.mo ? t.mo.get() : t.tiled.get()); }
 
 static inline int rows_mo(const ifa_model *m, const Tensor &t) { return m->opt_rows_mo && t.mo ? 1 : 0; }
 
@@ -333,7 +342,6 @@ struct PerfSpan {
     ~PerfSpan() { done(); }
     void done() { if (idx >= 0) { perf_end(m, idx); idx = -1; } }
 };
-void free_tensor(Tensor &t);
 void *kv_ptr(ifa_model *m, size_t layer, int slot, bool is_v);
 int ensure_mo(ifa_model *m);
 int ensure_mo_build(ifa_model *m);
@@ -389,17 +397,12 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
 // armed (m->pool.k > 0): ifa_topk_pool over the wanted rows of `logits` ([n_rows][vocab], this step's rows) + the copy of the result
 // block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.
 int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
-void pool_free(ifa_model *m);
-void logit_adjust_free(ifa_model *m);      // (called by pool_free)
 // ---- ifa_engine_score.hip
 static constexpr size_t LSE_PART_FLOATS = 256;      // rows * splits <= 128 pairs whatever the row count (ifa_logprob.hip, lse_splits)
 int lse_part_reserve(ifa_model *m);
 // armed (m->score.n > 0): the row log-sum-exp + target gather over `logits` ([n_rows][vocab], the next n_rows rows of the prompt); after
 // the last row the copy of the 2 * n floats into pinned staging.  A no-op otherwise.
 int score_enqueue(ifa_model *m, const half_t *logits, int n_rows);
-void score_free(ifa_model *m);
-// ---- ifa_kv_copy.hip
-void kv_copy_free(ifa_model *m);
 // ---- ifa_engine_moe.hip
 int launch_moe_router(ifa_model *m, int l);
 // Mixture of experts (ProcessGpuLayer_Moe, inference_worker.cc:1924-2146): router GEMV -> softmax -> D2H ->

@@ -51,16 +51,11 @@ __global__ void k_tp_pick(const float *__restrict__ gathered, int nranks, int n_
 // scratch of the distributed argmax for n_rows rows
 int tp_argmax_scratch(ifa_model *m, size_t n_rows)
 {
-    if (n_rows <= m->tp_rows_cap) return IFA_OK;
-    if (m->tp_best) IFA_HIP_CHECK(hipFree(m->tp_best));
-    if (m->tp_gather) IFA_HIP_CHECK(hipFree(m->tp_gather));
-    if (m->tp_tok) IFA_HIP_CHECK(hipFree(m->tp_tok));
-    m->tp_best = nullptr; m->tp_gather = nullptr; m->tp_tok = nullptr;
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tp_best, 8 * n_rows));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tp_gather, 8 * 64 * n_rows));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tp_tok, 4 * n_rows));
-    m->tp_rows_cap = n_rows;
-    drop_graphs(m);
+    if (n_rows <= m->tp_tok.cap()) return IFA_OK;
+    drop_graphs(m);                // the captured steps hold the old addresses
+    m->tp_tok.reset();             // (allocated last: its capacity stands for all three, so a failed growth reads as "none")
+    int rc;
+    if ((rc = m->tp_best.alloc(2 * n_rows)) || (rc = m->tp_gather.alloc(2 * 64 * n_rows)) || (rc = m->tp_tok.alloc(n_rows))) return rc;
     return IFA_OK;
 }
 
@@ -321,11 +316,11 @@ int tp_buffers(ifa_model *m)
     if (m->tp_a) return IFA_OK;
     const ifa_model_config &c = m->cfg;
     const size_t D = (size_t)c.dim;
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tp_a, D * 2));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tp_f, D * 2));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tp_hid, D * 2));
-    IFA_HIP_CHECK(hipMalloc((void **)&m->tp_logits, std::max<size_t>(m->g[T_LM_HEAD].rows, 1) * 2));
-    return tp_argmax_scratch(m, 1);
+    // (tp_a, the "done" mark above, last: a failure part-way is repeated by the next call)
+    int rc;
+    if ((rc = m->tp_f.alloc(D)) || (rc = m->tp_hid.alloc(D)) || (rc = m->tp_logits.alloc(std::max<size_t>(m->g[T_LM_HEAD].rows, 1)))
+        || (rc = tp_argmax_scratch(m, 1)) || (rc = m->tp_a.alloc(D))) return rc;
+    return IFA_OK;
 }
 
 // want_token = false (all but the last token of a prompt): the layers run, the lm_head / argmax / token exchange do not

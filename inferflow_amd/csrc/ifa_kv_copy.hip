@@ -44,27 +44,17 @@ __global__ __launch_bounds__(KVC_THREADS) void k_kv_copy(void *const *src_tab, v
     if (t < bytes) dst[t] = src[t];
 }
 
-void kv_copy_free(ifa_model *m)
-{
-    if (m->kvc_tab_dev) (void)hipFree(m->kvc_tab_dev);
-    if (m->kvc_tab_pin) (void)hipHostFree(m->kvc_tab_pin);
-    for (size_t i = 0; i + 1 < m->kvc_retired.size(); i += 2) { (void)hipFree(m->kvc_retired[i]); (void)hipHostFree(m->kvc_retired[i + 1]); }
-    m->kvc_tab_dev = m->kvc_tab_pin = nullptr;
-    m->kvc_tab_host.clear(); m->kvc_retired.clear();
-}
-
 // the device table lists the buffers slots `a` and `b` have now; if not, a new table of all slots is staged on the model's stream
 static int kv_copy_table(ifa_model *m, int a, int b)
 {
     const size_t L = m->layers.size(), n_slots = std::max<size_t>(m->slots.size(), 1);
-    bool ok = m->kvc_tab_dev && m->kvc_tab_host.size() == n_slots * 2 * L;
+    bool ok = m->kvc_tab.dev && m->kvc_tab_host.size() == n_slots * 2 * L;
     for (int slot : {a, b})
         for (size_t l = 0; ok && l < L; l++)
             ok = m->kvc_tab_host[((size_t)slot * L + l) * 2] == kv_ptr(m, l, slot, false)
                  && m->kvc_tab_host[((size_t)slot * L + l) * 2 + 1] == kv_ptr(m, l, slot, true);
     if (ok) return IFA_OK;
-    if (m->kvc_tab_dev) { m->kvc_retired.push_back(m->kvc_tab_dev); m->kvc_retired.push_back(m->kvc_tab_pin); }
-    m->kvc_tab_dev = m->kvc_tab_pin = nullptr;
+    if (m->kvc_tab.dev) m->kvc_retired.push_back(std::move(m->kvc_tab));
     m->kvc_tab_host.assign(n_slots * 2 * L, nullptr);
     for (size_t s = 0; s < n_slots; s++)
         for (size_t l = 0; l < L; l++) {
@@ -72,12 +62,12 @@ static int kv_copy_table(ifa_model *m, int a, int b)
             m->kvc_tab_host[(s * L + l) * 2 + 1] = kv_ptr(m, l, (int)s, true);
         }
     const size_t tab_bytes = m->kvc_tab_host.size() * sizeof(void *);
-    hipError_t e = hipMalloc((void **)&m->kvc_tab_dev, tab_bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&m->kvc_tab_pin, tab_bytes, hipHostMallocDefault);
-    if (e == hipSuccess) {
-        memcpy(m->kvc_tab_pin, m->kvc_tab_host.data(), tab_bytes);
+    hipError_t e = hipSuccess;
+    if (m->kvc_tab.reserve(m->kvc_tab_host.size())) e = hipErrorOutOfMemory;
+    else {
+        memcpy(m->kvc_tab.pin, m->kvc_tab_host.data(), tab_bytes);
         // (the pinned block is never written again: it is valid for as long as this copy may be pending)
-        e = hipMemcpyAsync(m->kvc_tab_dev, m->kvc_tab_pin, tab_bytes, hipMemcpyHostToDevice, m->stream);
+        e = hipMemcpyAsync(m->kvc_tab.dev, m->kvc_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream);
     }
     if (e != hipSuccess) {
         m->kvc_tab_host.clear();          // (the next call builds the table again)
@@ -106,8 +96,8 @@ extern "C" int ifa_model_kv_copy(ifa_model *m, int src_slot, int dst_slot, int n
     const size_t L = m->layers.size(), bytes = (size_t)n_rows * m->kv_row_bytes;
     // (+ 1 piece: a segment that ends on a chunk boundary, or holds fewer than 16 bytes, still gets the workgroup that moves the tail)
     const unsigned chunks = ifa_cdiv((bytes >> 4) + 1, KVC_CHUNK16);
-    k_kv_copy<<<dim3(chunks, (unsigned)(2 * L)), dim3(KVC_THREADS), 0, m->stream>>>(m->kvc_tab_dev + (size_t)src_slot * 2 * L,
-                                                                                 m->kvc_tab_dev + (size_t)dst_slot * 2 * L, bytes);
+    k_kv_copy<<<dim3(chunks, (unsigned)(2 * L)), dim3(KVC_THREADS), 0, m->stream>>>(m->kvc_tab.dev + (size_t)src_slot * 2 * L,
+                                                                                 m->kvc_tab.dev + (size_t)dst_slot * 2 * L, bytes);
     IFA_LAUNCH_CHECK();
     return IFA_OK;
 }

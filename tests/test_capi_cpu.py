@@ -64,3 +64,16 @@ def test_errors_are_codes_not_exceptions():
     assert b"null" in L.ifa_last_error()
     assert L.ifa_gemv(dt.F32, 1, 1, 32, dt.F16, 1, None, 1, None) == -1
     assert L.ifa_device_count() >= 0
+
+
+def test_worker_memory_hooks_answer_without_a_device():
+    """ifa_debug_alloc_fail_at / ifa_debug_live_allocs: a countdown and a counter, no HIP call"""
+    import ctypes as C
+    L = ia.lib()
+    n, b = C.c_longlong(-1), C.c_longlong(-1)
+    assert L.ifa_debug_live_allocs(C.byref(n), C.byref(b)) == 0
+    assert n.value >= 0 and b.value >= 0 and (n.value == 0) == (b.value == 0)      # (nothing, unless this process holds workers)
+    assert L.ifa_debug_live_allocs(None, None) == 0
+    assert L.ifa_debug_alloc_fail_at(3) == 0 and L.ifa_debug_alloc_fail_at(0) == 0
+    assert L.ifa_debug_alloc_fail_at(-1) == -1
+    assert b"nth" in L.ifa_last_error()
