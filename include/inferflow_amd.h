@@ -339,6 +339,24 @@ int ifa_model_select_kv(ifa_model *m, int slot);
  * rows computes what it would on the source.  n_rows = 0 is IFA_OK without a launch.  IFA_ERR_ARG: src_slot == dst_slot, a slot
  * outside ifa_model_kv_slots, n_rows outside 0..max_ctx, a model that is not finalized; IFA_ERR_STATE: a stream under capture. */
 int ifa_model_kv_copy(ifa_model *m, int src_slot, int dst_slot, int n_rows);
+/* Context shift (csrc/ifa_kv_shift.hip; arithmetic in DESIGN.md "Context shift"): of the n_rows cache rows of query slot `slot`
+ * the rows [keep, keep + discard) are dropped and the rows [keep + discard, n_rows) of every layer's K and V move to
+ * [keep, n_rows - discard).  V rows move byte for byte; K rows, which are stored with RoPE applied, are rotated back by `discard`
+ * positions on the way (table: (cos, -sin) of position `discard` from the rope function of the steps' own tables), Q8_B32T2 rows
+ * through dequantise / rotate / the store quantiser; a model without RoPE moves K byte for byte too.  Rows [0, keep), every byte
+ * from row n_rows - discard on and every other slot are not written.  All 2 * layers segments go through the slot table in one
+ * launch when the moved rows do not outnumber the dropped ones, else in ascending pieces of `discard` rows; on the model's stream,
+ * ordered with the steps around it, no host synchronisation; either the selected slot or another one.  IFA_ERR_ARG: keep < 0,
+ * discard < 1, keep + discard > n_rows, n_rows > max_ctx, an unknown slot, a Q8 cache whose head_dim is no multiple of 32, a model
+ * that is not finalized; IFA_ERR_STATE: a stream under capture, a partitioned worker (tp_size > 1 or a topology). */
+int ifa_model_kv_shift(ifa_model *m, int slot, int keep, int discard, int n_rows);
+/* The same on ONE layer's pair of buffers ([rows][kv_heads * head_dim] halfs, or Q8_B32T2 blocks) with the caller's table:
+ * table_dev = head_dim / 2 pairs (c, s) of fp32 on the device; pair (i0, i1) of a K row becomes (x0 * c - x1 * s, x0 * s + x1 * c).
+ * rope_order 1: pairs (2 i, 2 i + 1); 2: pairs (i, i + rope_cols / 2) for 2 i < rope_cols, the other columns move verbatim; 0: K
+ * moves like V (no table).  kcache / vcache may be NULL to skip a side; they need not start an allocation (the access width follows their alignment too), an
+ * odd address is IFA_ERR_ARG.  kv_dtype: IFA_F16 or IFA_Q8_B32T2. */
+int ifa_kv_shift_rows(int kv_dtype, void *kcache, void *vcache, size_t kv_heads, size_t head_dim, int rope_order, int rope_cols,
+                      const float *table_dev, size_t keep, size_t discard, size_t n_rows, ifa_stream stream);
 int ifa_model_set_option(ifa_model *m, const char *name, int value);
 /* up to 3 token ids the worker's greedy argmax (forward / decode / decode_batch) never selects: the unk id and
  * Invalid-type tokens GetSortedTopK skips (sampling_strategy.cc:281-297).  None by default at this level; the engine

@@ -52,6 +52,10 @@ typedef struct ifa_query_options {
     int n_logit_bias;
     const int *logit_bias_ids;
     const float *logit_bias_values;
+    /* context shift for this query (see ifa_engine_shift_query below).  context_shift: -1 the engine's `context_shift` key, 0 off,
+     * 1 on (-1 with a message where "context_shift_available" is 0); context_keep: -1 the engine's `context_shift_keep`, else the cache
+     * rows kept in front of the dropped block, 0 .. max_context_len / 2 (more is refused with a message) */
+    int context_shift, context_keep;   /* -1, -1 */
 } ifa_query_options;
 int ifa_engine_add_query_opt(ifa_engine *e, const int *tokens, int n_tokens, const ifa_query_options *options);
 /* logprobs of the query's most recent step (after ifa_engine_infer): *chosen = log p of the token the step chose; ids / logprobs
@@ -144,11 +148,30 @@ double ifa_perplexity_token_nll(const uint16_t *logits_f16, int vocab, int token
  * whose rows sat in a busy slot and were copied on the device, ifa_model_kv_copy), "lookup_decoding" (0 / 1: ifa_engine_generate_lookup
  * is available -- a single-device engine with return_output_tensors = false), "logit_processors" (0 / 1: ifa_engine_add_query_opt accepts
  * penalties and a logit_bias -- the same condition), "processed_steps" (steps, one per query per step, whose pool was built from a
- * row the logit processors had rewritten); -1 if unknown */
+ * row the logit processors had rewritten), "context_shift" (0 / 1: queries run past max_context_len by default -- the .ini key
+ * `context_shift = true` on a single-device engine with return_output_tensors = false; elsewhere the key is accepted and this stays
+ * 0), "context_shift_available" (0 / 1: that condition without the key: ifa_engine_shift_query and a per-query context_shift = 1
+ * work), "context_shifts" (shifts so far, automatic and explicit), "context_shift_tokens" (the tokens they dropped); -1 if unknown */
 int ifa_engine_model_info(ifa_engine *e, const char *key);
 /* prompt prefix cache: the leading prompt tokens of query_id whose K/V rows AddQuery found in a slot (the query's first Infer runs
  * only the rest; QueryInferenceResult::prefix_len reports the same number); 0 without a hit or with the cache off, -1 unknown id */
 int ifa_engine_query_cached_tokens(ifa_engine *e, int query_id);
+/* Context shift (.ini: `context_shift = false`, `context_shift_keep = 4`; DESIGN.md "Context shift").  A query whose tokens reach
+ * max_context_len is normally ended by ifa_engine_infer without an item.  With the shift on for it, the engine instead keeps its
+ * first `keep` cache rows, drops the block of the oldest rows behind them and moves the rest down on the device (ifa_model_kv_shift:
+ * the moved K rows are re-rotated to their new positions), erases the dropped tokens from the query and goes on; ifa_engine_generate
+ * and ifa_engine_generate_lookup then accept runs that cross the limit and shift where the Infer / Commit loop would.  An
+ * approximation by design: rows of layers above the first were computed while the dropped tokens were visible.  A shifted query
+ * leaves only its kept rows to the prompt prefix cache; its logit processors go on counting the dropped tokens.
+ * ifa_context_shift_plan (host-only) is the policy: 0 while n_tokens < max_ctx (or nothing behind `keep` is processed), else 1 with
+ * out2 = {keep, discard}, discard = max(1, (processed - keep + 1) / 2) -- the older half, rounded up, so that the rows that move
+ * never outnumber the dropped ones; -1: bad arguments (n_tokens > max_ctx, processed > n_tokens, keep outside 0 .. max_ctx / 2 ...).
+ * ifa_engine_shift_query is the same shift with the caller's own numbers (dropping one old chat turn, say): keep >= 0, discard >= 1,
+ * keep + discard <= the query's processed tokens, the query not ended, "context_shift_available" = 1; 1 ok, 0 failure with a message.
+ * ifa_engine_query_shifted_tokens: the tokens query_id has dropped so far; -1 unknown id. */
+int ifa_context_shift_plan(int n_tokens, int processed, int max_ctx, int keep, int *out2);
+int ifa_engine_shift_query(ifa_engine *e, int query_id, int keep, int discard);
+int ifa_engine_query_shifted_tokens(ifa_engine *e, int query_id);
 /* host-only: the cache's slot / reuse policy (host/prefix_cache.h).  Slot i holds the rows of record_lens[i] token ids -- the
  * records lie back to back in records_flat --, is busy (busy[i] != 0: a running query owns it) or free, and was last used at
  * stamps[i].  Match = common prefix of prompt and record, at most n_prompt - 1; the longest wins (ties: free before busy, then the
@@ -206,7 +229,8 @@ int ifa_service_selftest_loop(int max_ctx, int max_queries, int fail_at_infer_ca
  * payloads], final: the final message} with time_cost zeroed.  The body's fields are the service's: prompt_token_ids, max_output_len /
  * max_tokens, is_streaming_mode / stream, "logprobs": true, "top_logprobs": n (0..20), "repetition_penalty" (> 0), "presence_penalty" /
  * "frequency_penalty" (-2..2), "logit_bias": {"<id>": value in -100..100} (at most 300 entries) ... -- the loopback engine has no
- * logit processors: a request with them is answered "error.unsupported" */
+ * logit processors: a request with them is answered "error.unsupported"; "context_shift": bool and "context_keep": int (>= 0) go to
+ * the query's options -- the loopback engine cannot shift: "context_shift": true is answered "error.unsupported" */
 int ifa_service_selftest_request(const char *body, int is_openai_mode, int max_ctx, char *out_json, size_t cap);
 
 #ifdef __cplusplus

@@ -118,6 +118,8 @@ SIGNATURES = {
     "ifa_model_kv_slots": (_i, [_vp, _i]),
     "ifa_model_select_kv": (_i, [_vp, _i]),
     "ifa_model_kv_copy": (_i, [_vp, _i, _i, _i]),
+    "ifa_model_kv_shift": (_i, [_vp, _i, _i, _i, _i]),
+    "ifa_kv_shift_rows": (_i, [_i, _vp, _vp, _sz, _sz, _i, _i, _vp, _sz, _sz, _sz, _vp]),
     "ifa_model_decode_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ifa_model_decode_draft": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
     "ifa_model_set_pool_excluded": (_i, [_vp, _vp, _i]),
@@ -202,6 +204,9 @@ ENGINE_SIGNATURES = {
     "ifa_perplexity_token_nll": (C.c_double, [_vp, _i, _i]),
     "ifa_engine_model_info": (_i, [_vp, C.c_char_p]),
     "ifa_engine_query_cached_tokens": (_i, [_vp, _i]),
+    "ifa_context_shift_plan": (_i, [_i, _i, _i, _i, _ip]),
+    "ifa_engine_shift_query": (_i, [_vp, _i, _i, _i]),
+    "ifa_engine_query_shifted_tokens": (_i, [_vp, _i]),
     "ifa_prefix_cache_plan": (_i, [_ip, _ip, _ip, C.POINTER(C.c_longlong), _i, _ip, _i, _i, _ip]),
     "ifa_step_plan_query": (_i, [_i, _i, _i, _i, _i, _ip]),
     "ifa_step_plan_batch": (_i, [_i, _ip, _i, _ip, _ip]),
@@ -222,6 +227,12 @@ class QueryOptions(C.Structure):
                 ("logprobs", C.c_int), ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float),
                 ("frequency_penalty", C.c_float), ("n_logit_bias", C.c_int), ("logit_bias_ids", C.POINTER(C.c_int)),
                 ("logit_bias_values", C.POINTER(C.c_float))]
+
+
+class QueryOptionsShift(C.Structure):
+    """ifa_query_options as it has grown: the fields of QueryOptions, then context_shift / context_keep (-1: the engine's keys).
+    QueryOptions stays the shorter, earlier struct -- struct_size tells the library which one it was handed."""
+    _fields_ = QueryOptions._fields_ + [("context_shift", C.c_int), ("context_keep", C.c_int)]
 
 
 class ModelConfig(C.Structure):

@@ -251,6 +251,7 @@ struct ifa_model : Scratch {
     DevPin<void *> kvc_tab;
     std::vector<void *> kvc_tab_host;          // what the device table holds
     std::vector<DevPin<void *>> kvc_retired;   // replaced tables
+    DevBuf<float> kvs_rot;                     // context shift (ifa_model_kv_shift, ifa_kv_shift.hip): [head_dim / 2] (cos, sin) of the last call's rotation
     static constexpr int RING = 1024;
 };
 
@@ -343,6 +344,8 @@ struct PerfSpan {
     void done() { if (idx >= 0) { perf_end(m, idx); idx = -1; } }
 };
 void *kv_ptr(ifa_model *m, size_t layer, int slot, bool is_v);
+// ---- ifa_kv_copy.hip: the device table of every slot's K / V buffers lists what slots a and b have now (restaged on the model's stream if not)
+int kv_copy_table(ifa_model *m, int a, int b);
 int ensure_mo(ifa_model *m);
 int ensure_mo_build(ifa_model *m);
 int ensure_x32(ifa_model *m);

@@ -45,7 +45,7 @@ __global__ __launch_bounds__(KVC_THREADS) void k_kv_copy(void *const *src_tab, v
 }
 
 // the device table lists the buffers slots `a` and `b` have now; if not, a new table of all slots is staged on the model's stream
-static int kv_copy_table(ifa_model *m, int a, int b)
+int kv_copy_table(ifa_model *m, int a, int b)
 {
     const size_t L = m->layers.size(), n_slots = std::max<size_t>(m->slots.size(), 1);
     bool ok = m->kvc_tab.dev && m->kvc_tab_host.size() == n_slots * 2 * L;

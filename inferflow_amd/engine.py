@@ -46,20 +46,23 @@ class InferenceEngine:
             pass
 
     def add_query(self, tokens, strategy=None, seed=0, temperature=1.0, logprobs=-1, repetition_penalty=1.0, presence_penalty=0.0,
-                  frequency_penalty=0.0, logit_bias=None):
+                  frequency_penalty=0.0, logit_bias=None, context_shift=None, context_keep=None):
         """strategy: None (the model's default) or a name / SamplingStrategyId ("sample.top_p", "greedy", 1 ...).
         logprobs: -1 off; 0: the chosen token's log-probability; 1..20: also the n most probable tokens (last_logprobs).
         repetition_penalty (HF rule, prompt + generated ids), presence_penalty / frequency_penalty (OpenAI rule, generated ids),
         logit_bias ({token id: value}, -inf bans the id): logit processors applied on the device in front of the candidate pool
-        (include/inferflow_engine.h, ifa_engine_add_query_opt); a query with any of them takes the device pool route."""
+        (include/inferflow_engine.h, ifa_engine_add_query_opt); a query with any of them takes the device pool route.
+        context_shift: None (the engine's `context_shift` key), False, True -- the query runs past max_context_len by dropping old
+        cache rows; context_keep: None (the engine's `context_shift_keep`) or the rows kept in front of the dropped block."""
         arr = (C.c_int * len(tokens))(*[int(t) for t in tokens])
-        if repetition_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0 or logit_bias:
+        if repetition_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0 or logit_bias or context_shift is not None or context_keep is not None:
             sid = 0 if strategy is None else (strategy if isinstance(strategy, int) else self.strategy_id(strategy))
             bias = sorted((logit_bias or {}).items())
             ids = (C.c_int * max(1, len(bias)))(*[int(k) for k, _ in bias])
             vals = (C.c_float * max(1, len(bias)))(*[float(v) for _, v in bias])
-            opt = _capi.QueryOptions(C.sizeof(_capi.QueryOptions), int(sid), int(seed), float(temperature), int(logprobs), float(repetition_penalty),
-                                     float(presence_penalty), float(frequency_penalty), len(bias), ids, vals)
+            opt = _capi.QueryOptionsShift(C.sizeof(_capi.QueryOptionsShift), int(sid), int(seed), float(temperature), int(logprobs), float(repetition_penalty),
+                                          float(presence_penalty), float(frequency_penalty), len(bias), ids, vals,
+                                          -1 if context_shift is None else int(bool(context_shift)), -1 if context_keep is None else int(context_keep))
             return _capi.lib().ifa_engine_add_query_opt(self._h, arr, len(tokens), C.byref(opt))
         if logprobs != -1:
             sid = 0 if strategy is None else (strategy if isinstance(strategy, int) else self.strategy_id(strategy))
@@ -168,6 +171,16 @@ class InferenceEngine:
         """Leading prompt tokens whose K/V rows add_query found in a slot (prefix_cache = true in the .ini); -1: unknown id"""
         return _capi.lib().ifa_engine_query_cached_tokens(self._h, int(query_id))
 
+    def shift_query(self, query_id, keep, discard):
+        """Context shift with the caller's numbers: tokens [keep, keep + discard) of the query and their cache rows are dropped, the
+        rows behind them move down (InferenceEngine::ShiftQuery)"""
+        if not _capi.lib().ifa_engine_shift_query(self._h, int(query_id), int(keep), int(discard)):
+            raise EngineError("ShiftQuery failed: " + self._err())
+
+    def query_shifted_tokens(self, query_id):
+        """Tokens the query's context shifts have dropped so far; -1: unknown id"""
+        return _capi.lib().ifa_engine_query_shifted_tokens(self._h, int(query_id))
+
     def prefix_cache_stats(self):
         """{active, hits, tokens, copies} of the prompt prefix cache (model_info keys prefix_cache*)"""
         return {k: self.model_info("prefix_cache" + ("_" + k if k != "active" else "")) for k in ("active", "hits", "tokens", "copies")}
@@ -267,3 +280,10 @@ def random_doubles(seed, n):
     out = (C.c_double * n)()
     _capi.lib().ifa_sampling_random_doubles(int(seed), n, out)
     return [out[i] for i in range(n)]
+
+
+def context_shift_plan(n_tokens, processed, max_ctx, keep):
+    """Host-only: the context shift's policy (ifa_context_shift_plan): None for bad arguments, () for no shift, else (keep, discard)"""
+    out = (C.c_int * 2)()
+    rc = _capi.lib().ifa_context_shift_plan(int(n_tokens), int(processed), int(max_ctx), int(keep), out)
+    return None if rc < 0 else (() if rc == 0 else (out[0], out[1]))

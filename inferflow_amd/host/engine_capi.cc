@@ -13,6 +13,7 @@
 #include "prefix_cache.h"
 #include "step_plan.h"
 #include "lookup_draft.h"
+#include "context_shift.h"
 #include "half_bits.h"
 
 using namespace inferflow_amd;
@@ -65,12 +66,13 @@ int ifa_engine_add_query_opt(ifa_engine *e, const int *tokens, int n_tokens, con
     if (o->struct_size < sizeof(size_t)) { EngineSetError("ifa_engine_add_query_opt: struct_size %zu", o->struct_size); return -1; }
     ifa_query_options v;           // the caller's leading struct_size bytes over the defaults
     memset(&v, 0, sizeof v);
-    v.temperature = 1.0f; v.logprobs = -1; v.repetition_penalty = 1.0f;
+    v.temperature = 1.0f; v.logprobs = -1; v.repetition_penalty = 1.0f; v.context_shift = -1; v.context_keep = -1;
     memcpy(&v, o, std::min(o->struct_size, sizeof v));
     if (v.n_logit_bias < 0 || (v.n_logit_bias > 0 && (!v.logit_bias_ids || !v.logit_bias_values))) { EngineSetError("ifa_engine_add_query_opt: %d logit_bias entries without arrays", v.n_logit_bias); return -1; }
     QueryOptions opt; opt.strategy_id = v.strategy_id; opt.random_seed = v.random_seed; opt.temperature = v.temperature; opt.logprobs = v.logprobs;
     opt.repetition_penalty = v.repetition_penalty; opt.presence_penalty = v.presence_penalty; opt.frequency_penalty = v.frequency_penalty;
     for (int i = 0; i < v.n_logit_bias; i++) opt.logit_bias.emplace_back(v.logit_bias_ids[i], v.logit_bias_values[i]);
+    opt.context_shift = v.context_shift; opt.context_keep = v.context_keep;
     return e->engine.AddQuery(std::vector<int>(tokens, tokens + n_tokens), opt);
 }
 
@@ -316,11 +318,33 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "lookup_decoding") return e->engine.lookup_decoding_active() ? 1 : 0;
     if (k == "logit_processors") return e->engine.SupportsLogitProcessors() ? 1 : 0;
     if (k == "processed_steps") return (int)std::min<long long>(e->engine.processed_steps(), 0x7FFFFFFF);
+    if (k == "context_shift") return e->engine.ShiftsContext() ? 1 : 0;
+    if (k == "context_shift_available") return e->engine.SupportsContextShift() ? 1 : 0;
+    if (k == "context_shifts") return (int)std::min<long long>(e->engine.context_shifts(), 0x7FFFFFFF);
+    if (k == "context_shift_tokens") return (int)std::min<long long>(e->engine.context_shift_tokens(), 0x7FFFFFFF);
     if (k == "prefix_cache_copies") return (int)std::min<long long>(e->engine.prefix_cache_copies(), 0x7FFFFFFF);
     return -1;
 }
 
 int ifa_engine_query_cached_tokens(ifa_engine *e, int query_id) { return e ? e->engine.QueryCachedTokens(query_id) : -1; }
+
+int ifa_engine_query_shifted_tokens(ifa_engine *e, int query_id) { return e ? e->engine.QueryShiftedTokens(query_id) : -1; }
+
+int ifa_engine_shift_query(ifa_engine *e, int query_id, int keep, int discard)
+{
+    if (!e) { EngineSetError("ifa_engine_shift_query: null engine"); return 0; }
+    return e->engine.ShiftQuery(query_id, keep, discard) ? 1 : 0;
+}
+
+// host-only: the context shift's policy (host/context_shift.h)
+int ifa_context_shift_plan(int n_tokens, int processed, int max_ctx, int keep, int *out2)
+{
+    ContextShiftPlan plan;
+    if (!out2 || !PlanContextShift(n_tokens, processed, max_ctx, keep, plan)) { EngineSetError("ifa_context_shift_plan: bad arguments"); return -1; }
+    if (!plan.shift) return 0;
+    out2[0] = plan.keep; out2[1] = plan.discard;
+    return 1;
+}
 
 // host-only: the slot / reuse plan of the prompt prefix cache (host/prefix_cache.h)
 int ifa_prefix_cache_plan(const int *records_flat, const int *record_lens, const int *busy, const long long *stamps, int n_slots,

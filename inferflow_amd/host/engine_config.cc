@@ -122,6 +122,9 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "prefix_cache", config.prefix_cache);
     cfg.GetItem(section, "prefix_cache_min_tokens", config.prefix_cache_min_tokens);
     if (config.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config.prefix_cache_min_tokens); return false; }
+    cfg.GetItem(section, "context_shift", config.context_shift);
+    cfg.GetItem(section, "context_shift_keep", config.context_shift_keep);
+    if (config.context_shift_keep < 0) { EngineSetError("context_shift_keep must be at least 0 (got %d)", config.context_shift_keep); return false; }
     cfg.GetItem(section, "lookup_draft_len", config.lookup_draft_len);
     cfg.GetItem(section, "lookup_ngram_max", config.lookup_ngram_max);
     cfg.GetItem(section, "lookup_ngram_min", config.lookup_ngram_min);

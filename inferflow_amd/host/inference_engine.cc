@@ -12,6 +12,7 @@
 #include "step_plan.h"
 #include "prefix_cache.h"
 #include "lookup_draft.h"
+#include "context_shift.h"
 #include "half_bits.h"
 
 namespace inferflow_amd {
@@ -28,6 +29,7 @@ void InferenceEngine::Clear()
     prefix_active_ = false; slot_records_.clear();
     use_clock_ = prefix_hits_ = prefix_tokens_ = prefix_copies_ = 0;
     processed_steps_ = 0;
+    shift_active_ = false; context_shifts_ = context_shift_tokens_ = 0;
 }
 
 bool InferenceEngine::Init(const InferenceConfig &cfg)
@@ -89,6 +91,11 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
     if (config_.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config_.prefix_cache_min_tokens); Clear(); return false; }
     prefix_active_ = config_.prefix_cache && !multi_ && !config_.return_output_tensors;
     if (!LookupConfigOk(config_)) { Clear(); return false; }
+    if (config_.context_shift_keep < 0) { EngineSetError("context_shift_keep must be at least 0 (got %d)", config_.context_shift_keep); Clear(); return false; }
+    if (config_.context_shift && config_.context_shift_keep > MaxContextLen() / 2) {
+        EngineSetError("context_shift_keep %d exceeds half of max_context_len %d", config_.context_shift_keep, MaxContextLen()); Clear(); return false;
+    }
+    shift_active_ = config_.context_shift && SupportsContextShift();
     if (prefix_active_) slot_records_.assign((size_t)kv_slots_, SlotRecord());
     return true;
 }
@@ -124,8 +131,14 @@ int InferenceEngine::AddQuery(const std::vector<int> &tokens, const QueryOptions
         std::sort(seen.begin(), seen.end());
         for (size_t i = 1; i < seen.size(); i++) if (seen[i] == seen[i - 1]) { EngineSetError("logit_bias id %d is given twice", seen[i]); return -1; }
     }
+    if (query_options.context_shift < -1 || query_options.context_shift > 1) { EngineSetError("context_shift %d is outside -1..1", query_options.context_shift); return -1; }
+    if (query_options.context_keep < -1) { EngineSetError("context_keep %d is below -1", query_options.context_keep); return -1; }
+    if (query_options.context_shift == 1 && !SupportsContextShift()) { EngineSetError("context shift is not available on a multi-device engine or with return_output_tensors = true"); return -1; }
+    const bool shift_on = query_options.context_shift == -1 ? shift_active_ : query_options.context_shift == 1;
+    const int shift_keep = query_options.context_keep >= 0 ? query_options.context_keep : config_.context_shift_keep;
+    if (query_options.context_keep > max_ctx / 2 || (shift_on && shift_keep > max_ctx / 2)) { EngineSetError("context_keep %d exceeds half of max_context_len %d", shift_keep, max_ctx); return -1; }
     if ((int)queries_.size() >= std::min(config_.max_concurrent_queries, kv_slots_)) return 0;      // busy
-    Query q; q.id = next_query_id_++; q.tokens = tokens; q.options = query_options;
+    Query q; q.id = next_query_id_++; q.shift_on = shift_on; q.shift_keep = shift_keep; q.tokens = tokens; q.options = query_options;
     q.strategy = strategy; q.sampling = default_sampling_;
     if (query_options.random_seed != 0) q.rng.SetSeed((uint64_t)(int64_t)query_options.random_seed);    // SamplingStrategy::BeginQuery
     if (query_options.logprobs >= 0 && PoolK(q) > IFA_POOL_MAX) {      // (its steps could not end in a device pool: no logprobs would come back)
@@ -163,7 +176,7 @@ bool InferenceEngine::PlaceQuery(Query &q)
     }
     for (const auto &kv : queries_) {      // a running query's rows: what it has processed so far
         PrefixSlotView &v = views[(size_t)kv.second.kv_slot];
-        v.busy = true; v.record = kv.second.tokens.data(); v.record_len = std::min(kv.second.processed, (int)kv.second.tokens.size());
+        v.busy = true; v.record = kv.second.tokens.data(); v.record_len = ExactRows(kv.second);      // (a shifted query: its kept rows only)
     }
     PrefixPlan plan;
     if (!PlanPrefixReuse(views, q.tokens.data(), (int)q.tokens.size(), config_.prefix_cache_min_tokens, plan)) {
@@ -303,7 +316,7 @@ bool InferenceEngine::RemoveQuery(int query_id)
     if (prefix_active_) {            // the freed slot keeps the rows of the tokens the query has processed
         const Query &q = it->second;
         SlotRecord &r = slot_records_[(size_t)q.kv_slot];
-        r.tokens.assign(q.tokens.begin(), q.tokens.begin() + std::min(q.processed, (int)q.tokens.size()));
+        r.tokens.assign(q.tokens.begin(), q.tokens.begin() + ExactRows(q));      // (a shifted query: its kept rows only)
         r.stamp = ++use_clock_;
     }
     queries_.erase(it);
@@ -518,6 +531,58 @@ bool InferenceEngine::CountCommitted()
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------- context shift
+int InferenceEngine::QueryShiftedTokens(int query_id) const
+{
+    auto it = queries_.find(query_id);
+    return it == queries_.end() ? -1 : it->second.shifted_tokens;
+}
+
+// The device call is enqueue-only on the worker's stream, in front of the step's launches.  The query's device logit-processor state
+// is left alone: penalties go on counting the dropped tokens (DESIGN.md "Context shift").
+bool InferenceEngine::ApplyShift(Query &q, int keep, int discard)
+{
+    if (ifa_model_kv_shift(model_, q.kv_slot, keep, discard, q.processed) != IFA_OK) {
+        EngineSetError("context shift of query %d (keep %d, discard %d, %d rows) failed: %s", q.id, keep, discard, q.processed, ifa_last_error()); return false;
+    }
+    q.tokens.erase(q.tokens.begin() + keep, q.tokens.begin() + keep + discard);
+    q.processed -= discard;
+    q.counted -= std::max(0, std::min(q.counted, keep + discard) - keep);      // the erased tokens that lay below it
+    q.exact_rows = std::min(q.exact_rows, keep);
+    q.shifted_tokens += discard;
+    context_shifts_++; context_shift_tokens_ += discard;
+    return true;
+}
+
+bool InferenceEngine::ShiftIfFull(Query &q)
+{
+    if (!q.shift_on || q.ended) return true;
+    ContextShiftPlan plan;
+    if (!PlanContextShift((int)q.tokens.size(), q.processed, MaxContextLen(), q.shift_keep, plan)) {
+        EngineSetError("context shift of query %d: %zu tokens, %d processed, keep %d", q.id, q.tokens.size(), q.processed, q.shift_keep); return false;
+    }
+    return !plan.shift || ApplyShift(q, plan.keep, plan.discard);
+}
+
+bool InferenceEngine::ShiftFullQueries()
+{
+    if (multi_) return true;
+    for (auto &kv : queries_) if (!ShiftIfFull(kv.second)) return false;
+    return true;
+}
+
+bool InferenceEngine::ShiftQuery(int query_id, int keep, int discard)
+{
+    Query *qp = FindQuery(query_id);
+    if (!qp) return false;
+    if (!SupportsContextShift()) { EngineSetError("ShiftQuery: context shift is not available on a multi-device engine or with return_output_tensors = true"); return false; }
+    if (qp->ended) { EngineSetError("ShiftQuery: query %d has ended", query_id); return false; }
+    if (keep < 0 || discard < 1 || (long long)keep + discard > qp->processed) {
+        EngineSetError("ShiftQuery: keep %d + discard %d of the %d processed tokens of query %d", keep, discard, qp->processed, query_id); return false;
+    }
+    return ApplyShift(*qp, keep, discard);
+}
+
 bool InferenceEngine::Infer(InferenceResult &res)
 {
     res.items.clear(); res.perf_stat.time_map.clear();
@@ -525,6 +590,7 @@ bool InferenceEngine::Infer(InferenceResult &res)
     const auto t0 = std::chrono::steady_clock::now();
     const int max_ctx = MaxContextLen();
     if (!CountCommitted()) return false;
+    if (!ShiftFullQueries()) return false;       // in front of the batch: the batched step and InferQuery both see the shifted query
     std::vector<Query *> batch;
     // (a partition with several layer groups steps its queries one by one: a batched step is one tensor-parallel group's)
     if (LayerGroups() == 1)
@@ -586,7 +652,7 @@ bool InferenceEngine::DeviceGreedyOk(const Query &q, int n_new, bool lookup)
     else if (q.strategy != SamplingStrategyId::Greedy)
         EngineSetError(lookup ? "GenerateLookup() decodes greedily on the device; query %d uses strategy %d (use Infer / CommitInferenceResult)"
                               : "Generate() decodes greedily on the device; query %d uses strategy %d (use Infer / CommitInferenceResult)", q.id, (int)q.strategy);
-    else if ((int)q.tokens.size() + n_new > MaxContextLen())
+    else if (!q.shift_on && (int)q.tokens.size() + n_new > MaxContextLen())      // (with the context shift on the run is split at the limit)
         EngineSetError(lookup ? "GenerateLookup: %zu tokens + %d new tokens exceed max_context_len %d" : "Generate: %zu tokens + %d steps exceed max_context_len %d", q.tokens.size(), n_new, MaxContextLen());
     else return true;
     return false;
@@ -623,10 +689,14 @@ bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_
     Query &q = *qp;
     if (!DeviceGreedyOk(q, n_steps, false)) return false;
     if (!multi_ && ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
+    if (!ShiftIfFull(q)) return false;
     if (!PrefillPending(q, new_tokens, n_steps, nullptr)) return false;
     float ms_total = 0;
     while (n_steps > 0) {                              // the device token ring holds 1024 steps per call
-        const int k = std::min(n_steps, 1024);
+        // context shift: run to the limit, shift where Infer would (tokens == max_context_len, in front of the step), continue
+        if (!ShiftIfFull(q)) return false;
+        const int k = q.shift_on ? std::min(std::min(n_steps, 1024), MaxContextLen() - (int)q.tokens.size()) : std::min(n_steps, 1024);
+        if (k < 1) { EngineSetError("Generate: query %d is at max_context_len %d with nothing to drop behind its %d kept rows", q.id, MaxContextLen(), q.shift_keep); return false; }
         std::vector<int> out((size_t)k);
         float ms = 0;
         if (multi_) { if (!MultiDecode(q, k, out.data(), &ms)) return false; }
@@ -656,6 +726,7 @@ bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vect
     if (ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
     const int max_ctx = MaxContextLen();
     int left = max_new_tokens;
+    if (!ShiftIfFull(q)) return false;
     if (!PrefillPending(q, new_tokens, left, &st)) return false;
     const int *pred = prediction && !prediction->empty() ? prediction->data() : nullptr;
     const int n_pred = pred ? (int)prediction->size() : 0;
@@ -663,8 +734,11 @@ bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vect
     while (left > 0) {
         // here q.tokens.size() == q.processed + 1: the last token is committed, its K/V row is not in the cache yet.  A draft step
         // writes rows q.processed .. q.processed + m and may emit m + 1 tokens: m stays inside the request and the context
+        // With the context shift on, the shift runs where Infer would and a draft step also leaves tokens <= max_context_len
+        if (!ShiftIfFull(q)) { if (stats) *stats = st; return false; }
+        if ((int)q.tokens.size() >= max_ctx) { EngineSetError("GenerateLookup: query %d is at max_context_len %d with nothing to drop behind its %d kept rows", q.id, max_ctx, q.shift_keep); if (stats) *stats = st; return false; }
         const int pos0 = q.processed;
-        const int m_max = std::min(std::min(config_.lookup_draft_len, left - 1), max_ctx - pos0 - 1);
+        const int m_max = std::min(std::min(config_.lookup_draft_len, left - 1), max_ctx - pos0 - 1 - (q.shift_on ? 1 : 0));
         const int m = m_max >= 1 ? LookupDraft(q.tokens.data(), (int)q.tokens.size(), pred, n_pred, config_.lookup_ngram_max, config_.lookup_ngram_min, m_max, row + 1) : 0;
         if (m < 0) { EngineSetError("GenerateLookup: draft lookup failed"); return false; }
         st.steps++;

@@ -12,6 +12,7 @@
 // the exchanges through the C ABI collectives (RCCL).  Tokenizers, prompt templates and the HTTP service are outside
 // the hot path.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -115,6 +116,14 @@ struct InferenceConfig {
     // (host/lookup_draft.h).  Applies to a single-device engine with return_output_tensors = false; elsewhere the keys are accepted
     // and GenerateLookup is refused (model_info "lookup_decoding" = 0).
     int lookup_draft_len = 4, lookup_ngram_max = 3, lookup_ngram_min = 1;
+    // extension: context shift (host/context_shift.h; DESIGN.md "Context shift").  A query whose tokens reach max_context_len does not
+    // end: the engine keeps its first context_shift_keep cache rows, drops the older half of the rows behind them and moves the rest
+    // down on the device (ifa_model_kv_shift: K rows re-rotated to their new positions), then goes on.  An approximation by design
+    // -- rows of layers above the first were computed while the dropped tokens were still visible -- hence opt-in.  Applies to a
+    // single-device engine with return_output_tensors = false; elsewhere the keys are accepted and the shift stays off (model_info
+    // "context_shift" = 0).  QueryOptions::context_shift / context_keep override both per query.
+    bool context_shift = false;
+    int context_shift_keep = 4;
     DebugOptions debug;
 };
 
@@ -139,6 +148,9 @@ struct QueryOptions {               // SamplingStrategy::QueryOptions (sampling_
     float repetition_penalty = 1.0f, presence_penalty = 0.0f, frequency_penalty = 0.0f;
     std::vector<std::pair<int, float>> logit_bias;
     static const int MAX_LOGIT_BIAS = 1024;
+    // extension: context shift for this query.  context_shift: -1 the engine's key, 0 off, 1 on (refused where the engine cannot shift);
+    // context_keep: -1 the engine's context_shift_keep, else the rows kept in front of the dropped block (0 .. max_context_len / 2)
+    int context_shift = -1, context_keep = -1;
     bool Processed() const { return repetition_penalty != 1.0f || presence_penalty != 0.0f || frequency_penalty != 0.0f || !logit_bias.empty(); }
 };
 
@@ -189,6 +201,10 @@ public:
     virtual bool SupportsLogprobs() const { return false; }
     // whether AddQuery accepts a processed query (QueryOptions::Processed(); the service answers "error.unsupported" otherwise)
     virtual bool SupportsLogitProcessors() const { return false; }
+    // context shift: whether queries run past max_context_len by default (the service then does not cut max_output_len down to the
+    // room behind the prompt), and whether AddQuery accepts QueryOptions::context_shift = 1 at all
+    virtual bool ShiftsContext() const { return false; }
+    virtual bool SupportsContextShift() const { return false; }
 };
 
 class InferenceEngine : public QueryEngine {
@@ -207,7 +223,8 @@ public:
     int AddQuery(const std::vector<int> &tokens, const QueryOptions &query_options) override;
     int QueryCount() const override;
     // one step for every active query: prefill of the pending tokens, or one decode step.  A query whose context is full
-    // (tokens == max_context_len) is marked ended and gets NO item (QueryEnded tells the caller).
+    // (tokens == max_context_len) is marked ended and gets NO item (QueryEnded tells the caller) -- unless the context shift is on
+    // for it: then the shift runs in front of the step and the query goes on.
     bool Infer(InferenceResult &res) override;
     bool CommitInferenceResult(const std::map<int, QueryNextToken> &query_map) override;
     bool RemoveQuery(int query_id) override;
@@ -217,6 +234,16 @@ public:
     int VocabSize() const override { return spec_.hyper_params.vocab_size; }
     bool SupportsLogprobs() const override { return model_ && !multi_ && !config_.return_output_tensors; }
     bool SupportsLogitProcessors() const override { return model_ && !multi_ && !config_.return_output_tensors; }
+    bool ShiftsContext() const override { return shift_active_; }
+    bool SupportsContextShift() const override { return model_ && !multi_ && !config_.return_output_tensors; }
+    // context shifts so far and the tokens they dropped; the tokens query_id has dropped (-1: unknown id)
+    long long context_shifts() const { return context_shifts_; }
+    long long context_shift_tokens() const { return context_shift_tokens_; }
+    int QueryShiftedTokens(int query_id) const;
+    // Extension: a context shift with the caller's own policy (dropping one old chat turn, say): tokens [keep, keep + discard) of the
+    // query and their cache rows go, the rows behind them move down.  keep >= 0, discard >= 1, keep + discard <= the query's
+    // processed tokens, the query not ended; on any engine where SupportsContextShift(), whatever the context_shift key says.
+    bool ShiftQuery(int query_id, int keep, int discard);
     // steps (one per query per step) whose pool was built from a row the logit processors had rewritten
     long long processed_steps() const { return processed_steps_; }
 
@@ -282,6 +309,11 @@ private:
         bool ended = false;
         int kv_slot = 0;            // this query's KV cache inside the worker (ifa_model_select_kv)
         int cached_tokens = 0;      // rows the prefix cache supplied at AddQuery (processed started there)
+        // context shift: on for this query, its kept rows, the tokens dropped so far.  exact_rows: cache rows [0, min(processed,
+        // exact_rows)) hold exactly tokens[0 ..) at their positions -- everything until the first shift, the kept rows afterwards
+        // (the moved rows were computed behind tokens that are gone: no other prompt's rows) -- what the prefix cache may record
+        bool shift_on = false;
+        int shift_keep = 0, shifted_tokens = 0, exact_rows = 0x7FFFFFFF;
         int counted = 0;            // a processed query: tokens[0 .. counted) are in its device logit state (the prompt, then the generated ones)
         SamplingStrategyId strategy = SamplingStrategyId::Greedy;
         StdSamplingConfig sampling; // per query copy, like StdQueryData::config
@@ -294,6 +326,10 @@ private:
     // adj_slots: empty, or per pool row of the plan the state slot of a processed query (-1: the row stays raw)
     bool BatchStep(const std::vector<int> &toks, const std::vector<int> &pos, const std::vector<int> &slots, std::vector<int> &next,
                    const BatchStepPlan &plan, const std::vector<int> &adj_slots, BatchPools &pools, std::vector<uint16_t> &all);
+    bool ShiftFullQueries();        // the shift pass of Infer: every query with the shift on whose tokens have reached max_context_len
+    bool ShiftIfFull(Query &q);
+    bool ApplyShift(Query &q, int keep, int discard);      // device rows first, then the query's books; false: nothing changed
+    int ExactRows(const Query &q) const { return std::max(0, std::min(std::min(q.processed, (int)q.tokens.size()), q.exact_rows)); }
     bool CountCommitted();          // the tokens processed queries have committed since the last step -> their device counts, one call
     bool InferQuery(Query &q, InferenceResult &res);                                // one query's own step
     bool PoolStep(Query &q, int n_new, QueryInferenceResult &item);
@@ -339,6 +375,8 @@ private:
     void *logits_dev_ = nullptr;
     size_t logits_rows_ = 0;
     long long sampled_fused_steps_ = 0, processed_steps_ = 0;
+    bool shift_active_ = false;     // the context_shift key on an engine that can shift
+    long long context_shifts_ = 0, context_shift_tokens_ = 0;
     bool pool_lse_on_ = false;      // the worker's option pool_lse as last set
     // ---- prompt prefix cache.  Record invariant: rows [0, tokens.size()) of a FREE slot's K and V hold exactly these token ids at
     // these positions.  A busy slot's record is implicit (its query's tokens[0 .. processed)); RemoveQuery turns it into the stored

@@ -90,6 +90,8 @@ std::string InferFlowRequest::ProcessorsJson() const
         }
         s += "}";
     }
+    if (has_context_shift) s += std::string(", \"context_shift\": ") + (context_shift ? "true" : "false");
+    if (has_context_keep) s += ", \"context_keep\": " + std::to_string(context_keep);
     return s;
 }
 
@@ -156,6 +158,11 @@ bool InferFlowServiceCore::ParseRequest(InferFlowRequest &r, const std::string &
     if (!ReadPenalty(root, "repetition_penalty", 0.0f, std::numeric_limits<float>::max(), true, r.repetition_penalty, r.has_repetition_penalty)
         || !ReadPenalty(root, "presence_penalty", -2.0f, 2.0f, false, r.presence_penalty, r.has_presence_penalty)
         || !ReadPenalty(root, "frequency_penalty", -2.0f, 2.0f, false, r.frequency_penalty, r.has_frequency_penalty)) { if (err) *err = "error.invalid_penalty"; return false; }
+    if (root.Get("context_shift")) { if (!root.GetBool("context_shift", r.context_shift)) { if (err) *err = "error.invalid_context_shift"; return false; } r.has_context_shift = true; }
+    if (const JsonValue *ck = root.Get("context_keep")) {
+        if (ck->type != JsonValue::Number || !(ck->num >= 0.0 && ck->num <= 1e9) || ck->num != (double)(int)ck->num) { if (err) *err = "error.invalid_context_shift"; return false; }
+        r.context_keep = (int)ck->num; r.has_context_keep = true;
+    }
     if (!ReadLogitBias(root, r)) { r.logit_bias.clear(); if (err) *err = "error.invalid_logit_bias"; return false; }
     return true;
 }
@@ -236,7 +243,11 @@ bool InferFlowServiceCore::ProcessQuery(InferFlowResponseChunk &result, const In
     //  bound as InferenceEngine::AddQuery / Infer -- a prompt of max_ctx - 1 tokens is accepted and yields one token)
     const int room = max_ctx - (int)request.prompt_token_ids.size();
     if (room < 1) { result.ret_code = "error.too_long_request"; return false; }
-    const int max_len = request.max_output_len > 0 ? std::min(request.max_output_len, room) : room;
+    // With the context shift on for the query it runs past the limit: a positive max_output_len stands as it is.  A request without
+    // one keeps the bound above -- it must still end.
+    if (request.has_context_shift && request.context_shift && !engine_.SupportsContextShift()) { result.ret_code = "error.unsupported"; return false; }
+    const bool shifts = request.has_context_shift ? request.context_shift : engine_.ShiftsContext();
+    const int max_len = request.max_output_len > 0 ? (shifts ? request.max_output_len : std::min(request.max_output_len, room)) : room;
     QueryOptions qo;
     qo.strategy_id = (int)engine_.GetSamplingStrategyId(request.decoding_alg);
     qo.random_seed = request.random_seed;
@@ -248,6 +259,8 @@ bool InferFlowServiceCore::ProcessQuery(InferFlowResponseChunk &result, const In
     if (request.logprobs >= 0 && !engine_.SupportsLogprobs()) { result.ret_code = "error.logprobs_unsupported"; return false; }
     qo.repetition_penalty = request.repetition_penalty; qo.presence_penalty = request.presence_penalty; qo.frequency_penalty = request.frequency_penalty;
     qo.logit_bias = request.logit_bias;
+    if (request.has_context_shift) qo.context_shift = request.context_shift ? 1 : 0;
+    if (request.has_context_keep) qo.context_keep = request.context_keep;
     if (qo.Processed() && !engine_.SupportsLogitProcessors()) { result.ret_code = "error.unsupported"; return false; }
     int qid = 0;
     {

@@ -44,6 +44,9 @@ struct InferFlowRequest {                 // InferFlowRequest (inferflow_service
     float repetition_penalty = 1.0f, presence_penalty = 0.0f, frequency_penalty = 0.0f;
     std::vector<std::pair<int, float>> logit_bias;
     bool has_repetition_penalty = false, has_presence_penalty = false, has_frequency_penalty = false, has_logit_bias = false;
+    // context shift (QueryOptions): "context_shift": bool, "context_keep": int >= 0; has_*: the field was in the body
+    bool context_shift = false, has_context_shift = false, has_context_keep = false;
+    int context_keep = -1;
     // ", \"repetition_penalty\": 1.3000, ..." for the fields that were given (the parser's echo)
     std::string ProcessorsJson() const;
 };

@@ -92,6 +92,18 @@ class DecodeWorker:
         """Cache rows [0, n_rows) of every layer's K and V from slot src to slot dst: one launch on the worker's stream, enqueue-only."""
         check(lib().ifa_model_kv_copy(self._h, int(src), int(dst), int(n_rows)))
 
+    def kv_shift(self, slot, keep, discard, n_rows):
+        """Context shift on query slot `slot`: rows [keep, keep + discard) of its n_rows cache rows are dropped, the rows behind them
+        move down and the moved K rows are rotated back by `discard` positions (ifa_model_kv_shift); enqueue-only."""
+        check(lib().ifa_model_kv_shift(self._h, int(slot), int(keep), int(discard), int(n_rows)))
+
+    def kv_shift_rows(self, kcache_ptr, vcache_ptr, table_ptr, keep, discard, n_rows):
+        """ifa_kv_shift_rows with this worker's cache geometry and stream on one layer's pair of device buffers (addresses; None skips
+        a side): table_ptr = head_dim / 2 fp32 (c, s) pairs on the device.  Enqueue-only."""
+        c = self.cfg
+        kv_shift_rows(c.kv_dtype, kcache_ptr, vcache_ptr, c.kv_heads, c.head_dim, c.rope_order, int(c.head_dim * c.partial_rotary + 0.5), table_ptr,
+                      keep, discard, n_rows, lib().ifa_model_stream(self._h))
+
     def sync(self):
         """Wait for everything enqueued on the worker's stream (kv_copy only enqueues; forward / decode synchronise themselves)."""
         check(lib().ifa_stream_sync(C.c_void_p(lib().ifa_model_stream(self._h))))
@@ -535,3 +547,10 @@ def tp_decode(worker, first_token, start_pos, n_steps, tp=None, world=None, stag
     check(lib().ifa_model_tp_decode(worker._h, C.byref(topo), int(first_token), int(start_pos), int(n_steps),
                                     out.ctypes.data_as(C.c_void_p), C.byref(ms)))
     return out, ms.value
+
+
+def kv_shift_rows(kv_dtype, kcache_ptr, vcache_ptr, kv_heads, head_dim, rope_order, rope_cols, table_ptr, keep, discard, n_rows, stream=None):
+    """ifa_kv_shift_rows: the context shift on one layer's pair of device buffers (addresses; None skips a side) with the caller's
+    table of head_dim / 2 fp32 (c, s) pairs on the device.  Enqueue-only on `stream` (None: the null stream)."""
+    check(lib().ifa_kv_shift_rows(int(kv_dtype), C.c_void_p(kcache_ptr), C.c_void_p(vcache_ptr), int(kv_heads), int(head_dim), int(rope_order),
+                                  int(rope_cols), C.c_void_p(table_ptr), int(keep), int(discard), int(n_rows), C.c_void_p(stream)))
