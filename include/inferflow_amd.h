@@ -235,6 +235,42 @@ size_t ifa_logsumexp_workspace(size_t rows, size_t n);
 int ifa_logsumexp_rows(const void *logits_f16, size_t row_stride, const int *row_idx_dev, size_t rows, size_t n,
                        const int *targets_dev, float *lse_out_dev, float *target_logit_out_dev, void *workspace_dev, ifa_stream stream);
 
+/* ---- the draw of the sampled strategies on a candidate pool (csrc/ifa_sample_rule.h, csrc/ifa_sample_pool.hip): everything
+ * ChooseTokensFromPool does behind ifa_topk_pool for strategy_id 1 sample.std, 2 greedy, 3 top_k, 4 sample.top_p, 7 min_p.  Per row:
+ * count (0..k) entries ids[] / F16 vals[] in the pool's order (value descending, lower id among equals), the parameters below and
+ * the 48-bit state of the query's generator (java.util.Random's LCG; a generator seeded with s starts at (s ^ 0x5DEECE66D) & (2^48 - 1)).
+ *   greedy: ids[0]; the generator is not touched.
+ *   sort:   libstdc++'s std::sort under a.w > b.w restated (introsort, median of 3, runs of 16, heapsort below depth 2 floor(log2 n),
+ *           final insertion sort): NOT stable, its order of equal F16 values decides ids.
+ *   softmax: t = max(temperature, 0.001); e = (float)exp((double)((w - max) / t)); sequential float sum, floor 1e-5; p = e / sum.
+ *   cut:    1 / 4: running float sum until >= top_p or min(count, max_k) entries; 3: the same with top_p = 1; 7: entries while
+ *           p >= min_p * p[0] (the first always).
+ *   draw:   interval starts in double (a NaN probability counts 0), r = NextDouble() * total, the reference's interval search.
+ * The device's exp is ocml's double exp (1 ulp), the host's is libm's; rounded to float the two differ only where the double lies
+ * within an ulp of a float rounding boundary.  Everything else is integer or correctly rounded IEEE arithmetic. */
+typedef struct {
+    int strategy_id;
+    float temperature, top_p;
+    int max_k;
+    float min_p;
+    int pool_size;      /* ifa_model_decode_sampled only: the pool length k of the step (1 for greedy); the two calls below ignore it */
+} ifa_sample_params;
+/* One wave per row, enqueue-only, capturable.  counts_dev [rows], ids_dev / vals_f16_dev [rows][k_stride] as ifa_topk_pool writes
+ * them with k = k_stride (1..IFA_POOL_MAX); params_dev [rows]; rng_state_dev [rows] advances in place (by two steps per drawn
+ * row); tokens_out_dev / index_out_dev [rows]: the drawn id and its index in the sorted pool; weights_out_dev (nullable)
+ * [rows][k_stride]: the probabilities of the sorted pool (count per row; untouched for a greedy row).  A row that cannot be drawn --
+ * count 0, an unknown strategy, a NaN value -- writes token / index -1, leaves its generator alone and stores row + 1 into
+ * *err_dev if that word is 0 (clear it before the launch); the other rows are not affected. */
+int ifa_sample_pool_rows(const int *counts_dev, const int *ids_dev, const void *vals_f16_dev, size_t rows, int k_stride,
+                         const ifa_sample_params *params_dev, unsigned long long *rng_state_dev, int *tokens_out_dev, int *index_out_dev,
+                         float *weights_out_dev, int *err_dev, ifa_stream stream);
+/* host-only (no device needed): the same code compiled for the CPU, one row.  index_out / cut_len_out / weights_out [count] /
+ * order_ids_out [count] (the ids in sorted order) are nullable.  IFA_ERR_STATE: count == 0 (no token); IFA_ERR_ARG: count outside
+ * 0..IFA_POOL_MAX, an unknown strategy, a NaN value. */
+int ifa_sample_pool_host(const int *ids, const unsigned short *vals_f16, int count, const ifa_sample_params *p,
+                         unsigned long long *rng_state_inout, int *token_out, int *index_out, int *cut_len_out, float *weights_out,
+                         int *order_ids_out);
+
 /* ---- logit processors (csrc/ifa_logit_adjust.hip): repetition / frequency / presence penalties and logit_bias on F16 logits rows.
  * State per slot (one slot per query), dense over the n ids of the vocabulary, all in device memory owned by the caller:
  *   state_dev [slots][n] u32: bit 31 = the id occurs in the prompt, bits 0..30 = how many times it has been generated;
@@ -386,6 +422,21 @@ int ifa_model_forward(ifa_model *m, const int *tokens_host, int n_tokens, int pr
  * n_steps replays on the worker's stream. */
 int ifa_model_decode(ifa_model *m, int first_token, int start_pos, int n_steps,
                      int *out_tokens_host, float *elapsed_ms);
+/* ifa_model_decode with the token of every step DRAWN on the device (csrc/ifa_engine_sampled.hip): same arguments and semantics,
+ * same fused kernels, one graph replay per token, one synchronisation per call.  The captured step gathers its own input and
+ * ends in lm_head -> [ifa_logit_adjust_rows with the state of state_slot] -> ifa_topk_pool with k = p->pool_size and the mask of
+ * ifa_model_set_pool_excluded -> the rule of ifa_sample_pool_rows + the advance of the device state -> [ifa_logit_state_add of the
+ * drawn token to state_slot].  state_slot = -1: no logit processors; else a slot ifa_model_logit_state_reset has prepared: every
+ * drawn token is counted there exactly once, before the next step reads the slot (first_token is NOT counted by this call).
+ * *rng_state_inout: the generator state the first draw starts from; on success the state behind the last draw (n_steps draws of
+ * two steps each; untouched for greedy).  Parameters, generator state, slot and error word travel through device memory written
+ * by the call, so one captured step serves every query with the same (KV slot, pool_size, processors or not); the greedy step's
+ * graphs are separate and stay valid.  Tokens equal, step for step, ifa_model_decode_pool + ifa_sample_pool_host on the same
+ * logits.  IFA_ERR_STATE: a step whose pool was empty (message names the step; the call's results are not valid), options
+ * exact_order / perf_stat / fused = 0, a model the fused step does not cover, a partitioned worker, embeddings / lm_head missing;
+ * IFA_ERR_ARG: an unknown strategy, pool_size outside 1..IFA_POOL_MAX, a slot without logit state, ifa_model_decode's own checks. */
+int ifa_model_decode_sampled(ifa_model *m, int first_token, int start_pos, int n_steps, const ifa_sample_params *p,
+                             unsigned long long *rng_state_inout, int state_slot, int *out_tokens_host, float *elapsed_ms);
 /* Everything a decode call of n_steps from start_pos sets up before its first launch (the attention variant of the contexts it
  * reaches, the hand-off arenas, the captured step and its multi-step replay) WITHOUT running a step: a caller that times its
  * first call keeps graph capture / instantiation out of it.  The KV cache and the activations are not touched. */
@@ -463,7 +514,8 @@ int ifa_model_pool_adjust(ifa_model *m, int n_sel, const int *state_slots_host);
  * workers (tp_size > 1, or a topology) return IFA_ERR_STATE. */
 int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, const int *targets_host,
                             float *lse_host, float *target_logit_host, int *next_token_host);
-/* debugging taps: "logits", "logits_adj" (the rows the last armed pool step adjusted; null before the first), "hidden", "kcache", "vcache" (device pointers) */
+/* debugging taps: "logits", "logits_adj" (the rows the last armed pool step adjusted; null before the first), "logit_state" (the
+ * logit processors' u32 state rows [slots][vocab]; null before the first reset), "hidden", "kcache", "vcache" (device pointers) */
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes);
 void *ifa_model_stream(ifa_model *m);
 /* Test hooks over the worker's memory (every device / pinned block a model owns goes through two counted allocators,

@@ -104,7 +104,17 @@ int ifa_engine_last_logits(ifa_engine *e, int query_id, uint16_t *dst_f16, size_
  * GpuInferenceWorker::UpdatePerfStat (inference_worker.cc:2670-2697; measured on the op-by-op step, see ifa_model_perf_stat). */
 int ifa_engine_perf_stat(ifa_engine *e, unsigned *keys, float *ms, int capacity);
 
-/* extension: n greedy steps with device-side token feedback (graph replay); returns tokens written or -1 */
+/* extension: n steps with device-side token feedback (graph replay); returns tokens written or -1.  Greedy, unprocessed queries
+ * always.  With `device_sampler = true` in the .ini (default false; active on a single-device engine with return_output_tensors =
+ * false, elsewhere accepted and inert: model_info "device_sampler" = 0) also sampled queries of sample.std / top_k / sample.top_p /
+ * min_p and processed queries (penalties / logit_bias), sampled or greedy: every replayed step ends in the candidate pool and the draw
+ * on the device (ifa_model_decode_sampled; the rule is pinned in csrc/ifa_sample_rule.h and DESIGN.md "Device sampler"), the query's
+ * generator state goes to the device and comes back, and the tokens are exactly those of the ifa_engine_infer / ifa_engine_commit loop
+ * for the same seeded query; a later infer / commit or generate continues the same generator stream.  model_info
+ * "device_sampled_steps" counts the steps drawn on the device.  tfs, typical, mirostat, fsd and random_fsd queries, a vocabulary with
+ * more than 3 excluded ids and ifa_engine_generate_lookup stay refused; logprobs are not produced by this call.  The device's exp is
+ * ocml's (1 ulp), the host's is libm's: see the known gap in DESIGN.md.  The service shell streams through infer / commit and does not
+ * use this call. */
 int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_tokens, float *gpu_ms);
 /* extension: lookup decoding (prompt-lookup decoding / "predicted outputs").  Up to max_new greedy tokens like ifa_engine_generate,
  * but a step carries the query's last token plus up to `lookup_draft_len` (.ini, default 4, 1..7) draft tokens as rows of ONE

@@ -94,6 +94,8 @@ SIGNATURES = {
     "ifa_argmax": (_i, [_vp, _sz, _vp, _vp]),
     "ifa_argmax_masked": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "ifa_topk_pool": (_i, [_vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_sample_pool_rows": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_sample_pool_host": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ifa_logsumexp_workspace": (_sz, [_sz, _sz]),
     "ifa_logsumexp_rows": (_i, [_vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ifa_logit_adjust_rows": (_i, [_vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
@@ -113,6 +115,7 @@ SIGNATURES = {
     "ifa_model_fused_supported": (_i, [_vp, C.c_char_p, _sz]),
     "ifa_model_forward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "ifa_model_decode": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "ifa_model_decode_sampled": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "ifa_model_decode_prepare": (_i, [_vp, _i, _i]),
     "ifa_add_by_row_index": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "ifa_model_kv_slots": (_i, [_vp, _i]),
@@ -233,6 +236,11 @@ class QueryOptionsShift(C.Structure):
     """ifa_query_options as it has grown: the fields of QueryOptions, then context_shift / context_keep (-1: the engine's keys).
     QueryOptions stays the shorter, earlier struct -- struct_size tells the library which one it was handed."""
     _fields_ = QueryOptions._fields_ + [("context_shift", C.c_int), ("context_keep", C.c_int)]
+
+
+class SampleParams(C.Structure):
+    """ifa_sample_params (include/inferflow_amd.h)"""
+    _fields_ = [("strategy_id", C.c_int), ("temperature", C.c_float), ("top_p", C.c_float), ("max_k", C.c_int), ("min_p", C.c_float), ("pool_size", C.c_int)]
 
 
 class ModelConfig(C.Structure):

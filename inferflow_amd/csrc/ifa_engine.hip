@@ -123,6 +123,7 @@ void drop_graphs(ifa_model *m)
     m->batch_graphs.clear();
     for (auto &kv : m->draft_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
     m->draft_graphs.clear();
+    sampled_drop_graphs(m);
 }
 
 // ------------------------------------------------ op-by-op forward (any T)
@@ -602,6 +603,7 @@ int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr,
     size_t b = 0; void *p = nullptr;
     if (!strcmp(name, "logits")) { p = m->logits; b = (size_t)c.vocab * 2; }
     else if (!strcmp(name, "logits_adj")) { p = m->la_adj; b = m->la_adj ? m->la_adj.cap() / m->g[T_LM_HEAD].rows * (size_t)c.vocab * 2 : 0; }
+    else if (!strcmp(name, "logit_state")) { p = m->la_state; b = m->la_slots * m->g[T_LM_HEAD].rows * sizeof(unsigned); }      // [slots][vocab] u32 (null before the first reset)
     else if (!strcmp(name, "tp_logits")) { p = m->tp_logits; b = m->tp_logits ? m->g[T_LM_HEAD].rows * 2 : 0; }
     else if (!strcmp(name, "trace")) { p = m->trace; b = m->trace ? sizeof(long long) * 2048 * 8 : 0; }
     else if (!strcmp(name, "hidden")) { p = m->xn; b = (size_t)c.dim * 2; }

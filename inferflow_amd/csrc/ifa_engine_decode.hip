@@ -667,13 +667,14 @@ int launch_lm(ifa_model *m, const half_t *x, half_t *logits_out)
     return launch_lmhead(lm_params(m, x, logits_out), m->g[T_OUT_NORM].present() ? 1 : 0, m->opt_rpw_lm, m->stream);
 }
 
-int enqueue_fused_step(ifa_model *m)
+int enqueue_fused_step(ifa_model *m, int tail)
 {
     const ifa_model_config &c = m->cfg;
     hipStream_t s = m->stream;
     int rc;
-    // st_on: the previous step's last launch (or ifa_model_decode, for a call's first step) has gathered this step's input
-    if (!m->st_on && (rc = launch_gather(m))) return rc;
+    // st_on: the previous step's last launch (or ifa_model_decode, for a call's first step) has gathered this step's input; a
+    // sampled step always gathers its own (its token is drawn by the step's last launch but one)
+    if ((!m->st_on || tail == STEP_TAIL_SAMPLED) && (rc = launch_gather(m))) return rc;
     half_t *x = m->x, *xnext = m->x2;
     const int l_first = std::min(std::max(m->opt_debug_layer0, 0), c.layers - 1);
     const int n_layers = (m->opt_debug_layers > 0 && l_first + m->opt_debug_layers < c.layers) ? l_first + m->opt_debug_layers : c.layers;
@@ -709,6 +710,7 @@ int enqueue_fused_step(ifa_model *m)
         }
         std::swap(x, xnext);
     }
+    if (tail == STEP_TAIL_SAMPLED) return sampled_tail_enqueue(m, x);
     if (m->st_on) return launch_lm_tail(m, x);
     if ((rc = launch_lm(m, x))) return rc;
     k_dec_argmax_advance<<<dim3(1), dim3(1024), 0, s>>>(m->logits, (int)m->g[T_LM_HEAD].rows, m->state, ifa_model::RING);
@@ -738,7 +740,24 @@ int ifa_model_decode_prepare(ifa_model *m, int start_pos, int n_steps)
 
 namespace ifae {
 
-int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms, bool prepare_only)
+// a head's workgroup gave up waiting for its q | k | v rows (the error word the call copied back): the step's results are not valid
+static int qa_err_check(ifa_model *m, int qerr)
+{
+    if (qerr == 0) return IFA_OK;
+    (void)hipMemsetAsync(m->qa_err, 0, 16, m->stream);
+    (void)hipStreamSynchronize(m->stream);
+    // the waiting launches go off for this model (and, process-wide, for every model created later): the next call captures the
+    // five-launch step, whose kernels wait for nothing
+    m->opt_fuse_attn = 0; m->opt_fuse_ffn = 0;
+    drop_graphs(m);
+    waits_disable("the fused QKV + attention launch timed out waiting for sibling workgroups");
+    return ifa_fail(IFA_ERR_STATE, "fused decode launch: a wait for another workgroup's rows timed out (code 0x%x: 0x5_ q | k | v / attention output, 0x6_ Wo output, 0x9_ chained FFN launch); "
+                    "the results of this call are not valid -- repeat it: options fuse_attn / fuse_ffn are off now (five-launch step)", (unsigned)qerr);
+}
+
+// sc: the call draws its tokens on the device (ifa_model_decode_sampled, which has checked that the fused graph route is open)
+int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms, bool prepare_only,
+                const SampledCall *sc)
 {
     IFA_REQUIRE(m && m->finalized, "ifa_model_decode: model not finalized");
     IFA_REQUIRE(n_steps > 0 && n_steps <= ifa_model::RING, "ifa_model_decode: n_steps %d (max %d per call)", n_steps, ifa_model::RING);
@@ -795,7 +814,13 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
         m->host_pinned[6] = (int)m->qa_calls;
         IFA_HIP_CHECK(hipMemcpyAsync(m->qa_call, m->host_pinned + 6, sizeof(int), hipMemcpyHostToDevice, s));
     }
-    if (m->opt_graph && !m->graph_exec) {
+    hipGraphExec_t samp_exec = nullptr;
+    if (sc) {
+        if ((rc = sampled_prepare(m, *sc))) return rc;
+        if (m->opt_graph && (rc = sampled_graph(m, &samp_exec))) return rc;
+        if ((rc = sampled_begin(m, *sc))) return rc;
+    }
+    if (!sc && m->opt_graph && !m->graph_exec) {
         IFA_HIP_CHECK(hipStreamSynchronize(s));
         IFA_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         rc = enqueue_fused_step(m);
@@ -808,7 +833,7 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
         IFA_HIP_CHECK(hipGraphInstantiate(&m->graph_exec, m->graph, nullptr, nullptr, 0));
     }
     const int S = m->opt_graph_steps;
-    if (m->opt_graph && S > 1 && n_steps >= S && (!m->graph_exec_n || m->graph_n_steps != S)) {
+    if (!sc && m->opt_graph && S > 1 && n_steps >= S && (!m->graph_exec_n || m->graph_n_steps != S)) {
         if (m->graph_exec_n) { (void)hipGraphExecDestroy(m->graph_exec_n); m->graph_exec_n = nullptr; }
         if (m->graph_n) { (void)hipGraphDestroy(m->graph_n); m->graph_n = nullptr; }
         IFA_HIP_CHECK(hipStreamSynchronize(s));
@@ -826,8 +851,14 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (elapsed_ms) { IFA_HIP_CHECK(hipEventCreate(&e0)); IFA_HIP_CHECK(hipEventCreate(&e1)); IFA_HIP_CHECK(hipEventRecord(e0, s)); }
     th("events created, first recorded");
-    if (m->st_on && (rc = launch_gather(m))) return rc;      // the call's first step: its input is gathered here, every later one by the step before it
+    if (!sc && m->st_on && (rc = launch_gather(m))) return rc;      // the call's first step: its input is gathered here, every later one by the step before it
     for (int i = 0; i < n_steps;) {
+        if (sc) {
+            if (samp_exec) IFA_HIP_CHECK(hipGraphLaunch(samp_exec, s));
+            else if ((rc = enqueue_fused_step(m, STEP_TAIL_SAMPLED))) return rc;
+            i++;
+            continue;
+        }
         if (m->opt_graph && m->graph_exec_n && m->graph_n_steps == S && S > 1 && n_steps - i >= S) { IFA_HIP_CHECK(hipGraphLaunch(m->graph_exec_n, s)); i += S; continue; }
         if (m->opt_graph) IFA_HIP_CHECK(hipGraphLaunch(m->graph_exec, s));
         else if ((rc = enqueue_fused_step(m))) return rc;
@@ -835,7 +866,8 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     }
     th("steps enqueued");
     if (elapsed_ms) IFA_HIP_CHECK(hipEventRecord(e1, s));
-    if ((rc = pool_enqueue(m, m->logits, 1))) return rc;      // (armed by ifa_model_decode_pool only: the last step's row)
+    if (!sc && (rc = pool_enqueue(m, m->logits, 1))) return rc;      // (armed by ifa_model_decode_pool only: the last step's row)
+    if (sc && (rc = sampled_copy_back(m))) return rc;
     IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned + 8, m->state + 8, sizeof(int) * (size_t)n_steps, hipMemcpyDeviceToHost, s));
     int *qerr = m->host_pinned + 8 + ifa_model::RING;
     qerr[0] = 0;
@@ -843,17 +875,9 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     th("copies back enqueued");
     IFA_HIP_CHECK(hipStreamSynchronize(s));
     th("stream synchronised");
-    if (qerr[0] != 0) {      // a head's workgroup gave up waiting for its q | k | v rows: the step's results are not valid
-        (void)hipMemsetAsync(m->qa_err, 0, 16, s);
-        (void)hipStreamSynchronize(s);
+    if ((rc = qa_err_check(m, qerr[0])) || (sc && (rc = sampled_finish(m, *sc)))) {
         if (elapsed_ms) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
-        // the waiting launches go off for this model (and, process-wide, for every model created later): the next call captures the
-        // five-launch step, whose kernels wait for nothing
-        m->opt_fuse_attn = 0; m->opt_fuse_ffn = 0;
-        drop_graphs(m);
-        waits_disable("the fused QKV + attention launch timed out waiting for sibling workgroups");
-        return ifa_fail(IFA_ERR_STATE, "fused decode launch: a wait for another workgroup's rows timed out (code 0x%x: 0x5_ q | k | v / attention output, 0x6_ Wo output, 0x9_ chained FFN launch); "
-                        "the results of this call are not valid -- repeat it: options fuse_attn / fuse_ffn are off now (five-launch step)", (unsigned)qerr[0]);
+        return rc;
     }
     if (elapsed_ms) { IFA_HIP_CHECK(hipEventElapsedTime(elapsed_ms, e0, e1)); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
     if (out_tokens_host) memcpy(out_tokens_host, m->host_pinned + 8, sizeof(int) * (size_t)n_steps);

@@ -60,7 +60,7 @@ static int logit_partitioned(const ifa_model *m, const char *who)
 static size_t pool_idx_rows(const ifa_model *m) { return m->pool_idx.cap() / 2; }
 
 // staging for n_sel rows of k entries (grown on demand, outside any capture; one allocation serves every later step)
-static int pool_reserve(ifa_model *m, int n_sel, int k)
+int pool_reserve(ifa_model *m, int n_sel, int k)
 {
     const size_t bytes = pool_block_bytes(std::max(n_sel, 8), IFA_POOL_MAX >= k ? IFA_POOL_MAX : k, true);
     int rc;

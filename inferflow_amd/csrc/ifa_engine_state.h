@@ -252,6 +252,14 @@ struct ifa_model : Scratch {
     std::vector<void *> kvc_tab_host;          // what the device table holds
     std::vector<DevPin<void *>> kvc_retired;   // replaced tables
     DevBuf<float> kvs_rot;                     // context shift (ifa_model_kv_shift, ifa_kv_shift.hip): [head_dim / 2] (cos, sin) of the last call's rotation
+    // Sampled decode (ifa_model_decode_sampled, ifa_engine_sampled.hip).  samp_blk: the call's parameters, generator state, state
+    // slot and error word in device memory (+ pinned twin).  samp_k / samp_armed: pool length and "logit processors armed" of the
+    // current call, baked into the launches of the step it captures.  samp_graphs: the captured sampled step per
+    // (KV slot << 10 | k << 1 | armed) with the buffer addresses it names; the greedy step's graphs are not among them.
+    struct SampGraph { hipGraphExec_t exec = nullptr; const void *ptrs[8] = {}; };
+    std::map<int, SampGraph> samp_graphs;
+    DevPin<int> samp_blk;
+    int samp_k = 0; bool samp_armed = false;
     static constexpr int RING = 1024;
 };
 
@@ -378,8 +386,20 @@ int step_tail_ready(ifa_model *m);
 int launch_lm_tail(ifa_model *m, const half_t *x);
 int launch_gather(ifa_model *m);
 int launch_lm(ifa_model *m, const half_t *x, half_t *logits_out = nullptr);
-int enqueue_fused_step(ifa_model *m);
-int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms, bool prepare_only);
+// how a fused step ends: the greedy argmax (k_dec_lmhead_tail, or lm_head + k_dec_argmax_advance), or the draw (sampled_tail_enqueue)
+enum { STEP_TAIL_GREEDY = 0, STEP_TAIL_SAMPLED = 1 };
+struct SampledCall { const ifa_sample_params *p = nullptr; unsigned long long *rng = nullptr; int state_slot = -1; };
+int enqueue_fused_step(ifa_model *m, int tail = STEP_TAIL_GREEDY);
+int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms, bool prepare_only,
+                const SampledCall *sc = nullptr);
+// ---- ifa_engine_sampled.hip
+int sampled_prepare(ifa_model *m, const SampledCall &sc);
+int sampled_tail_enqueue(ifa_model *m, const half_t *x);
+int sampled_graph(ifa_model *m, hipGraphExec_t *exec_out);
+void sampled_drop_graphs(ifa_model *m);
+int sampled_begin(ifa_model *m, const SampledCall &sc);
+int sampled_copy_back(ifa_model *m);
+int sampled_finish(ifa_model *m, const SampledCall &sc);
 // ---- ifa_engine_forward.hip
 int gather_rows(ifa_model *m, const half_t *src, const int *idx_dev, int T, int dim, int n_src, half_t *dst, float scale);
 int matmul(ifa_model *m, const half_t *A, int T, const Tensor &W, const Tensor &bias, half_t *C);
@@ -400,6 +420,8 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
 // armed (m->pool.k > 0): ifa_topk_pool over the wanted rows of `logits` ([n_rows][vocab], this step's rows) + the copy of the result
 // block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.
 int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
+// device / pinned staging for n_sel rows of k entries (grown on demand, outside any capture)
+int pool_reserve(ifa_model *m, int n_sel, int k);
 // ---- ifa_engine_score.hip
 static constexpr size_t LSE_PART_FLOATS = 256;      // rows * splits <= 128 pairs whatever the row count (ifa_logprob.hip, lse_splits)
 int lse_part_reserve(ifa_model *m);

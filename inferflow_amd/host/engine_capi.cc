@@ -312,6 +312,8 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "partition_ranks") return e->engine.PartitionRanks();
     if (k == "device_sampling_pool") return e->engine.config().device_sampling_pool ? 1 : 0;
     if (k == "sampled_fused_steps") return (int)std::min<long long>(e->engine.sampled_fused_steps(), 0x7FFFFFFF);
+    if (k == "device_sampler") return e->engine.device_sampler_active() ? 1 : 0;
+    if (k == "device_sampled_steps") return (int)std::min<long long>(e->engine.device_sampled_steps(), 0x7FFFFFFF);
     if (k == "prefix_cache") return e->engine.prefix_cache_active() ? 1 : 0;
     if (k == "prefix_cache_hits") return (int)std::min<long long>(e->engine.prefix_cache_hits(), 0x7FFFFFFF);
     if (k == "prefix_cache_tokens") return (int)std::min<long long>(e->engine.prefix_cache_tokens(), 0x7FFFFFFF);

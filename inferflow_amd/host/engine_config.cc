@@ -119,6 +119,7 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "dynamic_batching_min_queries", config.dynamic_batching_min_queries);
     cfg.GetItem(section, "force_partition_path", config.force_partition_path);
     cfg.GetItem(section, "device_sampling_pool", config.device_sampling_pool);
+    cfg.GetItem(section, "device_sampler", config.device_sampler);
     cfg.GetItem(section, "prefix_cache", config.prefix_cache);
     cfg.GetItem(section, "prefix_cache_min_tokens", config.prefix_cache_min_tokens);
     if (config.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config.prefix_cache_min_tokens); return false; }

@@ -30,6 +30,7 @@ void InferenceEngine::Clear()
     use_clock_ = prefix_hits_ = prefix_tokens_ = prefix_copies_ = 0;
     processed_steps_ = 0;
     shift_active_ = false; context_shifts_ = context_shift_tokens_ = 0;
+    device_sampler_active_ = false; device_sampled_steps_ = 0;
 }
 
 bool InferenceEngine::Init(const InferenceConfig &cfg)
@@ -96,6 +97,7 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
         EngineSetError("context_shift_keep %d exceeds half of max_context_len %d", config_.context_shift_keep, MaxContextLen()); Clear(); return false;
     }
     shift_active_ = config_.context_shift && SupportsContextShift();
+    device_sampler_active_ = config_.device_sampler && !multi_ && !config_.return_output_tensors;
     if (prefix_active_) slot_records_.assign((size_t)kv_slots_, SlotRecord());
     return true;
 }
@@ -643,7 +645,18 @@ InferenceEngine::Query *InferenceEngine::FindQuery(int query_id)
 bool InferenceEngine::DeviceGreedyOk(const Query &q, int n_new, bool lookup)
 {
     if (q.ended) { EngineSetError("Query %d has ended", q.id); return false; }
-    if (q.options.Processed())
+    // device sampler: Generate (not GenerateLookup) draws on the device for the strategies its rule covers and runs the processors there
+    const bool drawn = !lookup && DeviceDrawn(q);
+    if (drawn && host_greedy_)
+        EngineSetError("Generate() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size());
+    else if (drawn && (PoolLen(q) < 1 || PoolLen(q) > IFA_POOL_MAX))
+        EngineSetError("Generate() draws from a device pool of at most %d candidates; query %d asks for %d (use Infer / CommitInferenceResult)", IFA_POOL_MAX, q.id, PoolLen(q));
+    else if (drawn) {
+        if (q.shift_on || (int)q.tokens.size() + n_new <= MaxContextLen()) return true;
+        EngineSetError("Generate: %zu tokens + %d steps exceed max_context_len %d", q.tokens.size(), n_new, MaxContextLen());
+    } else if (device_sampler_active_ && !lookup && q.strategy != SamplingStrategyId::Greedy)
+        EngineSetError("Generate() draws on the device for sample.std, top_k, sample.top_p and min_p; query %d uses strategy %d (tfs, typical, mirostat, fsd and random_fsd stay with Infer / CommitInferenceResult)", q.id, (int)q.strategy);
+    else if (q.options.Processed())
         EngineSetError(lookup ? "GenerateLookup() feeds the token back on the device without logit processors; query %d has penalties or a logit_bias (use Infer / CommitInferenceResult)"
                               : "Generate() feeds the token back on the device without logit processors; query %d has penalties or a logit_bias (use Infer / CommitInferenceResult)", q.id);
     else if (host_greedy_)
@@ -681,6 +694,61 @@ bool InferenceEngine::PrefillPending(Query &q, std::vector<int> &new_tokens, int
     return true;
 }
 
+bool InferenceEngine::DeviceDrawn(const Query &q) const
+{
+    if (!device_sampler_active_) return false;
+    const SamplingStrategyId s = q.strategy;
+    if (s == SamplingStrategyId::Greedy) return q.options.Processed();      // (an unprocessed greedy query keeps the greedy step)
+    return s == SamplingStrategyId::StdSampling || s == SamplingStrategyId::TopK || s == SamplingStrategyId::TopP || s == SamplingStrategyId::MinP;
+}
+
+bool InferenceEngine::CountQuery(Query &q)
+{
+    while (q.counted < (int)q.tokens.size()) {
+        const int n = std::min(1024, (int)q.tokens.size() - q.counted);
+        const std::vector<int> slots((size_t)n, q.kv_slot);
+        if (ifa_model_logit_state_add(model_, n, slots.data(), q.tokens.data() + q.counted) != IFA_OK) { EngineSetError("logit processors: %s", ifa_last_error()); return false; }
+        q.counted += n;
+    }
+    return true;
+}
+
+// PrefillPending for a query whose tokens are drawn on the device: the pending prompt's step ends in the candidate pool and the
+// host's sampler draws from it with the query's generator -- the step Infer takes, so the first token is Infer's
+bool InferenceEngine::PrefillPendingDrawn(Query &q, std::vector<int> &new_tokens, int &left)
+{
+    const int pending = (int)q.tokens.size() - q.processed;
+    if (pending <= 0) { EngineSetError("Query %d has no committed token to continue from", q.id); return false; }
+    if (pending == 1 && q.processed > 0) return true;
+    if (q.options.Processed() && !CountQuery(q)) return false;
+    if (pending > 1 && !EnsureLogitsRows((size_t)pending)) return false;
+    QueryInferenceResult item;
+    if (!PoolStep(q, pending, item)) return false;
+    if (item.next_tokens.empty()) { EngineSetError("Generate: the prompt step of query %d chose no token", q.id); return false; }
+    const int next = item.next_tokens[0].id;
+    q.processed = (int)q.tokens.size();
+    q.tokens.push_back(next); new_tokens.push_back(next); left--;
+    return true;
+}
+
+// k steps of the replayed graph with the draw on the device; the generator continues q.rng's stream and is handed back
+bool InferenceEngine::DecodeDrawn(Query &q, int k, int *out, float *gpu_ms)
+{
+    const bool processed = q.options.Processed();
+    if (processed && !CountQuery(q)) return false;      // every committed token is counted before the first step reads the slot
+    ifa_sample_params p;
+    p.strategy_id = (int)q.strategy; p.temperature = q.options.temperature; p.top_p = q.sampling.top_p; p.max_k = q.sampling.max_k;
+    p.min_p = q.sampling.min_p; p.pool_size = PoolLen(q);
+    unsigned long long state = q.rng.State();
+    if (ifa_model_decode_sampled(model_, q.tokens.back(), q.processed, k, &p, &state, processed ? q.kv_slot : -1, out, gpu_ms) != IFA_OK) {
+        EngineSetError("sampled decode failed: %s", ifa_last_error()); return false;
+    }
+    q.rng.SetState(state);
+    device_sampled_steps_ += k;
+    if (processed) { processed_steps_ += k; q.counted += k; }      // (the steps counted their own tokens; Generate appends them now)
+    return true;
+}
+
 bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_tokens, float *gpu_ms)
 {
     new_tokens.clear();
@@ -690,7 +758,8 @@ bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_
     if (!DeviceGreedyOk(q, n_steps, false)) return false;
     if (!multi_ && ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
     if (!ShiftIfFull(q)) return false;
-    if (!PrefillPending(q, new_tokens, n_steps, nullptr)) return false;
+    const bool drawn = DeviceDrawn(q);
+    if (drawn ? !PrefillPendingDrawn(q, new_tokens, n_steps) : !PrefillPending(q, new_tokens, n_steps, nullptr)) return false;
     float ms_total = 0;
     while (n_steps > 0) {                              // the device token ring holds 1024 steps per call
         // context shift: run to the limit, shift where Infer would (tokens == max_context_len, in front of the step), continue
@@ -699,7 +768,8 @@ bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_
         if (k < 1) { EngineSetError("Generate: query %d is at max_context_len %d with nothing to drop behind its %d kept rows", q.id, MaxContextLen(), q.shift_keep); return false; }
         std::vector<int> out((size_t)k);
         float ms = 0;
-        if (multi_) { if (!MultiDecode(q, k, out.data(), &ms)) return false; }
+        if (drawn) { if (!DecodeDrawn(q, k, out.data(), &ms)) return false; }
+        else if (multi_) { if (!MultiDecode(q, k, out.data(), &ms)) return false; }
         else if (ifa_model_decode(model_, q.tokens.back(), q.processed, k, out.data(), &ms) != IFA_OK) { EngineSetError("decode failed: %s", ifa_last_error()); return false; }
         ms_total += ms;
         for (int t : out) { q.tokens.push_back(t); new_tokens.push_back(t); }

@@ -111,6 +111,13 @@ struct InferenceConfig {
     // key is accepted and the cache stays off (model_info "prefix_cache" = 0).
     bool prefix_cache = false;
     int prefix_cache_min_tokens = 16;
+    // extension: device sampler.  Generate() also takes sampled queries (sample.std, top_k, sample.top_p, min_p) and processed
+    // queries (penalties / logit_bias; sampled or greedy): every step of the replayed graph ends in the candidate pool and the
+    // draw on the device (ifa_model_decode_sampled; the rule: csrc/ifa_sample_rule.h), the query's generator state travels to the
+    // device and back, and the tokens are the ones the Infer / CommitInferenceResult loop yields for the same seeded query.
+    // Applies to a single-device engine with return_output_tensors = false; elsewhere the key is accepted and inert (model_info
+    // "device_sampler" = 0).  Off by default: Generate then refuses such queries as before.
+    bool device_sampler = false;
     // extension: lookup decoding (InferenceEngine::GenerateLookup).  Up to lookup_draft_len (1..7) draft tokens per step, the
     // continuation of the longest n-gram of lookup_ngram_max .. lookup_ngram_min tokens that ends the query's context
     // (host/lookup_draft.h).  Applies to a single-device engine with return_output_tensors = false; elsewhere the keys are accepted
@@ -144,7 +151,7 @@ struct QueryOptions {               // SamplingStrategy::QueryOptions (sampling_
     // generated ids (x - (f * count + (count > 0 ? p : 0))); logit_bias: (id, value) pairs added last, -inf bans the id.  A query
     // with any of them non-neutral is PROCESSED: its steps end in the device pool whatever device_sampling_pool says, a greedy one
     // takes the pool's best entry, logprobs are those of the processed distribution at temperature 1.  Single-device engines with
-    // return_output_tensors = false only; Generate / GenerateLookup refuse a processed query.
+    // return_output_tensors = false only; GenerateLookup refuses a processed query, Generate takes one only with device_sampler on.
     float repetition_penalty = 1.0f, presence_penalty = 0.0f, frequency_penalty = 0.0f;
     std::vector<std::pair<int, float>> logit_bias;
     static const int MAX_LOGIT_BIAS = 1024;
@@ -254,8 +261,9 @@ public:
     bool ScoreTokens(const std::vector<int> &tokens, std::vector<float> &logprobs_out, std::vector<float> *lse_out = nullptr,
                      std::vector<float> *target_logit_out = nullptr);
 
-    // Extension: n greedy steps with the token fed back on the device (hipGraph replay, no host
-    // round trip per token).  Equivalent to n x {Infer, CommitInferenceResult(greedy)}.
+    // Extension: n steps with the token fed back on the device (hipGraph replay, no host round trip per token).  Equivalent to
+    // n x {Infer, CommitInferenceResult(the step's token)}: greedy queries always; with InferenceConfig::device_sampler also sampled
+    // (sample.std, top_k, sample.top_p, min_p) and processed queries, whose tokens are drawn on the device from the query's generator.
     bool Generate(int query_id, int n_steps, std::vector<int> &new_tokens, float *gpu_ms = nullptr);
 
     // Extension: lookup decoding (prompt-lookup / "predicted outputs").  Up to max_new_tokens greedy tokens like Generate, but a step
@@ -288,6 +296,10 @@ public:
     // single-token steps of sampled queries that took the worker's decode step + device pool instead of ifa_model_forward
     // (one per query per step; 0 unless device_sampling_pool is on)
     long long sampled_fused_steps() const { return sampled_fused_steps_; }
+    // device sampler (InferenceConfig::device_sampler): whether it is active on this engine; steps of Generate whose token was drawn
+    // on the device
+    bool device_sampler_active() const { return device_sampler_active_; }
+    long long device_sampled_steps() const { return device_sampled_steps_; }
     // prompt prefix cache (InferenceConfig::prefix_cache): whether it is active on this engine; queries that started behind reused
     // rows, the rows they reused in all, how many of them needed the device copy; the rows query_id reused at AddQuery (-1: unknown id)
     bool prefix_cache_active() const { return prefix_active_; }
@@ -348,6 +360,11 @@ private:
     Query *FindQuery(int query_id);
     bool DeviceGreedyOk(const Query &q, int n_new, bool lookup);
     bool PrefillPending(Query &q, std::vector<int> &new_tokens, int &left, LookupStats *st);
+    // device sampler: Generate draws this query's tokens on the device (a sampled strategy the device rule covers, or a processed query)
+    bool DeviceDrawn(const Query &q) const;
+    bool CountQuery(Query &q);                  // CountCommitted for one query
+    bool PrefillPendingDrawn(Query &q, std::vector<int> &new_tokens, int &left);       // the first token from the pool step, like Infer
+    bool DecodeDrawn(Query &q, int k, int *out, float *gpu_ms);
     // ---- multi-GPU partitions (devices = 0&1 | 0;1 | 0&1;2&3): one worker and one host thread per GPU, like the
     // reference's Infer_TensorParallelism / Infer_Std over GpuInferenceWorker threads (inference_engine.cc:1161-1296).
     // MultiGpu and everything that looks inside it: inference_engine_multi.cc
@@ -375,6 +392,8 @@ private:
     void *logits_dev_ = nullptr;
     size_t logits_rows_ = 0;
     long long sampled_fused_steps_ = 0, processed_steps_ = 0;
+    bool device_sampler_active_ = false;       // the device_sampler key on a single-device engine without output tensors
+    long long device_sampled_steps_ = 0;
     bool shift_active_ = false;     // the context_shift key on an engine that can shift
     long long context_shifts_ = 0, context_shift_tokens_ = 0;
     bool pool_lse_on_ = false;      // the worker's option pool_lse as last set

@@ -45,6 +45,9 @@ public:
     double NextDouble(double from, double to) { return from + NextDouble() * (to - from); }
     float NextFloat() { return Next(24) / ((float)(1 << 24)); }
     float NextFloat(float from, float to) { return from + NextFloat() * (to - from); }
+    // the 48-bit state, for a draw that continues this stream elsewhere (the device sampler) and hands it back
+    uint64_t State() const { return seed_; }
+    void SetState(uint64_t state) { seed_ = state & MASK; }
 
 private:
     static constexpr uint64_t MULTIPLIER = 0x5DEECE66DULL, ADDEND = 0xBULL, MASK = (1ULL << 48) - 1;

@@ -136,6 +136,17 @@ class DecodeWorker:
                                      out.ctypes.data_as(C.c_void_p), C.byref(ms) if timed else None))
         return out, ms.value
 
+    def decode_sampled(self, first_token, start_pos, n_steps, params, rng_state, state_slot=-1, timed=True):
+        """decode() with every token drawn on the device (ifa_model_decode_sampled).  params: _capi.SampleParams (pool_size = the
+        step's pool length); rng_state: the 48-bit generator state the first draw starts from (rng_state_of_seed); state_slot: the
+        logit-processor slot, -1 for none.  Returns (tokens, generator state behind the last draw, gpu_ms)."""
+        out = np.zeros(n_steps, np.int32)
+        ms = C.c_float(-1.0)
+        st = C.c_ulonglong(int(rng_state))
+        check(lib().ifa_model_decode_sampled(self._h, int(first_token), int(start_pos), int(n_steps), C.byref(params), C.byref(st), int(state_slot),
+                                             out.ctypes.data_as(C.c_void_p), C.byref(ms) if timed else None))
+        return out, st.value, ms.value
+
     def set_pool_excluded(self, ids):
         """ids (any count) the device candidate pool never offers; an empty list clears the mask"""
         a = np.ascontiguousarray(ids, np.int32).reshape(-1)
@@ -362,6 +373,53 @@ def topk_pool(logits, k, excluded_bits=None, stream=None):
                               C.c_void_p(excluded_bits.data_ptr()) if excluded_bits is not None else None,
                               C.c_void_p(ids.data_ptr()), C.c_void_p(vals.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
     return ids, vals, cnt
+
+
+def rng_state_of_seed(seed):
+    """the 48-bit state of the java.util.Random generator right after seeding it with `seed`"""
+    return (int(seed) ^ 0x5DEECE66D) & ((1 << 48) - 1)
+
+
+def sample_params_array(rows):
+    """numpy structured array [len(rows)] laid out like ifa_sample_params from (strategy_id, temperature, top_p, max_k, min_p) tuples"""
+    rec = np.dtype([("strategy_id", np.int32), ("temperature", np.float32), ("top_p", np.float32), ("max_k", np.int32), ("min_p", np.float32),
+                   ("pool_size", np.int32)])
+    a = np.zeros(len(rows), rec)
+    for i, r in enumerate(rows):
+        a[i] = tuple(r) + (0,)
+    return a
+
+
+def sample_pool_host(ids, vals_f16_bits, params, rng_state):
+    """ifa_sample_pool_host on one pool (no device): ids int32 [count], vals uint16 F16 bits [count], params a row of
+    sample_params_array (or _capi.SampleParams).  Returns (token, index, cut length, weights float32 [count], sorted ids int32 [count],
+    generator state afterwards); raises IfaError for an empty pool."""
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    vals = np.ascontiguousarray(vals_f16_bits).view(np.uint16).reshape(-1)
+    assert ids.size == vals.size
+    if isinstance(params, np.void):
+        params = np.array([params], params.dtype)
+    pp = C.c_void_p(params.ctypes.data) if isinstance(params, np.ndarray) else C.cast(C.pointer(params), C.c_void_p)
+    st = C.c_ulonglong(int(rng_state))
+    tok, idx, cut = C.c_int(-1), C.c_int(-1), C.c_int(0)
+    w, order = np.zeros(max(ids.size, 1), np.float32), np.full(max(ids.size, 1), -1, np.int32)
+    check(lib().ifa_sample_pool_host(ids.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), ids.size, pp, C.cast(C.pointer(st), C.c_void_p),
+                                     C.cast(C.pointer(tok), C.c_void_p), C.cast(C.pointer(idx), C.c_void_p), C.cast(C.pointer(cut), C.c_void_p),
+                                     w.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p)))
+    return tok.value, idx.value, cut.value, w[:ids.size], order[:ids.size], st.value
+
+
+def sample_pool_rows(counts, ids, vals, params, rng_states, err, weights=None, stream=None):
+    """ifa_sample_pool_rows on torch cuda tensors: counts int32 [rows], ids int32 / vals int16 F16 bits [rows][k], params uint8 bytes of
+    a sample_params_array [rows], rng_states int64 [rows] (advance in place), err int32 [1]; weights float32 [rows][k] or None.
+    Returns (tokens int32 [rows], index int32 [rows]); enqueue-only."""
+    import torch
+    rows, k = ids.shape
+    tokens = torch.empty(rows, dtype=torch.int32, device=ids.device)
+    index = torch.empty(rows, dtype=torch.int32, device=ids.device)
+    check(lib().ifa_sample_pool_rows(_ptr(counts), _ptr(ids), _ptr(vals), rows, int(k), _ptr(params), _ptr(rng_states), _ptr(tokens), _ptr(index),
+                                     _ptr(weights), _ptr(err), C.c_void_p(stream)))
+    return tokens, index
 
 
 def logsumexp_rows(logits, n=None, row_idx=None, targets=None, split=True, stream=None):
