@@ -645,6 +645,17 @@ int ifa_model_get_expert_tensor(ifa_model *m, int layer, int expert, int tensor_
  * which = 0 qkv, 1 attention, 2 wo, 3 ffn w1/w3, 4 w2, 5 lm_head.  For bench.py's roofline. */
 int ifa_model_time_kernel(ifa_model *m, int which, int iters, float *avg_us);
 
+/* The decode route plan (csrc/ifa_decode_route.h, DESIGN.md "Decode route plan"): which attention launch a decode step runs, with
+ * which kernel instance.  Host-only, no GPU needed.  facts[22], in the order of DecRouteFacts: head_dim, heads, kv_heads, max_ctx,
+ * kv_q8, reach, attn_split_ctx, attn_nsplits, attn_kt, attn_unload, fuse_attn, fuse_ffn, attn_q8, tail_layers_ok, gk, rw,
+ * chain_level, have_attq, waits, num_cus, visible_cus, own_launches.  out[14], in the order of DecRoute: kind (0 one workgroup per
+ * head, 1 keys split over workgroups, 2 tail of the fused QKV launch), nsplits, pb, kt, ul, gk, rw, chain, split_threshold, split,
+ * lds_attn, lds_scores, lds_pv, error. */
+int ifa_decode_route_plan(const int *facts, int n_facts, int *out, int n_out);
+/* The plan of the model's last decode / decode_prepare / time_kernel call: out[17] = the 14 values above, then num_cus,
+ * visible_cus and waits (1: launches whose workgroups wait for each other are allowed) as the engine sees them now. */
+int ifa_model_decode_route(ifa_model *m, int *out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

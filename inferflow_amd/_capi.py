@@ -137,6 +137,8 @@ SIGNATURES = {
     "ifa_model_get_buffer": (_i, [_vp, C.c_char_p, _i, C.POINTER(_vp), C.POINTER(_sz)]),
     "ifa_model_stream": (_vp, [_vp]),
     "ifa_model_time_kernel": (_i, [_vp, _i, _i, _vp]),
+    "ifa_decode_route_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_model_decode_route": (_i, [_vp, _vp, _i]),
     "ifa_model_set_stream": (_i, [_vp, _vp]),
     "ifa_model_tp_begin": (_i, [_vp, _i, _i]),
     "ifa_model_tp_begin_hidden": (_i, [_vp, _vp, _i]),

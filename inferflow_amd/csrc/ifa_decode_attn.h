@@ -2,6 +2,7 @@
 // variants), split from ifa_decode_kernels.h so that the per-format GEMV translation units do not depend on them.
 #pragma once
 #include "ifa_decode_kernels.h"
+#include "ifa_decode_route.h"      // dec_attn_smem / dec_attn_pv_smem / dec_attn_scores_smem, DEC_ATTN_MAX_SPLITS, DEC_PV_STAGE
 
 namespace ifa {
 
@@ -654,7 +655,6 @@ __global__ void __launch_bounds__(256) k_dec_attn(const half_t *pq, const uint8_
 //   k_dec_attn_pv      (head, split): global max, the full-row sum of exp (recomputed per split: a few thousand
 //                                      expf), P_j = half(half(e_j) * 1/sum) for its keys, partial P.V in fp32
 //   k_dec_attn_combine (head)       : sum of the partial outputs in split order -> half
-constexpr int DEC_ATTN_MAX_SPLITS = 32;      // splits per head are chosen per decode call from the context it will reach (8 / 16 / 32)
 
 struct DecAttnSplitWs {
     half_t *S;        // [heads][max_ctx]
@@ -861,7 +861,6 @@ __global__ void __launch_bounds__(256) k_dec_attn_scores(const DecAttnParams P, 
 // thread in flight (five trips per 320-key split), the Q8 loop one key -- 21 us per layer at 4096 keys for 33 MB of V (1.6 TB/s).  Now the
 // score row is staged through LDS in 16-byte pieces, 4096 keys at a time (thread t still adds keys t, t + 256, ... in ascending order),
 // and the V rows of the next eight keys of a thread are requested before the current eight are multiplied.
-constexpr int DEC_PV_STAGE = 4096;      // keys of the score row staged per pass (multiple of 256)
 
 template <int HD, bool Q8>
 __global__ void __launch_bounds__(256) k_dec_attn_pv(const DecAttnParams P, const DecAttnSplitWs ws)
@@ -995,21 +994,5 @@ __global__ void __launch_bounds__(HD) k_dec_attn_combine(const DecAttnSplitWs ws
     out[(size_t)h * HD + d] = yh;
     if constexpr (HD % 32 == 0) { if (xq) dec_attn_emit_q8<HD>(xq, heads * HD, h, d, yh); }
 }
-
-__host__ __device__ inline size_t dec_attn_scores_smem(int head_dim, bool q8) { return q8 ? 16 : (size_t)256 * (head_dim * 2 + 16); }
-
-__host__ __device__ inline size_t dec_attn_pv_smem(int head_dim, int max_ctx, int nsplits = 8)
-{
-    const size_t nsplit = 256 / (head_dim / 8);
-    const size_t chunk = (((size_t)max_ctx + nsplits - 1) / nsplits + 63) / 64 * 64;
-    return 8 * 4 + nsplit * head_dim * 4 + (size_t)(DEC_PV_STAGE + 8) * 2 + chunk * 2 + 16;      // + the staged piece of the score row
-}
-
-__host__ __device__ inline size_t dec_attn_smem(int head_dim, int max_ctx, int ktile_rows = 0)
-{
-    const size_t nsplit = 256 / (head_dim / 8);
-    return (size_t)head_dim * 3 * 2 + 16 * 4 + nsplit * head_dim * 4 + (size_t)ktile_rows * head_dim * 2 + (((size_t)max_ctx * 2 + 15) & ~(size_t)15) + 16;
-}
-
 
 } // namespace ifa

@@ -218,10 +218,10 @@ __global__ void __launch_bounds__(QA_THREADS) k_dec_qkv_attn(const half_t *px, c
 
 // host side (one translation unit per weight format: ifa_dqkvattn_<format>.hip)
 bool dec_qkv_attn_supported(int w_dtype, int cols, int heads, int kv_heads, int head_dim, int num_cus, int *gk_out, int *rw_out);
-int dec_qkv_attn_launch(int w_dtype, int norm, bool kv_q8, int pb, bool kt, const DecGemvParams &P, const DecAttnParams &A, const DecQkvAttnExtra &E,
+int dec_qkv_attn_launch(int w_dtype, int norm, bool kv_q8, int pb, bool kt, bool ul, const DecGemvParams &P, const DecAttnParams &A, const DecQkvAttnExtra &E,
                         int max_ctx, hipStream_t s);
 template <int DT>
-int dec_qkv_attn_launch_dt(int norm, bool kv_q8, int pb, bool kt, int rw, const DecGemvParams &P, const DecAttnParams &A, const DecQkvAttnExtra &E,
+int dec_qkv_attn_launch_dt(int norm, bool kv_q8, int pb, bool kt, bool ul, int rw, const DecGemvParams &P, const DecAttnParams &A, const DecQkvAttnExtra &E,
                            int max_ctx, hipStream_t s);
 
 } // namespace ifa

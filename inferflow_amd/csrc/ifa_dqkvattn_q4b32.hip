@@ -4,8 +4,8 @@
 
 namespace ifa {
 
-extern template int dec_qkv_attn_launch_dt<Q3H_B64T1>(int, bool, int, bool, int, const DecGemvParams &, const DecAttnParams &, const DecQkvAttnExtra &, int, hipStream_t);
-template int dec_qkv_attn_launch_dt<Q4_B32T1A>(int, bool, int, bool, int, const DecGemvParams &, const DecAttnParams &, const DecQkvAttnExtra &, int, hipStream_t);
+extern template int dec_qkv_attn_launch_dt<Q3H_B64T1>(int, bool, int, bool, bool, int, const DecGemvParams &, const DecAttnParams &, const DecQkvAttnExtra &, int, hipStream_t);
+template int dec_qkv_attn_launch_dt<Q4_B32T1A>(int, bool, int, bool, bool, int, const DecGemvParams &, const DecAttnParams &, const DecQkvAttnExtra &, int, hipStream_t);
 
 // Which models take the fused launch: q / k / v of one int8-path format with a kernel instance; 128-wide heads; a grid of one
 // workgroup per CU that splits evenly into kv groups (gk workgroups each, a multiple of the query heads per group) whose
@@ -27,7 +27,7 @@ bool dec_qkv_attn_supported(int w_dtype, int cols, int heads, int kv_heads, int 
     return true;
 }
 
-int dec_qkv_attn_launch(int w_dtype, int norm, bool kv_q8, int pb, bool kt, const DecGemvParams &P0, const DecAttnParams &A, const DecQkvAttnExtra &E,
+int dec_qkv_attn_launch(int w_dtype, int norm, bool kv_q8, int pb, bool kt, bool ul, const DecGemvParams &P0, const DecAttnParams &A, const DecQkvAttnExtra &E,
                         int max_ctx, hipStream_t s)
 {
     DecGemvParams P = P0;
@@ -38,8 +38,8 @@ int dec_qkv_attn_launch(int w_dtype, int norm, bool kv_q8, int pb, bool kt, cons
     if (!dec_qkv_attn_supported(w_dtype, P.cols, A.heads, A.kv_heads, 128, A.kv_heads * E.gk, &gk, &rw) || gk != E.gk)
         return ifa_fail(IFA_ERR_ARG, "fused QKV + attention: unsupported shape");
     switch (w_dtype) {
-    case Q4_B32T1A: case Q4_B32T1B: return dec_qkv_attn_launch_dt<Q4_B32T1A>(norm, kv_q8, pb, kt, rw, P, A, E, max_ctx, s);
-    case Q3H_B64T1: return dec_qkv_attn_launch_dt<Q3H_B64T1>(norm, kv_q8, pb, kt, rw, P, A, E, max_ctx, s);
+    case Q4_B32T1A: case Q4_B32T1B: return dec_qkv_attn_launch_dt<Q4_B32T1A>(norm, kv_q8, pb, kt, ul, rw, P, A, E, max_ctx, s);
+    case Q3H_B64T1: return dec_qkv_attn_launch_dt<Q3H_B64T1>(norm, kv_q8, pb, kt, ul, rw, P, A, E, max_ctx, s);
     default: return ifa_fail(IFA_ERR_DTYPE, "fused QKV + attention: dtype %d", w_dtype);
     }
 }

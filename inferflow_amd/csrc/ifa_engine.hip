@@ -596,6 +596,26 @@ int ifa_model_fused_supported(ifa_model *m, char *why, size_t why_len)
     return ok ? 1 : 0;
 }
 
+// the decode route plan (ifa_decode_route.h) for tests: the pure function, and what the model's last decode call planned
+int ifa_decode_route_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    IFA_REQUIRE(facts && out && n_facts == DEC_ROUTE_N_FACTS && n_out >= DEC_ROUTE_N_OUT, "ifa_decode_route_plan: %d facts, %d outputs expected", DEC_ROUTE_N_FACTS, DEC_ROUTE_N_OUT);
+    DecRouteFacts f;
+    memcpy(&f, facts, sizeof(f));
+    IFA_REQUIRE(f.head_dim >= 8 && f.max_ctx >= 1, "ifa_decode_route_plan: head_dim %d, max_ctx %d", f.head_dim, f.max_ctx);
+    const DecRoute r = plan_decode_route(f);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
+int ifa_model_decode_route(ifa_model *m, int *out, int n_out)
+{
+    IFA_REQUIRE(m && out && n_out >= DEC_ROUTE_N_OUT + 3, "ifa_model_decode_route: %d outputs expected", DEC_ROUTE_N_OUT + 3);
+    memcpy(out, &m->route, sizeof(m->route));
+    out[DEC_ROUTE_N_OUT] = num_cus(); out[DEC_ROUTE_N_OUT + 1] = visible_cus(); out[DEC_ROUTE_N_OUT + 2] = waits_enabled() ? 1 : 0;
+    return IFA_OK;
+}
+
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes)
 {
     IFA_REQUIRE(m && name && dptr, "ifa_model_get_buffer: null pointer");

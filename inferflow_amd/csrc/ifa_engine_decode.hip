@@ -4,40 +4,9 @@
 
 namespace ifae {
 
-// keys split over workgroups past attn_split_ctx; 8 splits per head up to 2K keys, 16 up to 8K, 32 beyond (a head's K / V
-// history streams through that many CUs: 8 splits left 16K-key contexts at 2 TB/s).  The captured steps hold the choice.
-bool qkv_attn_layer_ok(const ifa_model *m, int l, int *gk_out);
-
-// From how many keys on a head's keys are split over workgroups.  attn_split_ctx >= 0: that many (0: never).  -1 (default): by what
-// the one-workgroup attention is -- as the tail of the QKV launch with the heads' workgroups unloaded in the 256-row bucket (attn_unload)
-// and the rows past the bucket pulled towards the L2 by the idle waves, it holds up to ~520 keys with one kv head per query head
-// (400 / 450 / 500 / 560 keys 689 / 674 / 661 / 635 tok/s against 658 / 655 / 653 / 651 split; Q8 cache 662 / 653 / 643 / 620 against
-// 642 / 639 / 638 / 635) and ~650 with grouped queries (Mixtral 560 keys 388 against 381): profiles/r06_attn_unload.log; 320 otherwise
-static int attn_split_threshold(const ifa_model *m)
-{
-    if (m->opt_attn_split_ctx >= 0) return m->opt_attn_split_ctx;
-    const ifa_model_config &c = m->cfg;
-    bool tail = m->opt_attn_unload && m->opt_fuse_attn && waits_enabled() && dec_attn_smem(c.head_dim, c.max_ctx, 256) <= IFA_LDS_LIMIT;
-    int gk = 0;
-    for (int l = 0; tail && l < c.layers; l++) if (!qkv_attn_layer_ok(m, l, &gk)) tail = false;
-    if (tail && (long long)c.kv_heads * gk > (long long)visible_cus()) tail = false;
-    if (!tail) return 320;
-    return c.heads > c.kv_heads ? 640 : 512;
-}
-
-void choose_attn_split(ifa_model *m, int reach)
-{
-    // splits per head by the context the call reaches: 8 up to 8192 keys, 16 above (round 6, second session, after the kernels lost their
-    // request chains: 2048 / 4096 / 8192 keys 563 / 484 / 404 tok/s with 8 splits against 535 / 483 / 400 with 16; 16384 keys 301 / 303 / 281
-    // with 8 / 16 / 32; Q8 cache 4096 keys 487 against 465 -- profiles/r06_long_context_decode.log.  Was 8 / 16 / 32 from 512 / 2048 / 8192.)
-    const int thr = attn_split_threshold(m);
-    const int want = (thr > 0 && reach > thr) ? (reach > 8192 ? 16 : 8) : 0;
-    if (want != m->attn_split) { m->attn_split = want; drop_graphs(m); }
-    // rows of the K / V cache the one-workgroup kernel requests before it knows the position: the bucket this call stays
-    // inside (a longer context only costs the direct loads of the rows past it)
-    const int pb = reach <= 64 ? 64 : (reach <= 128 ? 128 : 256);
-    if (pb != m->attn_pb) { m->attn_pb = pb; drop_graphs(m); }
-}
+// Which attention launch a step takes, with which kernel instance, is planned once per decode call by plan_decode_route
+// (ifa_decode_route.h; rules R1 - R10 and the measurements behind their numbers: DESIGN.md, "Decode route plan") from the facts
+// decode_route_ready collects; the launches below read m->route and decide nothing.
 
 // ------------------------------------------------------------------ dispatch
 // reads one dword every `stride` bytes: warms the TLB / pulls lines towards L2+MALL
@@ -77,30 +46,26 @@ int lmhead_grid(const DecLmHeadParams &P, int wgs_per_cu_opt)
     return std::max(1, std::min(num_cus() * per_cu, (nbatch + DEC_WAVES - 1) / DEC_WAVES));
 }
 
+// the instance of nj column chunks per lane (1 .. 16; two rows per batch up to 4), with or without the norm, alone or as the step's tail
+template <int NJ>
+static void lmhead_go(int nj, int norm, dim3 grid, size_t smem, hipStream_t s, const DecLmHeadParams &P, const DecStepTail *Z)
+{
+    if constexpr (NJ <= 16) {
+        constexpr int R = NJ <= 4 ? 2 : 1;
+        if (nj != NJ) return lmhead_go<NJ + 1>(nj, norm, grid, smem, s, P, Z);
+        if (Z) { if (norm) k_dec_lmhead_tail<NJ, R, 1><<<grid, dim3(DEC_THREADS), smem, s>>>(P, *Z); else k_dec_lmhead_tail<NJ, R, 0><<<grid, dim3(DEC_THREADS), smem, s>>>(P, *Z); }
+        else if (norm) k_dec_lmhead_f16<NJ, R, 1><<<grid, dim3(DEC_THREADS), smem, s>>>(P);
+        else k_dec_lmhead_f16<NJ, R, 0><<<grid, dim3(DEC_THREADS), smem, s>>>(P);
+    }
+}
+
 int launch_lmhead(const DecLmHeadParams &P, int norm, int wgs_per_cu_opt, hipStream_t s, const DecStepTail *Z)
 {
-    const int chunks = P.cols / 8;
-    const int nj = (chunks + 63) / 64;
+    const int nj = (P.cols / 8 + 63) / 64;
     if (P.cols % 8 != 0 || nj < 1 || nj > 16) return ifa_fail(IFA_ERR_ARG, "fused lm_head supports cols %% 8 == 0 and <= 8192 (got %d)", P.cols);
-    const int R = nj <= 4 ? 2 : 1;
-    const int nbatch = (P.rows + R - 1) / R;
-    (void)nbatch;
     dim3 grid((unsigned)lmhead_grid(P, wgs_per_cu_opt));
     const size_t smem = (((size_t)P.cols * 2 + 15) & ~(size_t)15) + 132 * 4 + 16;
-#define IFA_LM(NJV, RV) \
-    case NJV: if (norm) k_dec_lmhead_f16<NJV, RV, 1><<<grid, dim3(DEC_THREADS), smem, s>>>(P); \
-              else k_dec_lmhead_f16<NJV, RV, 0><<<grid, dim3(DEC_THREADS), smem, s>>>(P); break;
-#define IFA_LMT(NJV, RV) \
-    case NJV: if (norm) k_dec_lmhead_tail<NJV, RV, 1><<<grid, dim3(DEC_THREADS), smem, s>>>(P, *Z); \
-              else k_dec_lmhead_tail<NJV, RV, 0><<<grid, dim3(DEC_THREADS), smem, s>>>(P, *Z); break;
-    if (Z) {
-        switch (nj) { IFA_LMT(1, 2) IFA_LMT(2, 2) IFA_LMT(3, 2) IFA_LMT(4, 2) IFA_LMT(5, 1) IFA_LMT(6, 1) IFA_LMT(7, 1) IFA_LMT(8, 1)
-                      IFA_LMT(9, 1) IFA_LMT(10, 1) IFA_LMT(11, 1) IFA_LMT(12, 1) IFA_LMT(13, 1) IFA_LMT(14, 1) IFA_LMT(15, 1) IFA_LMT(16, 1) }
-    } else
-    switch (nj) { IFA_LM(1, 2) IFA_LM(2, 2) IFA_LM(3, 2) IFA_LM(4, 2) IFA_LM(5, 1) IFA_LM(6, 1) IFA_LM(7, 1) IFA_LM(8, 1)
-                  IFA_LM(9, 1) IFA_LM(10, 1) IFA_LM(11, 1) IFA_LM(12, 1) IFA_LM(13, 1) IFA_LM(14, 1) IFA_LM(15, 1) IFA_LM(16, 1) }
-#undef IFA_LM
-#undef IFA_LMT
+    lmhead_go<1>(nj, norm, grid, smem, s, P, Z);
     IFA_LAUNCH_CHECK();
     return IFA_OK;
 }
@@ -179,7 +144,7 @@ int sep_norm(ifa_model *m, const half_t *x, const Tensor &w, const Tensor &b, ha
 
 // Can layer l take the attention as the tail of its QKV launch?  (the one-workgroup-per-head attention, RMS-norm wiring, q / k / v
 // of one int8-path format with a kernel instance, no tensor-parallel pending sum)
-bool qkv_attn_layer_ok(const ifa_model *m, int l, int *gk_out)
+static bool qkv_attn_layer_ok(const ifa_model *m, int l, int *gk_out, int *rw_out)
 {
     const ifa_model_config &c = m->cfg;
     const Layer &L = m->layers[(size_t)l];
@@ -188,21 +153,56 @@ bool qkv_attn_layer_ok(const ifa_model *m, int l, int *gk_out)
     if (!wq.present() || !wk.present() || !wv.present() || !wq.tiled || !wk.tiled || !wv.tiled) return false;
     if (!fused_int8(wq.dtype) || !same_fmt(wq.dtype, wk.dtype) || !same_fmt(wq.dtype, wv.dtype)) return false;
     if ((int)wq.rows != c.heads * c.head_dim || (int)wk.rows != c.kv_heads * c.head_dim || (int)wv.rows != c.kv_heads * c.head_dim) return false;
-    int rw = 0;
-    return dec_qkv_attn_supported(wq.dtype, (int)wq.cols, c.heads, c.kv_heads, c.head_dim, num_cus(), gk_out, &rw);
+    return dec_qkv_attn_supported(wq.dtype, (int)wq.cols, c.heads, c.kv_heads, c.head_dim, num_cus(), gk_out, rw_out);
 }
 
-// decides qa_on for the next captured step and allocates what the fused launch needs (never under capture)
-int qkv_attn_ready(ifa_model *m)
+// what weights and wiring allow of the chained FFN launch (DecRouteFacts::chain_level): dense gated FFN behind an RMS pre-norm,
+// sequential wiring, W1 / W3 / W2 (level 2: and Wo) of one format with an instance
+static int chain_level(const ifa_model *m)
 {
     const ifa_model_config &c = m->cfg;
-    int want = m->opt_fuse_attn && waits_enabled() && !m->attn_split && dec_attn_smem(c.head_dim, c.max_ctx, 256) <= IFA_LDS_LIMIT;
-    int gk = 0;
-    for (int l = 0; want && l < c.layers; l++) if (!qkv_attn_layer_ok(m, l, &gk)) want = 0;
-    // a head's attention waits for the gk workgroups of its kv group: the grid (kv_heads * gk workgroups of 512 threads at 256
-    // registers, one per CU) must be resident at once on the CUs this process may use (CU mask, partitioned device)
-    if (want && (long long)c.kv_heads * gk > (long long)visible_cus()) want = 0;
-    if (want && !m->qa_gran) {
+    if (c.norm_kind != 0 || c.tp_size > 1 || c.experts != 0 || c.parallel_attn || c.share_input) return 0;
+    int level = 2;
+    for (int l = 0; level && l < c.layers; l++) {
+        const Layer &L = m->layers[(size_t)l];
+        const Tensor &wo = L.t[T_WO], &w1 = L.t[T_W1], &w3 = L.t[T_W3], &w2 = L.t[T_W2];
+        if (!w1.present() || !w1.tiled || !w3.present() || !w3.tiled || !w2.present() || !w2.tiled || !L.t[T_FFN_NORM].present()
+            || (int)w1.cols != c.dim || (int)w2.rows != c.dim || w2.cols != w1.rows || w3.rows != w1.rows || !same_fmt(w1.dtype, w3.dtype)
+            || !dec_chain_supported(w1.dtype, w2.dtype, w1.dtype, c.dim, (int)w1.rows, false, c.dim, num_cus()))
+            level = 0;
+        else if (level == 2 && (!wo.present() || !wo.tiled || (int)wo.rows != c.dim
+                                || !dec_chain_supported(w1.dtype, w2.dtype, wo.dtype, c.dim, (int)w1.rows, true, (int)wo.cols, num_cus())))
+            level = 1;
+    }
+    return level;
+}
+
+static DecRouteFacts route_facts(const ifa_model *m, int reach, bool own_launches)
+{
+    const ifa_model_config &c = m->cfg;
+    DecRouteFacts f;
+    f.head_dim = c.head_dim; f.heads = c.heads; f.kv_heads = c.kv_heads; f.max_ctx = c.max_ctx; f.kv_q8 = c.kv_dtype == Q8_B32T2;
+    f.reach = reach;
+    f.attn_split_ctx = m->opt_attn_split_ctx; f.attn_nsplits = m->opt_attn_nsplits; f.attn_kt = m->opt_attn_kt; f.attn_unload = m->opt_attn_unload;
+    f.fuse_attn = m->opt_fuse_attn; f.fuse_ffn = m->opt_fuse_ffn; f.attn_q8 = m->opt_attn_q8;
+    f.waits = waits_enabled(); f.num_cus = num_cus(); f.visible_cus = visible_cus();
+    f.have_attq = m->attq ? 1 : 0; f.own_launches = own_launches;
+    // (the per-layer loops only where their answer can matter)
+    f.tail_layers_ok = f.fuse_attn && f.waits;
+    for (int l = 0; f.tail_layers_ok && l < c.layers; l++) if (!qkv_attn_layer_ok(m, l, &f.gk, &f.rw)) f.tail_layers_ok = 0;
+    f.chain_level = (f.fuse_ffn && f.waits && !own_launches) ? chain_level(m) : 0;
+    return f;
+}
+
+// Plans the route of a decode call that reaches `reach` keys (the captured steps hold it: they go when it changes) and allocates what
+// its launches need (never under capture).  own_launches: the tensor-parallel step -- split and bucket are chosen, the fused launches are off.
+int decode_route_ready(ifa_model *m, int reach, bool own_launches)
+{
+    const ifa_model_config &c = m->cfg;
+    const DecRoute route = plan_decode_route(route_facts(m, reach, own_launches));
+    m->route_reach = reach;
+    if (!(route == m->route)) { m->route = route; drop_graphs(m); }
+    if (route.kind == DEC_ROUTE_FUSED_TAIL && !m->qa_gran) {
         const size_t n = (size_t)c.layers * (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim;
         DevBuf<unsigned long long> gran; DevBuf<unsigned> call, err;      // installed together, zeroed
         int rc;
@@ -213,23 +213,7 @@ int qkv_attn_ready(ifa_model *m)
         m->qa_gran = std::move(gran); m->qa_call = std::move(call); m->qa_err = std::move(err);
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     }
-    // the chained FFN launch: dense gated FFN behind an RMS pre-norm, sequential wiring, W1 / W3 / W2 (and Wo) of one format with an
-    // instance, one workgroup per CU resident at once
-    int want_ch = (m->opt_fuse_ffn && waits_enabled() && c.norm_kind == 0 && c.tp_size <= 1 && c.experts == 0
-                   && !c.parallel_attn && !c.share_input && num_cus() <= visible_cus()) ? std::min(m->opt_fuse_ffn, 2) : 0;
-    if (want_ch == 2 && (!m->attq || !m->opt_attn_q8 || c.head_dim % 32 != 0)) want_ch = 1;
-    for (int l = 0; want_ch && l < c.layers; l++) {
-        const Layer &L = m->layers[(size_t)l];
-        const Tensor &wo = L.t[T_WO], &w1 = L.t[T_W1], &w3 = L.t[T_W3], &w2 = L.t[T_W2];
-        if (!w1.present() || !w1.tiled || !w3.present() || !w3.tiled || !w2.present() || !w2.tiled || !L.t[T_FFN_NORM].present()
-            || (int)w1.cols != c.dim || (int)w2.rows != c.dim || w2.cols != w1.rows || w3.rows != w1.rows || !same_fmt(w1.dtype, w3.dtype)
-            || !dec_chain_supported(w1.dtype, w2.dtype, w1.dtype, c.dim, (int)w1.rows, false, c.dim, num_cus()))
-            want_ch = 0;
-        else if (want_ch == 2 && (!wo.present() || !wo.tiled || (int)wo.rows != c.dim
-                                  || !dec_chain_supported(w1.dtype, w2.dtype, wo.dtype, c.dim, (int)w1.rows, true, (int)wo.cols, num_cus())))
-            want_ch = 1;
-    }
-    if (want_ch && !m->ch_gran) {
+    if (route.chain && !m->ch_gran) {
         const size_t n = (size_t)c.layers * (size_t)(c.dim + (int)m->layers[0].t[T_W1].rows);
         DevBuf<uint32_t> gran, flags; DevBuf<unsigned> call, err;      // installed together, zeroed
         int rc;
@@ -242,9 +226,6 @@ int qkv_attn_ready(ifa_model *m)
         if (call) m->qa_call = std::move(call);
         if (err) m->qa_err = std::move(err);
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-    }
-    if (want != m->qa_on || (want && gk != m->qa_gk) || want_ch != m->ch_on) {
-        m->qa_on = want; m->qa_gk = gk; m->ch_on = want_ch; drop_graphs(m);
     }
     return IFA_OK;
 }
@@ -276,35 +257,22 @@ int launch_qkv_attn(ifa_model *m, int l, const half_t *x, unsigned tag_add)
     DecAttnParams A; attn_params(m, l, A);
     DecQkvAttnExtra E; memset(&E, 0, sizeof(E));
     E.gran = m->qa_gran + (size_t)l * (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim;
-    E.epoch = m->qa_call; E.epoch_add = tag_add; E.err = m->qa_err; E.timeout_us = m->opt_fuse_attn_timeout_us; E.gk = m->qa_gk;
-    const int pb = (m->attn_pb == 64 || m->attn_pb == 128) ? m->attn_pb : 256;
-    const bool kt = m->opt_attn_kt && !A.kv_q8 && dec_attn_smem(c.head_dim, c.max_ctx, pb) <= IFA_LDS_LIMIT;
-    E.unload = ((m->opt_attn_unload >= 1 && pb == 256) || (m->opt_attn_unload >= 2 && pb == 128 && (kt || A.kv_q8))) ? 1 : 0;      // (2: the 128-row bucket too -- measurement)
-    return dec_qkv_attn_launch(L.t[T_WQ].dtype, 1, A.kv_q8 != 0, pb, kt, P, A, E, c.max_ctx, m->stream);
+    const DecRoute &R = m->route;
+    E.epoch = m->qa_call; E.epoch_add = tag_add; E.err = m->qa_err; E.timeout_us = m->opt_fuse_attn_timeout_us; E.gk = R.gk; E.unload = R.ul;
+    return dec_qkv_attn_launch(L.t[T_WQ].dtype, 1, A.kv_q8 != 0, R.pb, R.kt != 0, R.ul != 0, P, A, E, c.max_ctx, m->stream);
 }
 
 int launch_qkv(ifa_model *m, int l, const half_t *x)
 {
     const ifa_model_config &c = m->cfg;
     Layer &L = m->layers[(size_t)l];
-    DecGemvParams P; memset(&P, 0, sizeof(P));
-    P.x = x; P.norm_w = (const half_t *)L.t[T_ATTN_NORM].data; P.norm_b = (const half_t *)L.t[T_ATTN_NORM_B].data;
-    P.multi_base = c.attn_norm_base; P.eps = c.eps; P.cols = c.dim; P.nblk = c.dim / 32;
-    if (c.parallel_attn) P.xn_out = m->xn;         // the normalised input: parallel-attention models feed it to the FFN
+    DecGemvParams P; qkv_params(m, l, x, P);      // (xn_out: parallel-attention models feed the normalised input to the FFN)
     const bool std_norm = c.norm_kind != 0;
     if (std_norm) {
         int rc = sep_norm(m, x, L.t[T_ATTN_NORM], L.t[T_ATTN_NORM_B], m->xn);
         if (rc) return rc;
         P.x = m->xn; P.norm_w = nullptr; P.norm_b = nullptr; P.xn_out = nullptr;
     }
-    const int ids[3] = {T_WQ, T_WK, T_WV}; const int bids[3] = {T_WQ_B, T_WK_B, T_WV_B};
-    const size_t QDd = (size_t)c.heads * c.head_dim, KVDd = (size_t)c.kv_heads * c.head_dim;
-    half_t *outs[3] = {m->dqkv, m->dqkv + QDd, m->dqkv + QDd + KVDd};
-    for (int i = 0; i < 3; i++) {
-        P.W0[i] = wbytes(L.t[ids[i]]); P.b0[i] = (const half_t *)L.t[bids[i]].data;
-        P.y[i] = outs[i]; P.rows[i] = (int)L.t[ids[i]].rows;
-    }
-    P.nsets = 3;
     if (m->pend.on && !std_norm) {      // x = pend.x + merged product: formed in this kernel's prologue, stored as the new layer input
         P.x = m->pend.x; P.x_add = m->pend.add; P.x_add_bias = m->pend.bias; P.xsum_out = m->pend.out;
         m->pend.on = false;
@@ -316,6 +284,7 @@ int launch_qkv(ifa_model *m, int l, const half_t *x)
     if (same_fmt(L.t[T_WQ].dtype, L.t[T_WK].dtype) && same_fmt(L.t[T_WQ].dtype, L.t[T_WV].dtype)) return go(L.t[T_WQ].dtype, P);
     // mixed formats (e.g. wq quantised, wk / wv left F16 by the threshold rule): one launch per matrix; the first one forms
     // a pending sum, the others read the stored result
+    const int ids[3] = {T_WQ, T_WK, T_WV};
     for (int i = 0; i < 3; i++) {
         DecGemvParams Q = P;
         Q.nsets = 1; Q.W0[0] = P.W0[i]; Q.b0[0] = P.b0[i]; Q.y[0] = P.y[i]; Q.rows[0] = P.rows[i];
@@ -343,86 +312,45 @@ void attn_params(ifa_model *m, int l, DecAttnParams &A)
     A.out = m->att; A.max_ctx = c.max_ctx; A.xq = (c.head_dim % 32 == 0) ? m->attq : nullptr; A.trace = g_trace_ptr;
 }
 
+// the route's attention launch(es): keys split over workgroups (scores in global memory: past the split threshold, or when a head's
+// score row [max_ctx] does not fit the LDS), else one workgroup per head in the planned entry bucket
 int launch_attn(ifa_model *m, int l)
 {
     const ifa_model_config &c = m->cfg;
-    Layer &L = m->layers[(size_t)l];
-    const int rope_dims = (int)(c.head_dim * c.partial_rotary + 0.5f);
-    DecAttnParams A; memset(&A, 0, sizeof(A));
-    A.q = m->dqkv; A.k_new = m->dqkv + (size_t)c.heads * c.head_dim; A.v_new = A.k_new + (size_t)c.kv_heads * c.head_dim; A.kcache = (uint8_t *)L.kcache; A.vcache = (uint8_t *)L.vcache;
-    A.state = m->state; A.rope_tab = m->rope_tab; A.heads = c.heads; A.kv_heads = c.kv_heads;
-    A.kv_q8 = c.kv_dtype == Q8_B32T2; A.kq_scale = c.use_alibi ? 1.0f : c.kq_scale;
-    A.rope_order = c.rope_order; A.rope_cols = rope_dims;
-    A.alibi = c.use_alibi; A.alibi_base = c.tp_rank * c.heads; A.alibi_total = c.heads * std::max(1, c.tp_size);
-    A.out = m->att; A.max_ctx = c.max_ctx; A.xq = (c.head_dim % 32 == 0) ? m->attq : nullptr; A.trace = g_trace_ptr;
-    // the one-workgroup kernel keeps a head's score row [max_ctx] in LDS: past the device limit (160 KiB: ~75K tokens of
-    // context at head_dim 128) the keys-split-over-workgroups kernels run from position 0 on (scores in global memory)
-    const bool lds_split = dec_attn_smem(c.head_dim, c.max_ctx) > IFA_LDS_LIMIT;
-    if (m->attn_split || lds_split) {
-        // splits per head: 8, or what the decode call chose for the context it will reach (attn_split = 8 / 16 / 32); when only
-        // the LDS forces the split (very large max_context_len) as many as keep a split's probabilities inside the LDS
-        int nsp = m->attn_split > 1 ? m->attn_split : 8;
-        while (nsp < DEC_ATTN_MAX_SPLITS && dec_attn_pv_smem(c.head_dim, c.max_ctx, nsp) > IFA_LDS_LIMIT) nsp *= 2;
-        if (m->opt_attn_nsplits > 0) nsp = std::min(m->opt_attn_nsplits, DEC_ATTN_MAX_SPLITS);
-        m->attn_ws.nsplits = nsp;
-        const dim3 g2((unsigned)c.heads, (unsigned)nsp);
-        const size_t psmem = dec_attn_pv_smem(c.head_dim, c.max_ctx, nsp);
-        const size_t ssmem = dec_attn_scores_smem(c.head_dim, false);      // staging of 256 F16 key rows
-        if (psmem > IFA_LDS_LIMIT) return ifa_fail(IFA_ERR_ARG, "fused attention: max_context_len %d needs %zu bytes of LDS per workgroup", c.max_ctx, psmem);
-#define IFA_ATTN_S(HDV) \
-    case HDV: if (A.kv_q8) { k_dec_attn_scores<HDV, true><<<g2, dim3(256), 16, m->stream>>>(A, m->attn_ws); \
-                             if (psmem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_dec_attn_pv<HDV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmem)); \
-                             k_dec_attn_pv<HDV, true><<<g2, dim3(256), psmem, m->stream>>>(A, m->attn_ws); } \
-              else { if (ssmem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_dec_attn_scores<HDV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ssmem)); \
-                     k_dec_attn_scores<HDV, false><<<g2, dim3(256), ssmem, m->stream>>>(A, m->attn_ws); \
-                     if (psmem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_dec_attn_pv<HDV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmem)); \
-                     k_dec_attn_pv<HDV, false><<<g2, dim3(256), psmem, m->stream>>>(A, m->attn_ws); } \
-              k_dec_attn_combine<HDV><<<dim3((unsigned)c.heads), dim3(HDV), 0, m->stream>>>(m->attn_ws, m->att, A.xq, c.heads); break;
-        // head sizes that are not whole Q8 blocks (48, 80) exist with an F16 KV cache only
-#define IFA_ATTN_SF(HDV) \
-    case HDV: if (ssmem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_dec_attn_scores<HDV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ssmem)); \
-              k_dec_attn_scores<HDV, false><<<g2, dim3(256), ssmem, m->stream>>>(A, m->attn_ws); \
-              if (psmem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_dec_attn_pv<HDV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)psmem)); \
-              k_dec_attn_pv<HDV, false><<<g2, dim3(256), psmem, m->stream>>>(A, m->attn_ws); \
-              k_dec_attn_combine<HDV><<<dim3((unsigned)c.heads), dim3(HDV), 0, m->stream>>>(m->attn_ws, m->att, A.xq, c.heads); break;
-        switch (c.head_dim) {
-            IFA_ATTN_S(32) IFA_ATTN_S(64) IFA_ATTN_S(96) IFA_ATTN_S(128) IFA_ATTN_SF(48) IFA_ATTN_SF(80)
-        default: return ifa_fail(IFA_ERR_ARG, "fused attention: head_dim %d", c.head_dim);
-        }
-#undef IFA_ATTN_SF
-#undef IFA_ATTN_S
-        IFA_LAUNCH_CHECK();
-        return IFA_OK;
+    // A caller that runs the attention as a launch of its own where the stored plan has none -- the step's route is the fused tail
+    // (the timing entry), or no call has been planned yet (ifa_model_tp_attn driven layer by layer) -- takes the plan of the last
+    // reach with launches of its own.  Pure host work: fine under capture.
+    const bool unplanned = m->route.kind == DEC_ROUTE_FUSED_TAIL || (m->route.lds_attn | m->route.lds_pv) == 0;
+    const DecRoute R = unplanned ? plan_decode_route(route_facts(m, m->route_reach, true)) : m->route;
+    hipStream_t s = m->stream;
+    DecAttnParams A; attn_params(m, l, A);
+    if (R.kind == DEC_ROUTE_SPLIT) {
+        if (R.error) return ifa_fail(IFA_ERR_ARG, "fused attention: max_context_len %d needs %d bytes of LDS per workgroup", c.max_ctx, R.lds_pv);
+        DecAttnSplitWs ws = m->attn_ws; ws.nsplits = R.nsplits;
+        const dim3 g2((unsigned)c.heads, (unsigned)R.nsplits);
+        return attn_dispatch(c.head_dim, A.kv_q8 != 0, [&](auto hd, auto q8) {
+            constexpr int HD = decltype(hd)::value; constexpr bool Q8 = decltype(q8)::value;
+            int rc;
+            if ((rc = launch_lds(k_dec_attn_scores<HD, Q8>, g2, dim3(256), (size_t)R.lds_scores, s, A, ws))) return rc;
+            if ((rc = launch_lds(k_dec_attn_pv<HD, Q8>, g2, dim3(256), (size_t)R.lds_pv, s, A, ws))) return rc;
+            return launch_lds(k_dec_attn_combine<HD>, dim3((unsigned)c.heads), dim3(HD), 0, s, ws, m->att.get(), A.xq, c.heads);
+        });
     }
-    const int pb = (m->attn_pb == 64 || m->attn_pb == 128) ? m->attn_pb : 256;
-    const bool kt = m->opt_attn_kt && !A.kv_q8 && (c.head_dim == 32 || c.head_dim == 64 || c.head_dim == 128)
-        && dec_attn_smem(c.head_dim, c.max_ctx, pb) <= IFA_LDS_LIMIT;
-    const size_t asmem = dec_attn_smem(c.head_dim, c.max_ctx, kt ? pb : 0);
-    const dim3 grid((unsigned)c.heads), block(256);
-    // (attention_lds_ok() routed contexts whose score row does not fit the 160 KiB LDS to the split kernels above)
-#define IFA_ATTN_GO(HDV, Q8V, PBV, KTV) do { \
-        auto kern = k_dec_attn<HDV, Q8V, false, PBV, KTV>; \
-        if (asmem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)asmem)); \
-        kern<<<grid, block, asmem, m->stream>>>(A.q, A.kcache, A.vcache, A.heads, A.kv_heads, A); } while (0)
-#define IFA_ATTN_PB(HDV, Q8V, KTV) do { if (pb == 64) IFA_ATTN_GO(HDV, Q8V, 64, KTV); else if (pb == 128) IFA_ATTN_GO(HDV, Q8V, 128, KTV); else IFA_ATTN_GO(HDV, Q8V, 256, KTV); } while (0)
-    // head sizes with a power-of-two number of 16-byte pieces take the K rows through the LDS tile (F16 cache)
-#define IFA_ATTN(HDV) \
-    case HDV: if (A.kv_q8) IFA_ATTN_PB(HDV, true, false); else if (kt) IFA_ATTN_PB(HDV, false, true); else IFA_ATTN_PB(HDV, false, false); break;
-#define IFA_ATTN_Q(HDV) \
-    case HDV: if (A.kv_q8) IFA_ATTN_GO(HDV, true, 256, false); else IFA_ATTN_GO(HDV, false, 256, false); break;
-#define IFA_ATTN_F(HDV) \
-    case HDV: IFA_ATTN_GO(HDV, false, 256, false); break;
-    switch (c.head_dim) {
-        IFA_ATTN(32) IFA_ATTN(64) IFA_ATTN_Q(96) IFA_ATTN(128) IFA_ATTN_F(48) IFA_ATTN_F(80)
-    default: return ifa_fail(IFA_ERR_ARG, "fused attention: head_dim %d", c.head_dim);
-    }
-#undef IFA_ATTN_Q
-#undef IFA_ATTN_PB
-#undef IFA_ATTN_GO
-#undef IFA_ATTN_F
-#undef IFA_ATTN
-    IFA_LAUNCH_CHECK();
-    return IFA_OK;
+    return attn_dispatch(c.head_dim, A.kv_q8 != 0, [&](auto hd, auto q8) {
+        constexpr int HD = decltype(hd)::value; constexpr bool Q8 = decltype(q8)::value;
+        // head sizes with a power-of-two number of 16-byte pieces have the three entry buckets and, on an F16 cache, the K tile
+        constexpr bool pow2 = HD == 32 || HD == 64 || HD == 128;
+        auto go = [&](auto pb, auto kt) -> int {
+            constexpr int PB = decltype(pb)::value; constexpr bool KT = decltype(kt)::value;
+            if constexpr ((PB != 256 && !pow2) || (KT && (Q8 || !pow2)))
+                return ifa_fail(IFA_ERR_ARG, "fused attention: no instance for head_dim %d, Q8 cache %d, %d-row bucket, K tile %d", HD, (int)Q8, PB, (int)KT);
+            else
+                return launch_lds(k_dec_attn<HD, Q8, false, PB, KT>, dim3((unsigned)c.heads), dim3(256), (size_t)R.lds_attn, s, A.q, A.kcache, A.vcache, A.heads, A.kv_heads, A);
+        };
+        auto by_kt = [&](auto pb) { return R.kt ? go(pb, std::true_type{}) : go(pb, std::false_type{}); };
+        using std::integral_constant;
+        return R.pb == 64 ? by_kt(integral_constant<int, 64>{}) : R.pb == 128 ? by_kt(integral_constant<int, 128>{}) : by_kt(integral_constant<int, 256>{});
+    });
 }
 
 // partial != nullptr (tensor parallel): write the un-merged product there, no bias, no residual
@@ -433,31 +361,34 @@ static int native_fmt(const ifa_model *m, const Tensor &t, const uint8_t *&w)
     return t.dtype;
 }
 
+// Wo over the attention output.  partial: the un-merged product goes there (no bias, no residual); else a = Wo att (+ bias) with the
+// layer input x as the residual operand
+void wo_params(ifa_model *m, int l, const half_t *x, half_t *partial, DecGemvParams &P)
+{
+    Layer &L = m->layers[(size_t)l];
+    memset(&P, 0, sizeof(P));
+    P.x = m->att; P.cols = (int)L.t[T_WO].cols; P.nblk = P.cols / 32; P.eps = m->cfg.eps;
+    P.W0[0] = wbytes(L.t[T_WO]); P.rows[0] = (int)L.t[T_WO].rows; P.nsets = 1;
+    if (partial) { P.y[0] = partial; return; }
+    P.b0[0] = (const half_t *)L.t[T_WO_B].data;
+    P.y[0] = m->a; P.residual = x;
+    if (scale_on(m->cfg.attn_out_scale)) P.pre_scale = m->cfg.attn_out_scale;      // Scale(self_att_out) fused in front of the residual add
+}
+
 int launch_wo(ifa_model *m, int l, const half_t *x, half_t *partial)
 {
     Layer &L = m->layers[(size_t)l];
-    DecGemvParams P; memset(&P, 0, sizeof(P));
-    P.x = m->att; P.cols = (int)L.t[T_WO].cols; P.nblk = P.cols / 32; P.eps = m->cfg.eps;
-    P.W0[0] = wbytes(L.t[T_WO]); P.rows[0] = (int)L.t[T_WO].rows; P.nsets = 1;
+    DecGemvParams P; wo_params(m, l, x, partial, P);
     // the attention kernel left its output quantised (XqImage): the GEMV needs no prologue.  Rows longer than a lane's
     // register image (chunked kernel) keep the in-kernel quantiser
     const bool preq = m->attq && m->opt_attn_q8 && m->cfg.head_dim % 32 == 0 && P.cols == m->cfg.heads * m->cfg.head_dim && fused_int8(L.t[T_WO].dtype)
         && dec_gemv_supported(L.t[T_WO].dtype, (size_t)P.cols);
     if (preq) P.x = reinterpret_cast<const half_t *>(m->attq.get());      // NORM == 2 kernels read the quantised image through P.x
     const int dto = native_fmt(m, L.t[T_WO], P.W0[0]);
-    if (partial) {
-        P.y[0] = partial;
-        return preq ? launch_dec_gemv<EPI_PLAIN, 2>(dto, P, m->opt_rpw_wo, m->stream)
-                    : launch_dec_gemv<EPI_PLAIN, 0>(dto, P, m->opt_rpw_wo, m->stream);
-    }
-    P.b0[0] = (const half_t *)L.t[T_WO_B].data;
-    P.y[0] = m->a; P.residual = x;
-    if (scale_on(m->cfg.attn_out_scale)) P.pre_scale = m->cfg.attn_out_scale;      // Scale(self_att_out) fused in front of the residual add
-    if (m->cfg.parallel_attn || m->cfg.share_input)      // the residual is added once, after the FFN (inference_worker.cc:847-851)
-        return preq ? launch_dec_gemv<EPI_PLAIN, 2>(dto, P, m->opt_rpw_wo, m->stream)
-                    : launch_dec_gemv<EPI_PLAIN, 0>(dto, P, m->opt_rpw_wo, m->stream);
-    return preq ? launch_dec_gemv<EPI_RESIDUAL, 2>(dto, P, m->opt_rpw_wo, m->stream)
-                : launch_dec_gemv<EPI_RESIDUAL, 0>(dto, P, m->opt_rpw_wo, m->stream);
+    // (parallel attention / shared input: the residual is added once, after the FFN -- inference_worker.cc:847-851)
+    const bool plain = partial || m->cfg.parallel_attn || m->cfg.share_input;
+    if (preq) return plain ? launch_dec_gemv<EPI_PLAIN, 2>(dto, P, m->opt_rpw_wo, m->stream) : launch_dec_gemv<EPI_RESIDUAL, 2>(dto, P, m->opt_rpw_wo, m->stream);
+    return plain ? launch_dec_gemv<EPI_PLAIN, 0>(dto, P, m->opt_rpw_wo, m->stream) : launch_dec_gemv<EPI_RESIDUAL, 0>(dto, P, m->opt_rpw_wo, m->stream);
 }
 
 void moe_params(ifa_model *m, Layer &L, DecGemvParams &P, int slot, int tab_off)
@@ -469,16 +400,34 @@ void moe_params(ifa_model *m, Layer &L, DecGemvParams &P, int slot, int tab_off)
     P.moe_slot = slot; P.moe_tab_off = tab_off;
 }
 
+// the input side of W1 | W3: a (the attention output + residual) behind the FFN pre-norm
+static void ffn_in_params(ifa_model *m, Layer &L, DecGemvParams &P)
+{
+    const ifa_model_config &c = m->cfg;
+    memset(&P, 0, sizeof(P));
+    P.x = m->a; P.norm_w = (const half_t *)L.t[T_FFN_NORM].data; P.norm_b = (const half_t *)L.t[T_FFN_NORM_B].data;
+    P.eps = c.eps; P.cols = c.dim; P.nblk = c.dim / 32; P.act_kind = c.act_kind; P.multi_base = c.ffn_norm_base;
+}
+
+// dense t1 = act(W1 n) [* (W3 n)]
+void ffn13_params(ifa_model *m, int l, DecGemvParams &P)
+{
+    Layer &L = m->layers[(size_t)l];
+    ffn_in_params(m, L, P);
+    P.W0[0] = wbytes(L.t[T_W1]); P.b0[0] = (const half_t *)L.t[T_W1_B].data;
+    P.y[0] = m->t1; P.rows[0] = (int)L.t[T_W1].rows; P.nsets = 1;
+    if (L.t[T_W3].present()) { P.W1 = wbytes(L.t[T_W3]); P.b1 = (const half_t *)L.t[T_W3_B].data; }
+}
+
 // moe_slot >= 0: the FFN of the expert the router put in that slot (weights through L.moe_table)
 int launch_ffn13(ifa_model *m, int l, int moe_slot, const half_t *x_layer, int moe_nslots)
 {
     const ifa_model_config &c = m->cfg;
     Layer &L = m->layers[(size_t)l];
-    DecGemvParams P; memset(&P, 0, sizeof(P));
-    P.x = m->a; P.norm_w = (const half_t *)L.t[T_FFN_NORM].data; P.norm_b = (const half_t *)L.t[T_FFN_NORM_B].data;
-    P.eps = c.eps; P.cols = c.dim; P.nblk = c.dim / 32; P.act_kind = c.act_kind; P.multi_base = c.ffn_norm_base;
+    DecGemvParams P;
     if (moe_slot >= 0) {
         const Tensor &e1 = L.experts[0], &e3 = L.experts[2];
+        ffn_in_params(m, L, P);
         moe_params(m, L, P, moe_slot, 0);
         P.W0[0] = (const uint8_t *)e1.tiled; P.W1 = (const uint8_t *)e3.tiled;   // (replaced by the table lookup)
         // moe_nslots router slots in one launch: set i = the expert of slot moe_slot + i, its product at t1 + i * ffn
@@ -488,8 +437,7 @@ int launch_ffn13(ifa_model *m, int l, int moe_slot, const half_t *x_layer, int m
         if (e3.present()) return launch_dec_gemv<EPI_MOE_GLU, 1>(e1.dtype, P, m->opt_rpw_ffn, m->stream);
         return launch_dec_gemv<EPI_MOE_ACT, 1>(e1.dtype, P, m->opt_rpw_ffn, m->stream);
     }
-    P.W0[0] = wbytes(L.t[T_W1]); P.b0[0] = (const half_t *)L.t[T_W1_B].data;
-    P.y[0] = m->t1; P.rows[0] = (int)L.t[T_W1].rows; P.nsets = 1;
+    ffn13_params(m, l, P);
     // FFN input (inference_worker.cc:853-872): the attention's normalised input (parallel attention), the layer input
     // (shared input) or the attention output + residual; then the FFN pre-norm if the model has one
     const half_t *ff_in = c.parallel_attn ? m->xn : (c.share_input ? x_layer : m->a);
@@ -502,7 +450,6 @@ int launch_ffn13(ifa_model *m, int l, int moe_slot, const half_t *x_layer, int m
     }
     if (!need_norm) { P.norm_w = nullptr; P.norm_b = nullptr; }
     const bool glu = L.t[T_W3].present();
-    if (glu) { P.W1 = wbytes(L.t[T_W3]); P.b1 = (const half_t *)L.t[T_W3_B].data; }
     int dtw = L.t[T_W1].dtype;
     if (m->opt_q3h_native && L.t[T_W1].q3hn && (!glu || L.t[T_W3].q3hn)) {      // both matrices of the pair in the native form, or neither
         dtw = native_fmt(m, L.t[T_W1], P.W0[0]);
@@ -516,12 +463,28 @@ int launch_ffn13(ifa_model *m, int l, int moe_slot, const half_t *x_layer, int m
     return glu ? launch_dec_gemv<EPI_GLU, 0>(dtw, P, m->opt_rpw_ffn, m->stream) : launch_dec_gemv<EPI_ACT, 0>(dtw, P, m->opt_rpw_ffn, m->stream);
 }
 
+// dense W2 over t1.  partial: the un-merged product goes there; else xnext = W2 t1 (+ bias) + a (+ residual2, the layer input of
+// parallel / shared-input models)
+void w2_params(ifa_model *m, int l, half_t *xnext, half_t *partial, const half_t *residual2, DecGemvParams &P)
+{
+    Layer &L = m->layers[(size_t)l];
+    memset(&P, 0, sizeof(P));
+    P.x = m->t1; P.cols = (int)L.t[T_W2].cols; P.nblk = P.cols / 32; P.eps = m->cfg.eps;
+    P.W0[0] = wbytes(L.t[T_W2]); P.rows[0] = (int)L.t[T_W2].rows; P.nsets = 1;
+    if (partial) { P.y[0] = partial; return; }
+    P.b0[0] = (const half_t *)L.t[T_W2_B].data;
+    P.y[0] = xnext; P.residual = m->a; P.residual2 = residual2;
+    if (scale_on(m->cfg.ffn_out_scale)) P.pre_scale = m->cfg.ffn_out_scale;                               // Scale(ff_out)
+    if (l + 1 == m->cfg.layers && scale_on(m->cfg.out_scale)) P.post_scale = m->cfg.out_scale;        // Scale(last layer's output)
+}
+
 int launch_w2(ifa_model *m, int l, half_t *xnext, half_t *partial, int moe_slot, bool moe_last,
                      const half_t *residual2, int moe_t1_slot)
 {
     Layer &L = m->layers[(size_t)l];
-    DecGemvParams P; memset(&P, 0, sizeof(P));
+    DecGemvParams P;
     if (moe_slot >= 0) {
+        memset(&P, 0, sizeof(P));
         const Tensor &e2 = L.experts[1];
         moe_params(m, L, P, moe_slot, 2);
         P.x = m->t1 + (size_t)moe_t1_slot * e2.cols; P.cols = (int)e2.cols; P.eps = m->cfg.eps;      // (the gated product of this slot)
@@ -536,18 +499,9 @@ int launch_w2(ifa_model *m, int l, half_t *xnext, half_t *partial, int moe_slot,
         if (moe_last) return launch_dec_gemv<EPI_MOE_LAST, 0>(e2.dtype, P, m->opt_rpw_w2, m->stream);
         return launch_dec_gemv<EPI_MOE_ACC, 0>(e2.dtype, P, m->opt_rpw_w2, m->stream);
     }
-    P.x = m->t1; P.cols = (int)L.t[T_W2].cols; P.nblk = P.cols / 32; P.eps = m->cfg.eps;
-    P.W0[0] = wbytes(L.t[T_W2]); P.rows[0] = (int)L.t[T_W2].rows; P.nsets = 1;
+    w2_params(m, l, xnext, partial, residual2, P);
     const int dt2 = native_fmt(m, L.t[T_W2], P.W0[0]);
-    if (partial) {
-        P.y[0] = partial;
-        return launch_dec_gemv<EPI_PLAIN, 0>(dt2, P, m->opt_rpw_w2, m->stream);
-    }
-    P.b0[0] = (const half_t *)L.t[T_W2_B].data;
-    P.y[0] = xnext; P.residual = m->a; P.residual2 = residual2;     // + layer input for parallel / shared-input models
-    if (scale_on(m->cfg.ffn_out_scale)) P.pre_scale = m->cfg.ffn_out_scale;                               // Scale(ff_out)
-    if (l + 1 == m->cfg.layers && scale_on(m->cfg.out_scale)) P.post_scale = m->cfg.out_scale;        // Scale(last layer's output)
-    return launch_dec_gemv<EPI_RESIDUAL, 0>(dt2, P, m->opt_rpw_w2, m->stream);
+    return partial ? launch_dec_gemv<EPI_PLAIN, 0>(dt2, P, m->opt_rpw_w2, m->stream) : launch_dec_gemv<EPI_RESIDUAL, 0>(dt2, P, m->opt_rpw_w2, m->stream);
 }
 
 // [Wo ->] W1 | W3 -> W2 of layer l as ONE launch (ifa_decode_chain.h); x = the layer input (Wo's residual), xnext = the layer output
@@ -555,25 +509,11 @@ int launch_chain(ifa_model *m, int l, const half_t *x, half_t *xnext, unsigned t
 {
     const ifa_model_config &c = m->cfg;
     Layer &L = m->layers[(size_t)l];
-    const bool wo = m->ch_on == 2;
-    DecGemvParams PW; memset(&PW, 0, sizeof(PW));       // launch_wo's EPI_RESIDUAL / NORM 2 parameters
-    if (wo) {
-        PW.x = reinterpret_cast<const half_t *>(m->attq.get()); PW.cols = (int)L.t[T_WO].cols; PW.eps = c.eps;
-        PW.W0[0] = wbytes(L.t[T_WO]); PW.rows[0] = (int)L.t[T_WO].rows;
-        PW.b0[0] = (const half_t *)L.t[T_WO_B].data; PW.y[0] = m->a; PW.residual = x;
-        if (scale_on(c.attn_out_scale)) PW.pre_scale = c.attn_out_scale;
-    }
-    DecGemvParams P; memset(&P, 0, sizeof(P));          // launch_ffn13's dense EPI_GLU, NORM 1 parameters
-    P.x = m->a; P.norm_w = (const half_t *)L.t[T_FFN_NORM].data; P.norm_b = (const half_t *)L.t[T_FFN_NORM_B].data;
-    P.eps = c.eps; P.cols = c.dim; P.act_kind = c.act_kind; P.multi_base = c.ffn_norm_base;
-    P.W0[0] = wbytes(L.t[T_W1]); P.b0[0] = (const half_t *)L.t[T_W1_B].data; P.y[0] = m->t1; P.rows[0] = (int)L.t[T_W1].rows;
-    P.W1 = wbytes(L.t[T_W3]); P.b1 = (const half_t *)L.t[T_W3_B].data;
-    DecGemvParams Q; memset(&Q, 0, sizeof(Q));          // launch_w2's EPI_RESIDUAL parameters
-    Q.x = m->t1; Q.cols = (int)L.t[T_W2].cols; Q.eps = c.eps;
-    Q.W0[0] = wbytes(L.t[T_W2]); Q.rows[0] = (int)L.t[T_W2].rows; Q.b0[0] = (const half_t *)L.t[T_W2_B].data;
-    Q.y[0] = xnext; Q.residual = m->a;
-    if (scale_on(c.ffn_out_scale)) Q.pre_scale = c.ffn_out_scale;
-    if (l + 1 == c.layers && scale_on(c.out_scale)) Q.post_scale = c.out_scale;
+    const bool wo = m->route.chain == 2;
+    DecGemvParams PW, P, Q;       // the single launches' EPI_RESIDUAL / NORM 2, EPI_GLU / NORM 1 and EPI_RESIDUAL parameters
+    if (wo) { wo_params(m, l, x, nullptr, PW); PW.x = reinterpret_cast<const half_t *>(m->attq.get()); }
+    ffn13_params(m, l, P);
+    w2_params(m, l, xnext, nullptr, nullptr, Q);
     DecChainExtra E; memset(&E, 0, sizeof(E));
     const size_t per = (size_t)c.dim + L.t[T_W1].rows;
     E.gran_a = m->ch_gran + (size_t)l * per; E.gran_h = E.gran_a + c.dim;
@@ -679,14 +619,14 @@ int enqueue_fused_step(ifa_model *m, int tail)
     const int l_first = std::min(std::max(m->opt_debug_layer0, 0), c.layers - 1);
     const int n_layers = (m->opt_debug_layers > 0 && l_first + m->opt_debug_layers < c.layers) ? l_first + m->opt_debug_layers : c.layers;
     for (int l = l_first; l < n_layers; l++) {
-        if (m->qa_on) {
+        if (m->route.kind == DEC_ROUTE_FUSED_TAIL) {
             if ((rc = launch_qkv_attn(m, l, x))) return rc;
         } else {
             if ((rc = launch_qkv(m, l, x))) return rc;
             if ((rc = launch_attn(m, l))) return rc;
         }
-        if (m->ch_on) {      // [Wo ->] W1 | W3 -> W2 as one launch
-            if (m->ch_on == 1 && (rc = launch_wo(m, l, x))) return rc;
+        if (m->route.chain) {      // [Wo ->] W1 | W3 -> W2 as one launch
+            if (m->route.chain == 1 && (rc = launch_wo(m, l, x))) return rc;
             if ((rc = launch_chain(m, l, x, xnext))) return rc;
             std::swap(x, xnext);
             continue;
@@ -755,6 +695,23 @@ static int qa_err_check(ifa_model *m, int qerr)
                     "the results of this call are not valid -- repeat it: options fuse_attn / fuse_ffn are off now (five-launch step)", (unsigned)qerr);
 }
 
+// n greedy steps in a row as one captured, instantiated graph (replaces *graph)
+static int capture_steps(ifa_model *m, int n, hipGraph_t *graph, hipGraphExec_t *exec)
+{
+    int rc = IFA_OK;
+    IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
+    IFA_HIP_CHECK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
+    for (int i = 0; i < n && !rc; i++) rc = enqueue_fused_step(m);
+    hipGraph_t gph = nullptr;
+    hipError_t e = hipStreamEndCapture(m->stream, &gph);
+    if (rc) { if (gph) (void)hipGraphDestroy(gph); return rc; }
+    if (e != hipSuccess) return ifa_fail(IFA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+    if (*graph) (void)hipGraphDestroy(*graph);
+    *graph = gph;
+    IFA_HIP_CHECK(hipGraphInstantiate(exec, gph, nullptr, nullptr, 0));
+    return IFA_OK;
+}
+
 // sc: the call draws its tokens on the device (ifa_model_decode_sampled, which has checked that the fused graph route is open)
 int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms, bool prepare_only,
                 const SampledCall *sc)
@@ -766,26 +723,15 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     IFA_REQUIRE(m->g[T_EMBD].present() && m->g[T_LM_HEAD].present(), "ifa_model_decode: embeddings / lm_head missing (pipeline stage worker)");
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
     std::string why;
-    if (m->opt_exact_order) {      // order-exact steps, host-driven (a failure is an error, never a silent change of arithmetic)
+    // host-driven steps, same semantics: order-exact (a failure is an error, never a silent change of arithmetic), or the op-by-op
+    // fallback (also the path of option perf_stat: one launch per reference op to time)
+    const bool exact = m->opt_exact_order != 0;
+    if (exact || !m->opt_fused || m->opt_perf_stat || !fused_supported(m, &why)) {
         if (prepare_only) return IFA_OK;
         int tok = first_token;
         for (int i = 0; i < n_steps; i++) {
             int nt = 0;
-            int rc = forward_exact(m, tok, start_pos + i, nullptr, &nt);
-            if (rc) return rc;
-            if (out_tokens_host) out_tokens_host[i] = nt;
-            tok = nt;
-        }
-        if (elapsed_ms) *elapsed_ms = -1.0f;
-        return IFA_OK;
-    }
-    if (!m->opt_fused || m->opt_perf_stat || !fused_supported(m, &why)) {
-        // op-by-op fallback: same semantics, host-driven (also the path of option perf_stat: one launch per reference op to time)
-        if (prepare_only) return IFA_OK;
-        int tok = first_token;
-        for (int i = 0; i < n_steps; i++) {
-            int nt = 0;
-            int rc = forward_ops(m, &tok, 1, start_pos + i, nullptr, &nt);
+            int rc = exact ? forward_exact(m, tok, start_pos + i, nullptr, &nt) : forward_ops(m, &tok, 1, start_pos + i, nullptr, &nt);
             if (rc) return rc;
             if (out_tokens_host) out_tokens_host[i] = nt;
             tok = nt;
@@ -802,14 +748,13 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     if (rc) return rc;
     if (m->opt_q3h_native && (rc = ensure_q3hn(m))) return rc;
     hipStream_t s = m->stream;
-    // attention variant of this call: one workgroup per head, or keys split over workgroups once the context the
-    // call reaches passes the threshold (the captured step is re-captured when the variant changes)
-    choose_attn_split(m, start_pos + n_steps);
-    if ((rc = qkv_attn_ready(m))) return rc;
+    // the attention route of this call (the captured step is re-captured when it changes)
+    if ((rc = decode_route_ready(m, start_pos + n_steps))) return rc;
+    const bool waits_on = m->route.kind == DEC_ROUTE_FUSED_TAIL || m->route.chain;      // launches with granule tags and an error word
     if ((rc = step_tail_ready(m))) return rc;
     m->host_pinned[0] = first_token; m->host_pinned[1] = start_pos; m->host_pinned[2] = 0;
     IFA_HIP_CHECK(hipMemcpyAsync(m->state, m->host_pinned, 3 * sizeof(int), hipMemcpyHostToDevice, s));
-    if (m->qa_on || m->ch_on) {      // the granule tags of this call: (call counter, position) -- consecutive steps never share one
+    if (waits_on) {      // the granule tags of this call: (call counter, position) -- consecutive steps never share one
         m->qa_calls = (m->qa_calls % 4000u) + 1u;
         m->host_pinned[6] = (int)m->qa_calls;
         IFA_HIP_CHECK(hipMemcpyAsync(m->qa_call, m->host_pinned + 6, sizeof(int), hipMemcpyHostToDevice, s));
@@ -820,31 +765,13 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
         if (m->opt_graph && (rc = sampled_graph(m, &samp_exec))) return rc;
         if ((rc = sampled_begin(m, *sc))) return rc;
     }
-    if (!sc && m->opt_graph && !m->graph_exec) {
-        IFA_HIP_CHECK(hipStreamSynchronize(s));
-        IFA_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_fused_step(m);
-        hipGraph_t gph = nullptr;
-        hipError_t e = hipStreamEndCapture(s, &gph);
-        if (rc) { if (gph) (void)hipGraphDestroy(gph); return rc; }
-        if (e != hipSuccess) return ifa_fail(IFA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-        if (m->graph) (void)hipGraphDestroy(m->graph);
-        m->graph = gph;
-        IFA_HIP_CHECK(hipGraphInstantiate(&m->graph_exec, m->graph, nullptr, nullptr, 0));
-    }
+    if (!sc && m->opt_graph && !m->graph_exec && (rc = capture_steps(m, 1, &m->graph, &m->graph_exec))) return rc;
     const int S = m->opt_graph_steps;
     if (!sc && m->opt_graph && S > 1 && n_steps >= S && (!m->graph_exec_n || m->graph_n_steps != S)) {
         if (m->graph_exec_n) { (void)hipGraphExecDestroy(m->graph_exec_n); m->graph_exec_n = nullptr; }
         if (m->graph_n) { (void)hipGraphDestroy(m->graph_n); m->graph_n = nullptr; }
-        IFA_HIP_CHECK(hipStreamSynchronize(s));
-        IFA_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        for (int i = 0; i < S && !rc; i++) rc = enqueue_fused_step(m);
-        hipGraph_t gph = nullptr;
-        hipError_t e = hipStreamEndCapture(s, &gph);
-        if (rc) { if (gph) (void)hipGraphDestroy(gph); return rc; }
-        if (e != hipSuccess) return ifa_fail(IFA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-        m->graph_n = gph; m->graph_n_steps = S;
-        IFA_HIP_CHECK(hipGraphInstantiate(&m->graph_exec_n, m->graph_n, nullptr, nullptr, 0));
+        if ((rc = capture_steps(m, S, &m->graph_n, &m->graph_exec_n))) return rc;
+        m->graph_n_steps = S;
     }
     if (prepare_only) return IFA_OK;
     th("state copies enqueued");
@@ -871,7 +798,7 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned + 8, m->state + 8, sizeof(int) * (size_t)n_steps, hipMemcpyDeviceToHost, s));
     int *qerr = m->host_pinned + 8 + ifa_model::RING;
     qerr[0] = 0;
-    if (m->qa_on || m->ch_on) IFA_HIP_CHECK(hipMemcpyAsync(qerr, m->qa_err, 4, hipMemcpyDeviceToHost, s));
+    if (waits_on) IFA_HIP_CHECK(hipMemcpyAsync(qerr, m->qa_err, 4, hipMemcpyDeviceToHost, s));
     th("copies back enqueued");
     IFA_HIP_CHECK(hipStreamSynchronize(s));
     th("stream synchronised");
@@ -911,11 +838,9 @@ int ifa_model_time_kernel(ifa_model *m, int which, int iters, float *avg_us)
             k_touch<<<dim3(8), dim3(256), 0, s>>>((const uint8_t *)t.tiled, bytes, (size_t)m->opt_touch_stride, m->state + 7);
         }
     };
-    if (which == 7 || which == 9) {      // QKV + attention as one launch; the chained FFN launch
-        if ((rc = qkv_attn_ready(m))) return rc;
-        if (which == 9 && !m->ch_on) return ifa_fail(IFA_ERR_STATE, "chained FFN launch unavailable for this model / option set");
-        if (which == 7 && !m->qa_on) return ifa_fail(IFA_ERR_STATE, "fused QKV + attention launch unavailable for this model / option set");
-    }
+    if ((rc = decode_route_ready(m, m->route_reach))) return rc;      // the last call's reach under the options of now
+    if (which == 9 && !m->route.chain) return ifa_fail(IFA_ERR_STATE, "chained FFN launch unavailable for this model / option set");
+    if (which == 7 && m->route.kind != DEC_ROUTE_FUSED_TAIL) return ifa_fail(IFA_ERR_STATE, "fused QKV + attention launch unavailable for this model / option set");
     auto one = [&](int i) -> int {
         if (which == 7) return launch_qkv_attn(m, i % m->cfg.layers, m->x, (unsigned)(i + 1));
         if (which == 9) return launch_chain(m, i % m->cfg.layers, m->x, m->x2, (unsigned)(i + 1));
@@ -930,9 +855,7 @@ int ifa_model_time_kernel(ifa_model *m, int which, int iters, float *avg_us)
         default: return launch_lm(m, m->x);
         }
     };
-    k_dec_gather<<<dim3(2), dim3(256), 0, s>>>((const half_t *)m->g[T_EMBD].data, m->state, m->cfg.dim, (int)m->g[T_EMBD].rows, m->x,
-                                               m->cfg.rope_order ? m->rope_tab : nullptr, m->cfg.head_dim, m->cfg.rope_theta,
-                                               (int)(m->cfg.head_dim * m->cfg.partial_rotary + 0.5f), m->cfg.embd_scale);
+    if ((rc = launch_gather(m))) return rc;
     for (int i = 0; i < 3; i++) if ((rc = one(i))) return rc;
     if (m->opt_trace) {
         if (!m->trace && (rc = m->trace.alloc(2048 * 8))) return rc;

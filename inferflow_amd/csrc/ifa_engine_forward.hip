@@ -523,31 +523,17 @@ int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext
     // K / V rows of all of them go to the cache in a launch of their own first, and the attention kernel leaves the cache alone
     if (draft && (rc = draft_kv_store_launch(m, n, m->bqkv + QD, m->bqkv + QD + KVD, (int)(QD + 2 * KVD), rows_l))) return rc;
     {
-        const int rope_dims = (int)(c.head_dim * c.partial_rotary + 0.5f);
-        DecAttnParams A; memset(&A, 0, sizeof(A));
-        A.q = m->bqkv; A.k_new = m->bqkv + QD; A.v_new = A.k_new + KVD;
-        A.state = m->state; A.rope_tab = m->brope; A.heads = c.heads; A.kv_heads = c.kv_heads;
-        A.kv_q8 = c.kv_dtype == Q8_B32T2; A.kq_scale = c.use_alibi ? 1.0f : c.kq_scale;
-        A.rope_order = c.rope_order; A.rope_cols = rope_dims;
-        A.alibi = c.use_alibi; A.alibi_base = c.tp_rank * c.heads; A.alibi_total = c.heads * std::max(1, c.tp_size);
-        A.out = m->att; A.max_ctx = c.max_ctx; A.batch_rows = rows_l; A.q_stride = (int)(QD + 2 * KVD);
-        A.skip_store = draft ? 1 : 0;
+        DecAttnParams A; attn_params(m, l, A);      // the batch-1 step's; per row: q | k | v, positions and caches (rows_l), no quantised image
+        A.q = m->bqkv; A.k_new = m->bqkv + QD; A.v_new = A.k_new + KVD; A.kcache = nullptr; A.vcache = nullptr;
+        A.rope_tab = m->brope; A.batch_rows = rows_l; A.q_stride = (int)(QD + 2 * KVD);
+        A.skip_store = draft ? 1 : 0; A.xq = nullptr; A.trace = nullptr;
         const size_t asmem = dec_attn_smem(c.head_dim, c.max_ctx);
         const dim3 grid((unsigned)c.heads, (unsigned)n), block(256);
-#define IFA_BATTN(HDV, Q8V) { auto kern = k_dec_attn<HDV, Q8V, true>; \
-        if (asmem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)asmem)); \
-        kern<<<grid, block, asmem, m->stream>>>(A.q, nullptr, nullptr, A.heads, A.kv_heads, A); }
-        switch (c.head_dim) {
-        case 32: if (A.kv_q8) IFA_BATTN(32, true) else IFA_BATTN(32, false) break;
-        case 64: if (A.kv_q8) IFA_BATTN(64, true) else IFA_BATTN(64, false) break;
-        case 96: if (A.kv_q8) IFA_BATTN(96, true) else IFA_BATTN(96, false) break;
-        case 128: if (A.kv_q8) IFA_BATTN(128, true) else IFA_BATTN(128, false) break;
-        case 48: IFA_BATTN(48, false) break;
-        case 80: IFA_BATTN(80, false) break;
-        default: return ifa_fail(IFA_ERR_ARG, "fused batched attention: head_dim %d", c.head_dim);
-        }
-#undef IFA_BATTN
-        IFA_LAUNCH_CHECK();
+        rc = attn_dispatch(c.head_dim, A.kv_q8 != 0, [&](auto hd, auto q8) {
+            return launch_lds(k_dec_attn<decltype(hd)::value, decltype(q8)::value, true>, grid, block, asmem, m->stream,
+                              A.q, nullptr, nullptr, A.heads, A.kv_heads, A);
+        });
+        if (rc) return rc;
     }
     // 3. wo (+ bias) + residual
     clear();

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "ifa_host.h"
 #include "ifa_buf_hip.h"
@@ -129,18 +130,21 @@ struct ifa_model : Scratch {
     std::map<int, hipGraphExec_t> batch_graphs;      // captured batched step per batch size (dense models)
     std::map<int, hipGraphExec_t> draft_graphs;      // captured draft step (ifa_model_decode_draft: n rows of ONE slot) per row count
     // long-context decode attention (keys split over workgroups): workspace, switch and the context it starts at
-    DecAttnSplitWs attn_ws = {nullptr, nullptr, nullptr, 8};      // (what the kernels take: filled from the three owners below)
+    DecAttnSplitWs attn_ws = {nullptr, nullptr, nullptr, 8};      // (what the kernels take: filled from the three owners below; nsplits per launch from the route)
     DevBuf<half_t> attn_ws_S; DevBuf<float> attn_ws_lmax, attn_ws_opart;
     int opt_attn_unload = 1;       // 1 (default): in the 256-row bucket the heads' workgroups of the fused QKV + attention launch take no weight rows (UL kernels)
     int opt_attn_nsplits = 0;      // > 0: splits per head whatever the context (measurement)
+    // What the decode step of the last planned call runs (ifa_decode_route.h: the attention launch, its kernel instance, the chained
+    // FFN launch) and the reach it was planned for; the captured steps hold it (decode_route_ready)
+    DecRoute route; int route_reach = 256;
     // attention as the tail of the QKV launch (ifa_decode_qkv_attn.h): granules [layers][(heads + 2 kv_heads) * head_dim], the
     // decode-call counter the tags are built from, its own error word
-    int opt_fuse_attn = 1, opt_fuse_attn_timeout_us = 20000, qa_on = 0, qa_gk = 0;
+    int opt_fuse_attn = 1, opt_fuse_attn_timeout_us = 20000;
     DevBuf<unsigned long long> qa_gran;
     DevBuf<unsigned> qa_call, qa_err; unsigned qa_calls = 0;
     // consecutive GEMV ops of a layer as ONE launch with the next op's rows requested before the hand-off (ifa_decode_chain.h):
-    // option fuse_ffn = 1: W1 | W3 -> W2; 2: Wo -> W1 | W3 -> W2.  ch_on = what the captured step uses.  Granules [layers][dim + ffn].
-    int opt_fuse_ffn = 0, ch_on = 0, opt_chain_late_w2 = 0;
+    // option fuse_ffn = 1: W1 | W3 -> W2; 2: Wo -> W1 | W3 -> W2 (route.chain = what the captured step uses).  Granules [layers][dim + ffn].
+    int opt_fuse_ffn = 0, opt_chain_late_w2 = 0;
     int opt_q3h_native = 0;          // Q3H_B64T1 linears of the dense FFN and Wo streamed at 32 instead of 36 bytes per block (A / B: profiles/r06_q3h_native_ab.log)
     // Per-phase times in the reference's key space (InferencePerfStat, GpuInferenceWorker::UpdatePerfStat, inference_worker.cc:2670-2697:
     // (layer + 1) * 10000 + phase, the whole layer under + 0 for layers 0..5, the phases of layer 0 -- layer_idx_for_study_ -- under
@@ -160,8 +164,8 @@ struct ifa_model : Scratch {
     // st_on = what the captured step uses (F16 lm_head with the RMS / no final norm)
     int opt_step_tail = 1, st_on = 0;
     DevBuf<unsigned long long> st_keys; DevBuf<unsigned> st_counter;      // (st_keys.cap(): the lm_head grid the keys serve)
-    int attn_pb = 256, opt_attn_kt = 1;      // cache rows the one-workgroup decode attention requests at entry (64 / 128 / 256: the bucket the call stays inside); K rows through the LDS tile
-    int attn_split = 0, opt_attn_split_ctx = -1, opt_batch_graph = 0, opt_gemm_rows = 1, opt_batch_fused = 1, opt_moe_router_fused = 1, opt_prefill_big = 1, opt_rows_mo = 1, opt_moe_singles = 1;
+    int opt_attn_kt = 1;      // K rows of the one-workgroup decode attention through the LDS tile
+    int opt_attn_split_ctx = -1, opt_batch_graph = 0, opt_gemm_rows = 1, opt_batch_fused = 1, opt_moe_router_fused = 1, opt_prefill_big = 1, opt_rows_mo = 1, opt_moe_singles = 1;
     // independent KV caches ("query slots", one per concurrent query like the reference's per-query
     // LayerKVCache sets): the inactive ones park their cache pointers and captured graph here
     struct KvSlot { std::vector<DevBuf<void>> k, v; hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; };
@@ -275,8 +279,6 @@ static inline bool scale_on(float s) { return s < 0.9999f || s > 1.0001f; }     
 static inline bool same_fmt(int a, int b) { return a == b || (is_q4(a) && is_q4(b)); }
 
 
-static constexpr size_t IFA_LDS_LIMIT = 160 * 1024;      // LDS per workgroup on gfx950 (MI355X_MICROARCH.md)
-
 static inline int num_cus() { return dec_num_cus(); }
 
 
@@ -339,6 +341,33 @@ static inline int rows_mo(const ifa_model *m, const Tensor &t) { return m->opt_r
 
 namespace ifae {
 
+// "raise the dynamic-LDS attribute when over 48 KiB, then launch"
+template <class K, class... Args>
+static int launch_lds(K kern, dim3 grid, dim3 block, size_t smem, hipStream_t s, Args... args)
+{
+    if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    kern<<<grid, block, smem, s>>>(args...);
+    IFA_LAUNCH_CHECK();
+    return IFA_OK;
+}
+
+// f(head_dim constant, Q8-cache constant) over the pairs the attention kernels exist for: 32 / 64 / 96 / 128 with an F16 or a Q8 cache,
+// 48 / 80 (no whole Q8 blocks) with an F16 cache only
+template <class F>
+static int attn_dispatch(int head_dim, bool q8, F &&f)
+{
+    using std::integral_constant;
+    switch (head_dim) {
+    case 32: return q8 ? f(integral_constant<int, 32>{}, std::true_type{}) : f(integral_constant<int, 32>{}, std::false_type{});
+    case 64: return q8 ? f(integral_constant<int, 64>{}, std::true_type{}) : f(integral_constant<int, 64>{}, std::false_type{});
+    case 96: return q8 ? f(integral_constant<int, 96>{}, std::true_type{}) : f(integral_constant<int, 96>{}, std::false_type{});
+    case 128: return q8 ? f(integral_constant<int, 128>{}, std::true_type{}) : f(integral_constant<int, 128>{}, std::false_type{});
+    case 48: if (!q8) return f(integral_constant<int, 48>{}, std::false_type{}); break;
+    case 80: if (!q8) return f(integral_constant<int, 80>{}, std::false_type{}); break;
+    }
+    return ifa_fail(IFA_ERR_ARG, "fused attention: head_dim %d with %s cache", head_dim, q8 ? "a Q8" : "an F16");
+}
+
 // ---- ifa_engine.hip
 void drop_graphs(ifa_model *m);
 // perf_stat spans (ifa_engine.hip): no-ops unless the option is on.  PerfSpan brackets a phase on the model's stream.
@@ -360,16 +389,14 @@ int ensure_x32(ifa_model *m);
 int ensure_q3hn(ifa_model *m);
 int ensure_scratch(ifa_model *m, int T);
 // ---- ifa_engine_decode.hip
-void choose_attn_split(ifa_model *m, int reach);
 bool fused_ok(const Tensor &t, bool long_rows);
 int lmhead_grid(const DecLmHeadParams &P, int wgs_per_cu_opt);
 int launch_lmhead(const DecLmHeadParams &P, int norm, int wgs_per_cu_opt, hipStream_t s, const DecStepTail *Z = nullptr);
 bool has_post_norms(const ifa_model *m);
 bool fused_supported(const ifa_model *m, std::string *why);
 int sep_norm(ifa_model *m, const half_t *x, const Tensor &w, const Tensor &b, half_t *dst);
-void attn_params(ifa_model *m, int l, DecAttnParams &A);
-bool qkv_attn_layer_ok(const ifa_model *m, int l, int *gk_out);
-int qkv_attn_ready(ifa_model *m);
+void attn_params(ifa_model *m, int l, DecAttnParams &A);      // (the batch-1 step's; batch_fused_layer overrides the per-row fields)
+int decode_route_ready(ifa_model *m, int reach, bool own_launches = false);
 void qkv_params(ifa_model *m, int l, const half_t *x, DecGemvParams &P);
 int launch_qkv_attn(ifa_model *m, int l, const half_t *x, unsigned tag_add = 0);
 int launch_qkv(ifa_model *m, int l, const half_t *x);

@@ -453,7 +453,7 @@ int ifa_model_tp_decode(ifa_model *m, const ifa_tp_topology *topo, int first_tok
                 start_pos, start_pos + n_steps, m->cfg.max_ctx);
     const ifa_tp_topology &t = *topo;
     hipStream_t s = m->stream;
-    choose_attn_split(m, start_pos + n_steps);
+    if ((rc = decode_route_ready(m, start_pos + n_steps, true))) return rc;      // (split and bucket; this step's launches are its own)
     // the step counter restarts: the token ring of this call begins at state[8]
     m->host_pinned[0] = first_token; m->host_pinned[1] = start_pos; m->host_pinned[2] = 0;
     IFA_HIP_CHECK(hipMemcpyAsync(m->state, m->host_pinned, 3 * sizeof(int), hipMemcpyHostToDevice, s));

@@ -268,6 +268,18 @@ class DecodeWorker:
         check(lib().ifa_model_time_kernel(self._h, which, iters, C.byref(us)))
         return us.value
 
+    ROUTE_FIELDS = ("kind", "nsplits", "pb", "kt", "ul", "gk", "rw", "chain", "split_threshold", "split", "lds_attn", "lds_scores", "lds_pv",
+                    "error", "num_cus", "visible_cus", "waits")
+    ROUTE_KINDS = ("one_workgroup", "split", "fused_tail")
+
+    def decode_route(self):
+        """the plan of the last decode / decode_prepare call (csrc/ifa_decode_route.h) as a dict; kind as one of ROUTE_KINDS"""
+        out = (C.c_int * len(self.ROUTE_FIELDS))()
+        check(lib().ifa_model_decode_route(self._h, out, len(out)))
+        d = dict(zip(self.ROUTE_FIELDS, out))
+        d["kind"] = self.ROUTE_KINDS[d["kind"]]
+        return d
+
     def get_tensor_host(self, layer, tid):
         """(dtype, uint8/uint16 numpy copy, rows, cols) of a loaded tensor in reference layout, or None."""
         d, p, r, c = C.c_int(), C.c_void_p(), C.c_size_t(), C.c_size_t()

@@ -560,6 +560,7 @@ def check_attq(image, att_dev16, cols):
 # ----------------------------------------------------------------------------- the matrix both test files walk
 N_ONE_WG = (1, 2, 8, 9, 63, 64, 65, 127, 128, 129, 255, 256, 257, 264, 511, 512, 513, 640)          # one workgroup per head, and the fused launch
 N_SPLIT = (1, 2, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 255, 256, 257, 511, 512, 513, 700)             # keys split over workgroups
+N_LDS_SPLIT = (1, 9, 257, 700)                                                                        # the split the LDS forces (max_ctx 81920)
 N_ODD_HEADS = (65, 257)                                                                             # head_dim 80 / 96
 N_VARIANTS = (64, 65, 257)                                                                          # ALiBi / RoPE variants
 

@@ -2,8 +2,12 @@
 route the engine can choose, at the contexts where those routes change behaviour.
 
 Routes: k_dec_attn (one workgroup per head; entry buckets of 64 / 128 / 256 rows, direct loads past the bucket, K rows through the LDS
-tile or straight into registers), the same body as the tail of the fused QKV launch (attn_unload 0 / 1, with and without the chained
-FFN launch behind it), and k_dec_attn_scores / _pv / _combine with 8 / 16 / 32 splits, contexts shorter than the split count included.
+tile or straight into registers), the same body as the tail of the fused QKV launch (attn_unload 0 / 1; fuse_ffn 0 and its default,
+which is 0 too: the chained FFN launch is covered by tests/test_gpu_chain.py), and k_dec_attn_scores / _pv / _combine with 8 / 16 / 32
+splits, contexts shorter than the split count included, also where only the LDS forces the split (max_context_len 81920).
+Every walk asserts, at the first step of each context, the route the engine planned (ifa_model_decode_route: kind, entry bucket, K tile,
+unloaded heads, splits, chained launch) against the one its name claims: options alone do not prove which kernel ran (a CU mask,
+disabled waits or an LDS limit change it), and the failure message shows num_cus / visible_cus / waits.
 
 One case (tests/decode_attn_util.py has the reference, the inputs and the assertions):
   * a one-layer model; a throw-away step leaves the probe token's pre-RoPE q | k | v in "dqkv" (they depend on the token and the
@@ -45,8 +49,7 @@ every one of them by ONE ulp of its own size wherever the element is at least a 
 elements, where the two products nearly cancel, are held to one ulp at the pair's length instead: measured up to 36 of their own ulp
 there (128-wide, position 510) and never more than 0.125 at the pair's length.  Q8: 0 .. 3 codes per walk differ from the reference's, by one.
 
-Remaining gap: the batched attention (decode_batch / decode_draft: k_dec_attn<.., BATCH>) and the split that the LDS forces at very
-large max_context_len are not covered here."""
+Remaining gap: the batched attention (decode_batch / decode_draft: k_dec_attn<.., BATCH>) is not covered here."""
 import numpy as np
 import pytest
 
@@ -84,14 +87,33 @@ def _report(route, stats):
           % (route, len(stats), errs[len(errs) // 2], worst[0], worst[1], worst[2], worst[3]))
 
 
-def _walk(wk, geo, ns, stats, route):
-    """every case of every context in ns through one decode step; appends (err, family, n, needle) to stats"""
+def _bucket(reach):
+    return 64 if reach <= 64 else 128 if reach <= 128 else 256
+
+
+def _assert_route(wk, want, where):
+    got = wk.decode_route()
+    diff = {k: (got[k], v) for k, v in want.items() if got[k] != v}
+    assert not diff, "%s: planned route differs from the walk's, (got, want) = %s; the whole plan: %s (num_cus %d, visible_cus %d, waits %d)" % (
+        where, diff, got, got["num_cus"], got["visible_cus"], got["waits"])
+
+
+def _one_wg(geo, kt):
+    """the route of k_dec_attn alone at n keys: bucketed instances and the K tile on head_dim 32 / 64 / 128 only"""
+    pow2 = geo.head_dim in (32, 64, 128)
+    return lambda n: dict(kind="one_workgroup", pb=_bucket(n) if pow2 else 256, kt=int(bool(kt) and pow2 and geo.kv_dtype == F16), ul=0, nsplits=0, chain=0)
+
+
+def _walk(wk, geo, ns, stats, route, expect):
+    """every case of every context in ns through one decode step; appends (err, family, n, needle) to stats.  expect(n): the fields of
+    the planned route (Worker.decode_route) a step at n keys must show"""
     wk.decode(TOK, 0, 1)
+    _assert_route(wk, expect(1), (route, "first step"))
     dqkv_raw = wk.read_buffer("dqkv").copy()
     dqkv = dqkv_raw.view(np.float16)
     emits = geo.head_dim % 32 == 0 and wk.buffer("attq")[1] > 0
     rb = geo.row_bytes
-    failed, rows_seen, row_fig = [], set(), [0, 0, 0.0, 0.0]
+    failed, rows_seen, routes_seen, row_fig = [], set(), set(), [0, 0, 0.0, 0.0]
     for n in ns:
         p = n - 1
         for c in U.make_cases(dqkv, p, geo):
@@ -99,6 +121,9 @@ def _walk(wk, geo, ns, stats, route):
                 wk.write_buffer("kcache", c.k_rows[:p])
                 wk.write_buffer("vcache", c.v_rows[:p])
             wk.decode(TOK, p, 1)
+            if n not in routes_seen:         # (the route depends on the reach alone: asserted once per context)
+                routes_seen.add(n)
+                _assert_route(wk, expect(n), (route, n))
             att = wk.read_buffer("att").view(np.float16).copy()
             kc = wk.read_buffer("kcache", nbytes=n * rb).reshape(n, rb)
             vc = wk.read_buffer("vcache", nbytes=n * rb).reshape(n, rb)
@@ -144,7 +169,7 @@ def test_one_workgroup_per_head(name, kvd, kt):
         wk.set_option(k, v)
     ns = U.N_ONE_WG if name not in ("hd80", "hd96") else U.N_ODD_HEADS
     stats = []
-    _walk(wk, geo, ns, stats, "one-wg %s %s kt%d" % (name, KV_ID[kvd], kt))
+    _walk(wk, geo, ns, stats, "one-wg %s %s kt%d" % (name, KV_ID[kvd], kt), _one_wg(geo, kt))
     wk.close()
 
 
@@ -152,7 +177,7 @@ def test_one_workgroup_per_head(name, kvd, kt):
 @pytest.mark.parametrize("kvd", [F16, Q8], ids=["kvf16", "kvq8"])
 def test_fused_qkv_attention_launch(kvd, fuse_ffn):
     """the attention as the tail of the QKV launch (dim 4096, head_dim 128 only): the same contexts, both mappings of the heads'
-    workgroups past 128 keys (attn_unload), with and without the chained FFN launch behind it"""
+    workgroups past 128 keys (attn_unload), fuse_ffn 0 and left at its default (0: no chained FFN launch in either)"""
     wk, s, geo = _build("wide128", kvd, 640)
     wk.set_option("attn_split_ctx", 0)
     wk.set_option("fuse_attn", 1)
@@ -163,7 +188,9 @@ def test_fused_qkv_attention_launch(kvd, fuse_ffn):
         ns = U.N_ONE_WG if unload == 1 else tuple(n for n in U.N_ONE_WG if n > 128)
         route = "fused-qkv %s unload%d %s" % (KV_ID[kvd], unload, "ffn0" if fuse_ffn == 0 else "ffn-default")
         stats = []
-        _walk(wk, geo, ns, stats, route)
+        # (F16 rows through the K tile, attn_kt's default; unloaded heads in the 256-row bucket; 8 workgroups per kv group on 256 CUs)
+        _walk(wk, geo, ns, stats, route, lambda n: dict(kind="fused_tail", pb=_bucket(n), kt=int(kvd == F16), ul=int(unload == 1 and n > 128),
+                                                       nsplits=0, chain=0, rw=6))
         # the fused launch is really the one that ran: its timing entry point refuses models / option sets it does not take
         assert wk.time_kernel(7, 4) > 0.0
     wk.close()
@@ -175,13 +202,30 @@ SPLIT = [(name, kvd, nsp) for name in ("gqa64", "wide128") for kvd in (F16, Q8) 
 @pytest.mark.parametrize("name,kvd,nsplits", SPLIT, ids=["%s-%s-%dsplits" % (n, KV_ID[k], s) for n, k, s in SPLIT])
 def test_keys_split_over_workgroups(name, kvd, nsplits):
     """k_dec_attn_scores / _pv / _combine from two keys on (attn_split_ctx 1), contexts with fewer keys than splits included
-    (a one-key context has reach 1 and stays on the one-workgroup kernel: that is the route the engine takes)"""
+    (a one-key context has reach 1 and stays on one workgroup per head -- k_dec_attn, or on the 7B widths the tail of the fused QKV
+    launch: that is the route the engine takes)"""
     wk, s, geo = _build(name, kvd, 704)
     wk.set_option("attn_split_ctx", 1)
     wk.set_option("attn_nsplits", nsplits)
     route = "split %s %s x%d" % (name, KV_ID[kvd], nsplits)
     stats = []
-    _walk(wk, geo, U.N_SPLIT, stats, route)
+    one_key = dict(kind="fused_tail", pb=64, kt=int(kvd == F16), ul=0) if name == "wide128" else _one_wg(geo, 1)(1)
+    _walk(wk, geo, U.N_SPLIT, stats, route, lambda n: one_key if n == 1 else dict(kind="split", nsplits=nsplits, split=8, chain=0))
+    wk.close()
+
+
+@pytest.mark.parametrize("kvd", [F16, Q8], ids=["kvf16", "kvq8"])
+def test_split_forced_by_the_lds(kvd):
+    """max_context_len 81920 on the 64-wide heads: a head's score row (8656 + 2 x 81920 bytes) does not fit the 160 KiB LDS, so
+    k_dec_attn_scores / _pv / _combine run from position 0 on although the threshold never asks for them (attn_split_ctx 0: split = 0),
+    with 8 splits of 10240 keys (36928 bytes of LDS for the P.V launch).  The contexts are a subset of gqa64's, whose references
+    tests/test_decode_attn_ref_cpu.py holds to the same bounds."""
+    assert set(U.N_LDS_SPLIT) <= set(U.GEOMETRIES["gqa64"][3])
+    wk, s, geo = _build("gqa64", kvd, 81920)
+    wk.set_option("attn_split_ctx", 0)
+    stats = []
+    _walk(wk, geo, U.N_LDS_SPLIT, stats, "lds-split gqa64 %s" % KV_ID[kvd],
+          lambda n: dict(kind="split", nsplits=8, split=0, split_threshold=0, lds_pv=36928, error=0, chain=0))
     wk.close()
 
 
@@ -196,7 +240,7 @@ def test_alibi_and_rope_variants(name, kvd, split):
     wk.set_option("attn_split_ctx", 1 if split else 0)
     route = "%s %s %s" % (name, KV_ID[kvd], "split" if split else "one-wg")
     stats = []
-    _walk(wk, geo, U.N_VARIANTS, stats, route)
+    _walk(wk, geo, U.N_VARIANTS, stats, route, (lambda n: _one_wg(geo, 1)(1) if n == 1 else dict(kind="split", nsplits=8, split=8)) if split else _one_wg(geo, 1))
     wk.close()
 
 
@@ -223,11 +267,14 @@ def test_call_partitioning_is_bit_identical(name, kvd):
         wk.reset()
         tok = int(wk.forward(prompt[:p0], 0))
         whole = state(wk.decode(tok, p0, m)[0])
+        kind = "fused_tail" if name == "wide128" else "one_workgroup"      # (reach <= 270: under every split threshold)
+        _assert_route(wk, dict(kind=kind, pb=_bucket(p0 + m)), ("whole call", p0, m))
         wk.reset()
         assert int(wk.forward(prompt[:p0], 0)) == tok
         toks, t = [], tok
         for i in range(m):
             t = int(wk.decode(t, p0 + i, 1)[0][0])
+            _assert_route(wk, dict(kind=kind, pb=_bucket(p0 + i + 1)), ("single step", p0, i))
             toks.append(t)
         single = state(toks)
         assert whole[0] == single[0], ("tokens", p0, m)
