@@ -656,6 +656,23 @@ int ifa_decode_route_plan(const int *facts, int n_facts, int *out, int n_out);
  * visible_cus and waits (1: launches whose workgroups wait for each other are allowed) as the engine sees them now. */
 int ifa_model_decode_route(ifa_model *m, int *out, int n_out);
 
+/* The prompt and batched-step route plans (csrc/ifa_prompt_route.h, DESIGN.md "Prompt route plan"): which kernels the linears of a
+ * prompt's / a batched step's layers go through, from which copy of the weights, and what is built first.  Host-only, no GPU needed.
+ * Prompt: facts[19], in the order of PromptRouteFacts: T, exact_order, perf_stat, prefill_chunk, prefill_mid, prefill_mid_max,
+ * prefill_big, prefill_big_min, prefill_res_mid, rows_mo, gemm_rows, batch_fused, gemm_splitk, rows_kparts, topo, experts, rows_layers
+ * (0 no, 1 from MO copies only, 2 from the tiled layout too), big_layers, mid_shapes.  out[22], in the order of PromptRoute: kind (0 exact
+ * order, 1 op by op, 2 rows GEMM, 3 mid-length GEMM, 4 large tiles), first_pass, norm_fused, res_mid, then (kernel, src, mo, no_waits) of
+ * wq | wk | wv, wo, w1 / w3 and w2 (kernel 0 rows / 1 mid / 2 large tiles; src 0 tiled / 1 MO copy / 2 x32 copy or reference rows), need_mo
+ * (2: after the x32 copies), need_x32.
+ * Batched step: facts[13], in the order of BatchRouteFacts: n, exact_order, may_chunk, rows_mo, gemm_rows, batch_fused, rows_kparts,
+ * batch_graph, graph, topo, rows_layers, has_moe, logits_out.  out[9], in the order of BatchRoute: kind (0 exact order, 1 op by op,
+ * 2 fused), chunk, norm_fused, captured, (kernel, src, mo, no_waits) of every product, need_mo. */
+int ifa_prompt_route_plan(const int *facts, int n_facts, int *out, int n_out);
+int ifa_batch_route_plan(const int *facts, int n_facts, int *out, int n_out);
+/* The route of the model's last prompt call (ifa_model_forward and what runs through it), out[22] as above; a prompt of two passes
+ * shows first_pass 32 and the first pass's route.  Plans nothing, allocates nothing. */
+int ifa_model_prompt_route(ifa_model *m, int *out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -616,6 +616,34 @@ int ifa_model_decode_route(ifa_model *m, int *out, int n_out)
     return IFA_OK;
 }
 
+// the prompt and batched-step route plans (ifa_prompt_route.h) for tests: the pure functions, and what the model's last prompt call ran
+int ifa_prompt_route_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    IFA_REQUIRE(facts && out && n_facts == PROMPT_ROUTE_N_FACTS && n_out >= PROMPT_ROUTE_N_OUT, "ifa_prompt_route_plan: %d facts, %d outputs expected", PROMPT_ROUTE_N_FACTS, PROMPT_ROUTE_N_OUT);
+    PromptRouteFacts f;
+    memcpy(&f, facts, sizeof(f));
+    const PromptRoute r = plan_prompt_route(f);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
+int ifa_batch_route_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    IFA_REQUIRE(facts && out && n_facts == BATCH_ROUTE_N_FACTS && n_out >= BATCH_ROUTE_N_OUT, "ifa_batch_route_plan: %d facts, %d outputs expected", BATCH_ROUTE_N_FACTS, BATCH_ROUTE_N_OUT);
+    BatchRouteFacts f;
+    memcpy(&f, facts, sizeof(f));
+    const BatchRoute r = plan_batch_route(f);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
+int ifa_model_prompt_route(ifa_model *m, int *out, int n_out)
+{
+    IFA_REQUIRE(m && out && n_out >= PROMPT_ROUTE_N_OUT, "ifa_model_prompt_route: %d outputs expected", PROMPT_ROUTE_N_OUT);
+    memcpy(out, &m->prompt_route, sizeof(m->prompt_route));
+    return IFA_OK;
+}
+
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes)
 {
     IFA_REQUIRE(m && name && dptr, "ifa_model_get_buffer: null pointer");

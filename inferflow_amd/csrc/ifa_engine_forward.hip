@@ -162,31 +162,203 @@ int layer_tail_ops(ifa_model *m, int l, int T, half_t *&x, const half_t *attn_in
     return IFA_OK;
 }
 
-// no_head: a chunk of a longer prompt that is not its last one -- the layers only (KV cache rows written), no lm_head / argmax / sync
-// 33 .. prefill_mid_max tokens through k_gemm_mid (csrc/ifa_gemm_mid.hip): the large-tile route's conditions + an operand-order copy of
-// every linear (built here on first use).  From 33 tokens on: 5.3 ms for 33..48 tokens against 5.9-6.6 for two passes of the rows
-// GEMM (tools/short_prompt_routes.py, profiles/r06_prefill_mid_parts.log)
-bool prefill_mid_ok(ifa_model *m, int T, bool any_length)
+// ---- Route plans (ifa_prompt_route.h; rules P1 - P12 / B1 - B5 and the measurements behind their numbers: DESIGN.md, "Prompt route plan").
+// What the plans read of the model, from ONE walk over the seven linears of every layer (minus the FFN of mixture-of-experts layers,
+// which moe_ffn routes):
+//   rows_layers  the rows GEMM (ifa_gemm_rows_mfma.hip; the five launches of the batched step, the four of a prompt of 2..32 tokens): dense or
+//                device-routed layers with the sequential RMS wiring, every linear tiled Q4_B32T1 (2) or a 64-weight format with an MO copy (1)
+//   big_layers   the large-tile GEMM (ifa_gemm.hip, k_gemm_big): sequential wiring, every linear a 20-byte-block Q4 tensor or a 64-weight
+//                format through its Q4_B32T1A-layout copy (ensure_x32), wq / wk / wv of one format, dims in multiples of 64
+//   mid_shapes   k_gemm_mid (ifa_gemm_mid.hip) reads every linear's MO copy: the shapes ensure_mo builds one for, rows in 16s
+struct RouteModelFacts { int rows_layers = 0, big_layers = 0, mid_shapes = 1, has_moe = 0; };
+static RouteModelFacts route_model_facts(const ifa_model *m)
 {
     const ifa_model_config &c = m->cfg;
-    if (!m->opt_prefill_mid || !m->opt_rows_mo || T <= 32 || (!any_length && T > m->opt_prefill_mid_max) || c.experts != 0 || !prefill_big_ok(m)) return false;
-    if (ensure_mo(m) != IFA_OK) return false;
-    for (int l = 0; l < c.layers; l++) {
+    const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim, F = c.ffn;
+    const bool plain = !has_post_norms(m) && !c.parallel_attn && !c.share_input && !scale_on(c.attn_out_scale) && !scale_on(c.ffn_out_scale);
+    const bool hd_ok = c.head_dim == 32 || c.head_dim == 48 || c.head_dim == 64 || c.head_dim == 80 || c.head_dim == 96 || c.head_dim == 128;
+    RouteModelFacts r;
+    if (plain && gemm_rows_use_mfma() && c.norm_kind == 0 && !scale_on(c.out_scale) && !(D % 128 || QD % 128 || F % 128 || D > 4096 || KVD % 16) && hd_ok
+        && !(c.kv_dtype == Q8_B32T2 && c.head_dim % 32 != 0) && dec_attn_smem(c.head_dim, c.max_ctx) <= IFA_LDS_LIMIT) r.rows_layers = 2;
+    r.big_layers = plain && !(D % 64 || QD % 64 || F % 64);
+    for (const Layer &L : m->layers) {
+        const bool moe = c.experts > 0 && L.t[T_MOE_GATE].present();
+        r.has_moe |= moe;
         const int ids[] = {T_WQ, T_WK, T_WV, T_WO, T_W1, T_W3, T_W2};
-        for (int id : ids) { const Tensor &t = m->layers[(size_t)l].t[id]; if (!t.present() || !t.mo || t.cols % 128 != 0 || t.rows % 16 != 0) return false; }
+        for (int id : ids) {
+            const Tensor &t = L.t[id];
+            const bool mo_shape = t.present() && t.tiled && rows_mo_fmt(t.dtype) && t.cols % 128 == 0;      // (what ensure_mo builds a copy for)
+            if (!mo_shape || t.rows % 16 != 0) r.mid_shapes = 0;
+            if (moe && (id == T_W1 || id == T_W3 || id == T_W2)) continue;
+            if (!t.present() || !t.tiled) r.rows_layers = 0;
+            else if (!is_q4(t.dtype)) r.rows_layers = mo_shape ? std::min(r.rows_layers, 1) : 0;
+            const bool b64 = (t.dtype == Q4_B64T1 || t.dtype == Q3H_B64T1) && t.tiled;
+            if (!t.present() || (t.dtype != Q4_B32T1A && t.dtype != Q4_B32T1B && !b64)) r.big_layers = 0;
+        }
+        if (moe && !moe_device_ok(m, L)) r.rows_layers = 0;
+        if (!L.t[T_ATTN_NORM].present() || !L.t[T_FFN_NORM].present()) r.rows_layers = r.big_layers = 0;
+        if (L.t[T_ATTN_NORM_B].present() || L.t[T_FFN_NORM_B].present()) r.rows_layers = 0;
+        if (L.t[T_WK].dtype != L.t[T_WQ].dtype || L.t[T_WV].dtype != L.t[T_WQ].dtype || (!moe && L.t[T_W3].dtype != L.t[T_W1].dtype)) r.big_layers = 0;
     }
-    return true;
+    return r;
 }
 
-int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, bool no_head)
+static PromptRouteFacts prompt_facts(const ifa_model *m, int T, bool entry)
+{
+    PromptRouteFacts f;
+    f.T = T; f.exact_order = entry && m->opt_exact_order; f.perf_stat = m->opt_perf_stat != 0; f.prefill_chunk = entry && m->opt_prefill_chunk;
+    f.prefill_mid = m->opt_prefill_mid; f.prefill_mid_max = m->opt_prefill_mid_max; f.prefill_big = m->opt_prefill_big; f.prefill_big_min = m->opt_prefill_big_min;
+    f.prefill_res_mid = m->opt_prefill_res_mid; f.rows_mo = m->opt_rows_mo; f.gemm_rows = m->opt_gemm_rows; f.batch_fused = m->opt_batch_fused;
+    f.gemm_splitk = m->opt_gemm_splitk; f.rows_kparts = m->opt_rows_kparts;
+    f.topo = m->topo != nullptr; f.experts = m->cfg.experts;
+    if (T >= 2 && !f.topo && !f.exact_order) {      // (the walk only where its answer can matter)
+        const RouteModelFacts mf = route_model_facts(m);
+        f.rows_layers = mf.rows_layers; f.big_layers = mf.big_layers; f.mid_shapes = mf.mid_shapes;
+    }
+    return f;
+}
+
+// ensure_mo for a plan that needs the copies.  A failed build switches opt_rows_mo off (it is no error of the call): what was planned with
+// the copies in view -- up to 32 rows, the 64-weight formats, k_gemm_mid -- no longer holds, so the caller plans again
+static int route_mo_ready(ifa_model *m, bool &replan)
+{
+    const int had = m->opt_rows_mo;
+    const int rc = ensure_mo(m);
+    replan = rc == IFA_OK && had && !m->opt_rows_mo;
+    return rc;
+}
+
+// Plans a prompt of T tokens behind prefix_len (ifa_model::prompt_route) and builds the weight copies its launches read, in the plan's
+// order.  entry: the call is ifa_model_forward's, whose decisions -- exact order, two passes -- are planned too; a single pass
+// (forward_ops) plans without them.
+int prompt_route_ready(ifa_model *m, int T, int prefix_len, bool entry, PromptRoute &R)
+{
+    R = plan_prompt_route(prompt_facts(m, T, entry));
+    if (R.kind != PROMPT_EXACT && (T <= 0 || prefix_len < 0 || prefix_len + T > m->cfg.max_ctx))
+        return ifa_fail(IFA_ERR_ARG, "forward: %d tokens at prefix %d exceed max_ctx %d", T, prefix_len, m->cfg.max_ctx);
+    int rc;
+    bool replan = false;
+    if (R.need_mo == 1 && (rc = route_mo_ready(m, replan))) return rc;
+    if (replan) R = plan_prompt_route(prompt_facts(m, T, entry));
+    if (R.need_x32 && (rc = ensure_x32(m))) return rc;
+    if (R.need_mo == 2 && (rc = route_mo_ready(m, replan))) return rc;
+    if (replan) R = plan_prompt_route(prompt_facts(m, T, entry));
+    m->prompt_route = R;
+    return IFA_OK;
+}
+
+// ---- The four parameter blocks of a layer's linears on the fused routes: wq | wk | wv behind the attention norm, wo + residual, w1 / w3 + GLU
+// behind the FFN norm, w2 + residual.  The prompt routes (forward_ops) and the batched step (batch_fused_layer) differ in where q | k | v
+// and the layer's output go.
+static const uint8_t *gm_w(const Tensor &t, int src)
+{
+    return (const uint8_t *)(src == GM_W_MO ? t.mo.get() : src == GM_W_X32 ? (t.x32 ? t.x32.get() : t.data.get()) : t.tiled.get());
+}
+
+static GmArgs gm_args(const ifa_model *m, int T, const GmPlan &g, const Tensor &w, const Tensor &bias, const half_t *X, size_t K, half_t *Y, size_t N)
+{
+    GmArgs P;
+    memset(&P, 0, sizeof(P));
+    P.T = T; P.eps = m->cfg.eps; P.act_kind = m->cfg.act_kind; P.mo = g.mo; P.no_waits = g.no_waits;
+    P.W[0] = gm_w(w, g.src); P.rows[0] = (int)N; P.nsets = 1; P.nblk = (int)(K / 32);
+    P.X = X; P.ldx = (int)K; P.bias[0] = (const half_t *)bias.data.get();
+    P.Y = Y; P.ldy = (int)N;
+    return P;
+}
+
+// x: the layer's input, or -- the norm being a launch of its own -- its normalised rows; qkv: one [T][q | k | v] matrix, or null for m->q, m->k, m->v
+static GmArgs gm_qkv(const ifa_model *m, const Layer &L, int T, const GmPlan &g, bool norm_fused, const half_t *x, half_t *qkv)
 {
     const ifa_model_config &c = m->cfg;
-    if (T <= 0 || prefix_len < 0 || prefix_len + T > c.max_ctx)
-        return ifa_fail(IFA_ERR_ARG, "forward: %d tokens at prefix %d exceed max_ctx %d", T, prefix_len, c.max_ctx);
-    int rc = ensure_scratch(m, T);
-    if (rc) return rc;
+    const int QD = c.heads * c.head_dim, KVD = c.kv_heads * c.head_dim;
+    GmArgs P = gm_args(m, T, g, L.t[T_WQ], L.t[T_WQ_B], x, c.dim, qkv, QD);
+    P.W[1] = gm_w(L.t[T_WK], g.src); P.W[2] = gm_w(L.t[T_WV], g.src);
+    P.rows[0] = QD; P.rows[1] = KVD; P.rows[2] = KVD; P.nsets = 3;
+    if (norm_fused) { P.norm_w = (const half_t *)L.t[T_ATTN_NORM].data.get(); P.multi_base = c.attn_norm_base; }
+    P.bias[1] = (const half_t *)L.t[T_WK_B].data.get(); P.bias[2] = (const half_t *)L.t[T_WV_B].data.get();
+    P.ldy = qkv ? QD + 2 * KVD : 0;
+    if (!qkv) { P.Yset[0] = m->q; P.Yset[1] = m->k; P.Yset[2] = m->v; P.ldyset[0] = QD; P.ldyset[1] = KVD; P.ldyset[2] = KVD; }
+    return P;
+}
+
+static GmArgs gm_wo(const ifa_model *m, const Layer &L, int T, const GmPlan &g, const half_t *x)
+{
+    GmArgs P = gm_args(m, T, g, L.t[T_WO], L.t[T_WO_B], m->att, (size_t)m->cfg.heads * m->cfg.head_dim, m->a, m->cfg.dim);
+    P.res = x; P.ldres = m->cfg.dim;
+    return P;
+}
+
+static GmArgs gm_w13(const ifa_model *m, const Layer &L, int T, const GmPlan &g, bool norm_fused)
+{
+    GmArgs P = gm_args(m, T, g, L.t[T_W1], L.t[T_W1_B], norm_fused ? m->a : m->hn, m->cfg.dim, m->t1, m->cfg.ffn);
+    P.W1 = gm_w(L.t[T_W3], g.src); P.bias1 = (const half_t *)L.t[T_W3_B].data.get();
+    if (norm_fused) { P.norm_w = (const half_t *)L.t[T_FFN_NORM].data.get(); P.multi_base = m->cfg.ffn_norm_base; }
+    return P;
+}
+
+static GmArgs gm_w2(const ifa_model *m, const Layer &L, int T, const GmPlan &g, half_t *out)
+{
+    GmArgs P = gm_args(m, T, g, L.t[T_W2], L.t[T_W2_B], m->t1, m->cfg.ffn, out, m->cfg.dim);
+    P.res = m->a; P.ldres = m->cfg.dim;
+    return P;
+}
+
+// A product through the kernel of its plan.  own: the plan of the route's other products -- k_gemm_mid may decline wo / w2 of a Big route
+// (PromptRoute::res_mid), which the large tiles take then (with the no_waits of the plan that was tried, as ever)
+static int gm_launch(ifa_model *m, const Tensor &w, GmArgs &P, const GmPlan &g, const GmPlan &own, int epi, int norm)
+{
+    if (g.kernel == GM_K_ROWS) return gemm_rows_mfma_launch(P, epi, norm, m->stream);
+    if (g.kernel == GM_K_MID) {
+        if (gemm_mid_ok(w.dtype, P, epi)) return gemm_mid(P, epi, m->stream);
+        if (own.kernel == GM_K_MID) return ifa_fail(IFA_ERR_STATE, "mid-length GEMM declined a product of %zu x %zu", w.rows, w.cols);
+        P.W[0] = gm_w(w, own.src); P.mo = own.mo;
+    }
+    return gemm_big(w.x32 ? (int)Q4_B32T1A : w.dtype, P, epi, m->stream);
+}
+
+// RoPE of q and k, and the T new K / V rows into the cache behind prefix_len (one launch where the rope kernel stores F16 rows itself)
+static int rope_store_rows(ifa_model *m, Layer &L, int T, int prefix_len)
+{
+    const ifa_model_config &c = m->cfg;
     ifa_stream s = m->stream;
-    const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim;
+    const size_t KVD = (size_t)c.kv_heads * c.head_dim;
+    int rc;
+    uint8_t *kdst = (uint8_t *)L.kcache + (size_t)prefix_len * m->kv_row_bytes;
+    uint8_t *vdst = (uint8_t *)L.vcache + (size_t)prefix_len * m->kv_row_bytes;
+    const bool kv_f16 = c.kv_dtype != Q8_B32T2;
+    bool kv_stored = false;
+    if (c.rope_order != 0) {
+        rc = ifa_rope_qk_store(m->q, m->k, m->v, c.head_dim, c.heads, c.kv_heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary,
+                               kv_f16 ? kdst : nullptr, kv_f16 ? vdst : nullptr, m->kv_row_bytes / 2, s);
+        if (rc == IFA_OK) kv_stored = kv_f16;
+        else if (rc != IFA_ERR_STATE) return rc;
+        else {
+            if ((rc = ifa_rope(m->q, c.head_dim, c.heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary, s))) return rc;
+            if ((rc = ifa_rope(m->k, c.head_dim, c.kv_heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary, s))) return rc;
+        }
+    }
+    if (!kv_f16) {
+        if ((rc = ifa_quantize_act_q8(m->k, T, KVD, kdst, s))) return rc;
+        if ((rc = ifa_quantize_act_q8(m->v, T, KVD, vdst, s))) return rc;
+    } else if (!kv_stored) {
+        IFA_HIP_CHECK(hipMemcpyAsync(kdst, m->k, (size_t)T * m->kv_row_bytes, hipMemcpyDeviceToDevice, m->stream));
+        IFA_HIP_CHECK(hipMemcpyAsync(vdst, m->v, (size_t)T * m->kv_row_bytes, hipMemcpyDeviceToDevice, m->stream));
+    }
+    return IFA_OK;
+}
+
+// no_head: a chunk of a longer prompt that is not its last one -- the layers only (KV cache rows written), no lm_head / argmax / sync
+// planned: the route ifa_model_forward planned for this very pass (prompt_route_ready); without it the pass plans itself
+int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, bool no_head, const PromptRoute *planned)
+{
+    const ifa_model_config &c = m->cfg;
+    int rc;
+    PromptRoute R;
+    if (planned) R = *planned;
+    else if ((rc = prompt_route_ready(m, T, prefix_len, false, R))) return rc;
+    if ((rc = ensure_scratch(m, T))) return rc;
+    ifa_stream s = m->stream;
+    const size_t D = c.dim;
     const ifa_tp_topology *tp = m->topo;            // multi-GPU partition (ifa_model_tp_prefill): merges + stage hand-over
     const bool first_stage = !tp || tp->stage == 0, last_stage = !tp || tp->next_rank < 0 || tp->n_stages == 1;
     const bool merging = tp_merging(m);
@@ -207,105 +379,42 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
     // prompts every one of them is a fixed ~5 us)
     const bool seq_wiring = !c.parallel_attn && !c.share_input;
     bool xn_ready = false;           // m->xn already holds the next norm's output (fused into the previous layer's last Add)
-    // prompts of 2..16 tokens on a dense Q4 model with the sequential RMS wiring: the linears of a layer as FOUR launches of
-    // the rows GEMM (ifa_gemm_rows_mfma.hip) -- norm prologue + wq | wk | wv into q / k / v, wo + residual, norm + w1 / w3 +
-    // GLU, w2 + residual -- instead of seven products and four element-wise launches (9..16 tokens: the norms stay launches)
-    // Prompts above `prefill_big_min` tokens (47; round 4: 128) take the same four launches per layer from the large-tile GEMM (ifa_gemm.hip, k_gemm_big: the
-    // weights dequantised once per workgroup and step into LDS; reference-layout rows), norms as their own launches.
-    // the mid-length kernel (33 .. prefill_mid_max tokens): every linear of every layer a 4-bit tensor with its operand-order copy, dense FFN
+    // The fused routes (R: Rows, Mid, Big): the linears of a layer as FOUR launches -- (norm prologue +) wq | wk | wv into q / k / v, wo +
+    // residual, (norm +) w1 / w3 + GLU, w2 + residual -- instead of seven products and four element-wise launches.  Rows: the rows GEMM
+    // (ifa_gemm_rows_mfma.hip), up to 32 tokens.  Mid: k_gemm_mid on the operand-order copies, 33 .. prefill_mid_max tokens.  Big: the
+    // large-tile GEMM (ifa_gemm.hip, k_gemm_big: the weights dequantised once per workgroup and step into LDS; reference-layout rows); up
+    // to prefill_res_mid tokens it keeps wo and w2 (4096 output columns: 128 x 128 tiles whatever the kernel) on k_gemm_mid.
     const bool pstat = m->opt_perf_stat != 0;       // per-phase times: the op-by-op layer below (one launch per reference op), never the fused routes
-    const bool pf_mid = !tp && !pstat && prefill_mid_ok(m, T, false);
-    const bool pf_big = pf_mid || (!tp && !pstat && T > std::max(32, m->opt_prefill_big_min) && prefill_big_ok(m));
-    bool pf_fused = pf_big || (!tp && !pstat && T >= 2 && T <= 32 && batch_fused_ok(m, T) && c.experts == 0);
-    if (pf_fused && !pf_big) {
-        if ((rc = ensure_mo(m))) return rc;
-        pf_fused = batch_fused_ok(m, T);          // (ensure_mo may have switched the copies off: ask again, see forward_batch)
-    }
-    if (pf_big && !pf_mid && (rc = ensure_x32(m))) return rc;
-    // above prefill_mid_max: wo and w2 (4096 output columns: 128 x 128 tiles whatever the kernel) still through k_gemm_mid -- at 1024 tokens
-    // 41 / 102 us per launch against 51 / 143 for the split-K halves of the large-tile kernel, which keeps wq | wk | wv and the gated pair
-    // (profiles/r06_prefill_mid_parts.log section 13: 1024 / 1536 / 2048 tokens 4.5 / 3 / 0.8 % faster, 4096 tokens 4.7 % slower: up to 2048)
-    const bool pf_res_mid = pf_big && !pf_mid && !tp && T <= m->opt_prefill_res_mid && prefill_mid_ok(m, T, true);
-    for (int l = 0; l < c.layers && pf_fused; l++) {
+    const bool fused = R.kind == PROMPT_ROWS || R.kind == PROMPT_MID || R.kind == PROMPT_BIG;
+    for (int l = 0; l < c.layers && fused; l++) {
         Layer &L = m->layers[l];
-        const size_t F = c.ffn;
-        const bool norm_fused = !pf_big && (T <= 8 || rows_mo(m, L.t[T_WQ])) && T <= 16;
-        auto wp = [&](int id) { return pf_mid ? (const uint8_t *)L.t[id].mo : (pf_big ? (const uint8_t *)(L.t[id].x32 ? L.t[id].x32 : L.t[id].data) : rows_w(m, L.t[id])); };
-        const int mo_flag = pf_mid ? 1 : (pf_big ? 0 : rows_mo(m, L.t[T_WQ]));
-        auto lin = [&](const GmArgs &A, int id, int epi, int norm) {
-            if (pf_mid && gemm_mid_ok(L.t[id].dtype, A, epi)) return gemm_mid(A, epi, m->stream);
-            if (pf_mid) return ifa_fail(IFA_ERR_STATE, "mid-length GEMM declined a product of layer tensor %d", id);
-            return pf_big ? gemm_big(L.t[id].x32 ? (int)Q4_B32T1A : L.t[id].dtype, A, epi, m->stream) : gemm_rows_mfma_launch(A, epi, norm, m->stream);
-        };
-        Tensor nob;
-        GmArgs P;
-        auto clear = [&]() { memset(&P, 0, sizeof(P)); P.T = T; P.eps = c.eps; P.act_kind = c.act_kind; P.mo = mo_flag; P.no_waits = pf_big ? !m->opt_gemm_splitk : !m->opt_rows_kparts; };
-        clear();
-        if (!norm_fused && (rc = norm_rows(m, x, T, L.t[T_ATTN_NORM], pf_big ? L.t[T_ATTN_NORM_B] : nob, m->xn, c.attn_norm_base))) return rc;
-        P.W[0] = wp(T_WQ); P.W[1] = wp(T_WK); P.W[2] = wp(T_WV);
-        P.rows[0] = (int)QD; P.rows[1] = (int)KVD; P.rows[2] = (int)KVD; P.nsets = 3; P.nblk = (int)(D / 32);
-        P.X = norm_fused ? x : m->xn; P.ldx = (int)D;
-        if (norm_fused) { P.norm_w = (const half_t *)L.t[T_ATTN_NORM].data; P.multi_base = c.attn_norm_base; }
-        P.bias[0] = (const half_t *)L.t[T_WQ_B].data; P.bias[1] = (const half_t *)L.t[T_WK_B].data; P.bias[2] = (const half_t *)L.t[T_WV_B].data;
-        P.Yset[0] = m->q; P.Yset[1] = m->k; P.Yset[2] = m->v; P.ldyset[0] = (int)QD; P.ldyset[1] = (int)KVD; P.ldyset[2] = (int)KVD;
-        if ((rc = lin(P, T_WQ, GM_PLAIN, norm_fused ? 1 : 0))) return rc;
-        uint8_t *kdst = (uint8_t *)L.kcache + (size_t)prefix_len * m->kv_row_bytes;
-        uint8_t *vdst = (uint8_t *)L.vcache + (size_t)prefix_len * m->kv_row_bytes;
-        const bool kv_f16 = c.kv_dtype != Q8_B32T2;
-        bool kv_stored = false;
-        if (c.rope_order != 0) {
-            rc = ifa_rope_qk_store(m->q, m->k, m->v, c.head_dim, c.heads, c.kv_heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary,
-                                   kv_f16 ? kdst : nullptr, kv_f16 ? vdst : nullptr, m->kv_row_bytes / 2, s);
-            if (rc == IFA_OK) kv_stored = kv_f16;
-            else if (rc != IFA_ERR_STATE) return rc;
-            else {
-                if ((rc = ifa_rope(m->q, c.head_dim, c.heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary, s))) return rc;
-                if ((rc = ifa_rope(m->k, c.head_dim, c.kv_heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary, s))) return rc;
-            }
-        }
-        if (!kv_f16) {
-            if ((rc = ifa_quantize_act_q8(m->k, T, KVD, kdst, s))) return rc;
-            if ((rc = ifa_quantize_act_q8(m->v, T, KVD, vdst, s))) return rc;
-        } else if (!kv_stored) {
-            IFA_HIP_CHECK(hipMemcpyAsync(kdst, m->k, (size_t)T * m->kv_row_bytes, hipMemcpyDeviceToDevice, m->stream));
-            IFA_HIP_CHECK(hipMemcpyAsync(vdst, m->v, (size_t)T * m->kv_row_bytes, hipMemcpyDeviceToDevice, m->stream));
-        }
+        const Tensor nob;      // (the rows GEMM's route has no norm biases: rows_layers)
+        const bool norm_fused = R.norm_fused != 0, rows = R.kind == PROMPT_ROWS;
+        if (!norm_fused && (rc = norm_rows(m, x, T, L.t[T_ATTN_NORM], rows ? nob : L.t[T_ATTN_NORM_B], m->xn, c.attn_norm_base))) return rc;
+        GmArgs P = gm_qkv(m, L, T, R.qkv, norm_fused, norm_fused ? x : m->xn, nullptr);
+        if ((rc = gm_launch(m, L.t[T_WQ], P, R.qkv, R.qkv, GM_PLAIN, norm_fused))) return rc;
+        if ((rc = rope_store_rows(m, L, T, prefix_len))) return rc;
         if ((rc = ifa_attention(m->q, L.kcache, L.vcache, c.kv_dtype, prefix_len + T, T, prefix_len, c.heads, c.kv_heads,
                                 c.head_dim, c.use_alibi ? 1.0f : c.kq_scale, c.use_alibi, c.tp_rank * c.heads,
                                 c.heads * std::max(1, c.tp_size), m->att, s))) return rc;
-        clear();
-        P.W[0] = wp(T_WO); P.rows[0] = (int)D; P.nsets = 1; P.nblk = (int)(QD / 32);
-        P.X = m->att; P.ldx = (int)QD; P.bias[0] = (const half_t *)L.t[T_WO_B].data;
-        P.Y = m->a; P.ldy = (int)D; P.res = x; P.ldres = (int)D;
-        if (pf_res_mid) { P.W[0] = (const uint8_t *)L.t[T_WO].mo; P.mo = 1; P.no_waits = !m->opt_rows_kparts; }
-        if (pf_res_mid && gemm_mid_ok(L.t[T_WO].dtype, P, GM_RESIDUAL)) { if ((rc = gemm_mid(P, GM_RESIDUAL, m->stream))) return rc; }
-        else { if (pf_res_mid) { P.W[0] = wp(T_WO); P.mo = mo_flag; } if ((rc = lin(P, T_WO, GM_RESIDUAL, 0))) return rc; }
-        clear();
-        if (!norm_fused && (rc = norm_rows(m, m->a, T, L.t[T_FFN_NORM], pf_big ? L.t[T_FFN_NORM_B] : nob, m->hn, c.ffn_norm_base))) return rc;
-        if (c.experts > 0 && L.t[T_MOE_GATE].present()) {      // (pf_big only) mixture of experts: the attention half fused, the expert FFNs device-routed
+        P = gm_wo(m, L, T, R.wo, x);
+        if ((rc = gm_launch(m, L.t[T_WO], P, R.wo, R.qkv, GM_RESIDUAL, 0))) return rc;
+        if (!norm_fused && (rc = norm_rows(m, m->a, T, L.t[T_FFN_NORM], rows ? nob : L.t[T_FFN_NORM_B], m->hn, c.ffn_norm_base))) return rc;
+        if (c.experts > 0 && L.t[T_MOE_GATE].present()) {      // (Big only) mixture of experts: the attention half fused, the expert FFNs device-routed
             if ((rc = moe_ffn(m, L, m->hn, T))) return rc;
             if ((rc = ifa_add(m->f, m->a, (size_t)T * D, 0, m->f, s))) return rc;
             std::swap(m->x, m->f);
             x = m->x;
             continue;
         }
-        P.W[0] = wp(T_W1); P.W1 = wp(T_W3); P.rows[0] = (int)F; P.nsets = 1; P.nblk = (int)(D / 32);
-        P.X = norm_fused ? m->a : m->hn; P.ldx = (int)D;
-        if (norm_fused) { P.norm_w = (const half_t *)L.t[T_FFN_NORM].data; P.multi_base = c.ffn_norm_base; }
-        P.bias[0] = (const half_t *)L.t[T_W1_B].data; P.bias1 = (const half_t *)L.t[T_W3_B].data;
-        P.Y = m->t1; P.ldy = (int)F;
-        if ((rc = lin(P, T_W1, GM_GLU, norm_fused ? 1 : 0))) return rc;
-        clear();
-        P.W[0] = wp(T_W2); P.rows[0] = (int)D; P.nsets = 1; P.nblk = (int)(F / 32);
-        P.X = m->t1; P.ldx = (int)F; P.bias[0] = (const half_t *)L.t[T_W2_B].data;
-        P.Y = m->f; P.ldy = (int)D; P.res = m->a; P.ldres = (int)D;
-        if (pf_res_mid) { P.W[0] = (const uint8_t *)L.t[T_W2].mo; P.mo = 1; P.no_waits = !m->opt_rows_kparts; }
-        if (pf_res_mid && gemm_mid_ok(L.t[T_W2].dtype, P, GM_RESIDUAL)) { if ((rc = gemm_mid(P, GM_RESIDUAL, m->stream))) return rc; }
-        else { if (pf_res_mid) { P.W[0] = wp(T_W2); P.mo = mo_flag; } if ((rc = lin(P, T_W2, GM_RESIDUAL, 0))) return rc; }
+        P = gm_w13(m, L, T, R.w13, norm_fused);
+        if ((rc = gm_launch(m, L.t[T_W1], P, R.w13, R.qkv, GM_GLU, norm_fused))) return rc;
+        P = gm_w2(m, L, T, R.w2, m->f);
+        if ((rc = gm_launch(m, L.t[T_W2], P, R.w2, R.qkv, GM_RESIDUAL, 0))) return rc;
         std::swap(m->x, m->f);
         x = m->x;
     }
-    for (int l = pf_fused ? c.layers : 0; l < c.layers; l++) {
+    for (int l = fused ? c.layers : 0; l < c.layers; l++) {
         Layer &L = m->layers[l];
         // perf_stat spans in the reference's key space (inference_worker.cc:296-322, 806-950, 1030-1400): the whole layer under + 0 for layers
         // 0..5; for layer 0 (layer_idx_for_study_) + 300 = ProcessGpuLayer_Attention as a whole, + 10 its pre-norm, + 30 the q / k / v products
@@ -327,29 +436,10 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
             if ((rc = matmul(m, attn_in, T, L.t[T_WK], L.t[T_WK_B], m->k))) return rc;
             if ((rc = matmul(m, attn_in, T, L.t[T_WV], L.t[T_WV_B], m->v))) return rc;
         }
-        PerfSpan sp_rope(m, pbase + 50, st);
-        uint8_t *kdst = (uint8_t *)L.kcache + (size_t)prefix_len * m->kv_row_bytes;
-        uint8_t *vdst = (uint8_t *)L.vcache + (size_t)prefix_len * m->kv_row_bytes;
-        const bool kv_f16 = c.kv_dtype != Q8_B32T2;
-        bool kv_stored = false;
-        if (c.rope_order != 0) {
-            rc = ifa_rope_qk_store(m->q, m->k, m->v, c.head_dim, c.heads, c.kv_heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary,
-                                   kv_f16 ? kdst : nullptr, kv_f16 ? vdst : nullptr, m->kv_row_bytes / 2, s);
-            if (rc == IFA_OK) kv_stored = kv_f16;
-            else if (rc != IFA_ERR_STATE) return rc;
-            else {
-                if ((rc = ifa_rope(m->q, c.head_dim, c.heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary, s))) return rc;
-                if ((rc = ifa_rope(m->k, c.head_dim, c.kv_heads, T, prefix_len, c.rope_theta, c.rope_order, c.partial_rotary, s))) return rc;
-            }
+        {
+            PerfSpan sp(m, pbase + 50, st);
+            if ((rc = rope_store_rows(m, L, T, prefix_len))) return rc;
         }
-        if (!kv_f16) {
-            if ((rc = ifa_quantize_act_q8(m->k, T, KVD, kdst, s))) return rc;
-            if ((rc = ifa_quantize_act_q8(m->v, T, KVD, vdst, s))) return rc;
-        } else if (!kv_stored) {
-            IFA_HIP_CHECK(hipMemcpyAsync(kdst, m->k, (size_t)T * m->kv_row_bytes, hipMemcpyDeviceToDevice, m->stream));
-            IFA_HIP_CHECK(hipMemcpyAsync(vdst, m->v, (size_t)T * m->kv_row_bytes, hipMemcpyDeviceToDevice, m->stream));
-        }
-        sp_rope.done();
         {
             PerfSpan sp(m, pbase + 60, st);
             if ((rc = ifa_attention(m->q, L.kcache, L.vcache, c.kv_dtype, prefix_len + T, T, prefix_len, c.heads, c.kv_heads,
@@ -448,77 +538,44 @@ __global__ void __launch_bounds__(256) k_kv_store_rows(const half_t *__restrict_
 
 // ---- the batched step as five launches per layer (the structure of the batch-1 step: ifa_gemm_rows_mfma.hip with the norm
 // prologue / GLU / residual epilogues, k_dec_attn<.., BATCH>): dense models with the sequential RMS wiring, every linear in
-// tiled Q4_B32T1, 2..16 queries.  Everything else takes the op-by-op rows below.
-bool batch_fused_ok(const ifa_model *m, int n)
+// tiled Q4_B32T1 or with an MO copy (rows_layers), 2..16 queries, up to 32 from the MO copies.  Everything else takes the op-by-op rows
+// of forward_batch.
+// batch_route_ready plans a batched step of n rows and builds what it needs before its launches (and its capture).  entry: the call is
+// ifa_model_decode_batch's, whose decisions -- exact order, several steps -- are planned too, and whose steps make themselves ready.
+static int batch_route_ready(ifa_model *m, int n, bool logits_out, bool entry, BatchRoute &R)
 {
-    const ifa_model_config &c = m->cfg;
-    if (!m->opt_batch_fused || !m->opt_gemm_rows || !gemm_rows_use_mfma() || n < 2 || n > (m->opt_rows_mo ? 32 : 16) || m->topo) return false;      // (17..32 rows: MO copies only)
-    if (has_post_norms(m)) return false;
-    if (c.norm_kind != 0 || c.parallel_attn || c.share_input) return false;
-    if (scale_on(c.attn_out_scale) || scale_on(c.ffn_out_scale) || scale_on(c.out_scale)) return false;
-    const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim, F = c.ffn;
-    if (D % 128 || QD % 128 || F % 128 || D > 4096 || KVD % 16 || D % 16 || F % 16) return false;
-    if (c.head_dim != 32 && c.head_dim != 48 && c.head_dim != 64 && c.head_dim != 80 && c.head_dim != 96 && c.head_dim != 128) return false;
-    if (c.kv_dtype == Q8_B32T2 && c.head_dim % 32 != 0) return false;
-    if (dec_attn_smem(c.head_dim, c.max_ctx) > IFA_LDS_LIMIT) return false;
-    for (const Layer &L : m->layers) {
-        const bool moe = c.experts > 0 && L.t[T_MOE_GATE].present();      // MoE layers: the attention half is fused, the FFN runs moe_ffn
-        const int ids[] = {T_WQ, T_WK, T_WV, T_WO, T_W1, T_W3, T_W2};
-        for (int id : ids) {
-            if (moe && (id == T_W1 || id == T_W3 || id == T_W2)) continue;
-            if (!L.t[id].present() || !L.t[id].tiled) return false;
-            if (!is_q4(L.t[id].dtype) && !(m->opt_rows_mo && rows_mo_fmt(L.t[id].dtype) && L.t[id].cols % 128 == 0)) return false;
-        }
-        if (moe && !moe_device_ok(m, L)) return false;
-        if (!L.t[T_ATTN_NORM].present() || !L.t[T_FFN_NORM].present() || L.t[T_ATTN_NORM_B].present() || L.t[T_FFN_NORM_B].present()) return false;
+    BatchRouteFacts f;
+    f.n = n; f.exact_order = entry && m->opt_exact_order; f.may_chunk = entry;
+    f.rows_mo = m->opt_rows_mo; f.gemm_rows = m->opt_gemm_rows; f.batch_fused = m->opt_batch_fused; f.rows_kparts = m->opt_rows_kparts;
+    f.batch_graph = m->opt_batch_graph; f.graph = m->opt_graph; f.topo = m->topo != nullptr; f.logits_out = logits_out;
+    if (!f.exact_order) { const RouteModelFacts mf = route_model_facts(m); f.rows_layers = mf.rows_layers; f.has_moe = mf.has_moe; }
+    R = plan_batch_route(f);
+    if (entry) return IFA_OK;      // (its steps make themselves ready)
+    int rc;
+    if (R.need_mo) {
+        bool replan = false;
+        if ((rc = route_mo_ready(m, replan))) return rc;
+        if (replan) { f.rows_mo = m->opt_rows_mo; R = plan_batch_route(f); }
+        if (R.kind == BATCH_FUSED && (rc = gemm_rows_kparts_reserve(m->stream))) return rc;
     }
-    return true;
+    if (f.has_moe && m->opt_moe_overlap && (rc = ensure_side_stream(m))) return rc;
+    return IFA_OK;
 }
 
-// prompts above `prefill_big_min` tokens as four launches of the large-tile GEMM per layer (forward_ops, pf_big): dense layers with the
-// sequential wiring, every linear a 20-byte-block Q4 tensor (wq / wk / wv of one format), dims in multiples of 64
-bool prefill_big_ok(const ifa_model *m)
-{
-    const ifa_model_config &c = m->cfg;
-    if (!m->opt_prefill_big || m->topo || c.parallel_attn || c.share_input || has_post_norms(m)) return false;
-    if (scale_on(c.attn_out_scale) || scale_on(c.ffn_out_scale)) return false;
-    const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, F = c.ffn;
-    if (D % 64 || QD % 64 || F % 64) return false;
-    for (const Layer &L : m->layers) {
-        const bool moe = c.experts > 0 && L.t[T_MOE_GATE].present();      // MoE layers: the attention half is fused, the FFN runs moe_ffn
-        const int ids[] = {T_WQ, T_WK, T_WV, T_WO, T_W1, T_W3, T_W2};
-        for (int id : ids) {
-            if (moe && (id == T_W1 || id == T_W3 || id == T_W2)) continue;
-            const bool b64 = (L.t[id].dtype == Q4_B64T1 || L.t[id].dtype == Q3H_B64T1) && L.t[id].tiled;      // via their Q4_B32T1A-layout copy (ensure_x32)
-            if (!L.t[id].present() || !L.t[id].data || (L.t[id].dtype != Q4_B32T1A && L.t[id].dtype != Q4_B32T1B && !b64)) return false;
-        }
-        if (L.t[T_WK].dtype != L.t[T_WQ].dtype || L.t[T_WV].dtype != L.t[T_WQ].dtype || (!moe && L.t[T_W3].dtype != L.t[T_W1].dtype)) return false;
-        if (!L.t[T_ATTN_NORM].present() || !L.t[T_FFN_NORM].present()) return false;
-    }
-    return true;
-}
-
-int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext, const void *rows_l, bool draft)
+static int batch_fused_layer(ifa_model *m, const BatchRoute &R, int l, int n, const half_t *x, half_t *xnext, const void *rows_l, bool draft)
 {
     const ifa_model_config &c = m->cfg;
     Layer &L = m->layers[(size_t)l];
-    const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim, F = c.ffn;
+    const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim;
     int rc;
-    GmArgs P;
-    auto clear = [&]() { memset(&P, 0, sizeof(P)); P.T = n; P.eps = c.eps; P.act_kind = c.act_kind; P.no_waits = !m->opt_rows_kparts; };
     // 1. RmsNorm -> wq | wk | wv  (one virtual row space, one [n][q | k | v] output)
-    clear();
-    P.W[0] = rows_w(m, L.t[T_WQ]); P.W[1] = rows_w(m, L.t[T_WK]); P.W[2] = rows_w(m, L.t[T_WV]); P.mo = rows_mo(m, L.t[T_WQ]);
-    P.rows[0] = (int)QD; P.rows[1] = (int)KVD; P.rows[2] = (int)KVD; P.nsets = 3; P.nblk = (int)(D / 32);
-    // (9..16 queries: the activation rows are staged in chunks of 2048 columns, so the norm runs as its own launch)
-    const bool norm_fused = (n <= 8 || rows_mo(m, L.t[T_WQ])) && n <= 16;      // (MO layout: 16 rows x 4096 columns are one chunk too; 17..32 rows: chunked)
-    Tensor nob;
+    // (9..16 queries: the activation rows are staged in chunks of 2048 columns, so the norm runs as its own launch; MO layout: 16 rows x
+    // 4096 columns are one chunk too; 17..32 rows: chunked)
+    const bool norm_fused = R.norm_fused != 0;
+    const Tensor nob;
     if (!norm_fused && (rc = norm_rows(m, x, n, L.t[T_ATTN_NORM], nob, m->xn, c.attn_norm_base))) return rc;
-    P.X = norm_fused ? x : m->xn; P.ldx = (int)D;
-    if (norm_fused) { P.norm_w = (const half_t *)L.t[T_ATTN_NORM].data; P.multi_base = c.attn_norm_base; }
-    P.bias[0] = (const half_t *)L.t[T_WQ_B].data; P.bias[1] = (const half_t *)L.t[T_WK_B].data; P.bias[2] = (const half_t *)L.t[T_WV_B].data;
-    P.Y = m->bqkv; P.ldy = (int)(QD + 2 * KVD);
-    if ((rc = gemm_rows_mfma_launch(P, GM_PLAIN, norm_fused ? 1 : 0, m->stream))) return rc;
+    GmArgs P = gm_qkv(m, L, n, R.gm, norm_fused, norm_fused ? x : m->xn, m->bqkv);
+    if ((rc = gm_launch(m, L.t[T_WQ], P, R.gm, R.gm, GM_PLAIN, norm_fused))) return rc;
     // 2. RoPE, KV store, attention of every query on its own cache.  Draft step (the n rows are consecutive positions of ONE slot): the
     // K / V rows of all of them go to the cache in a launch of their own first, and the attention kernel leaves the cache alone
     if (draft && (rc = draft_kv_store_launch(m, n, m->bqkv + QD, m->bqkv + QD + KVD, (int)(QD + 2 * KVD), rows_l))) return rc;
@@ -536,11 +593,8 @@ int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext
         if (rc) return rc;
     }
     // 3. wo (+ bias) + residual
-    clear();
-    P.W[0] = rows_w(m, L.t[T_WO]); P.mo = rows_mo(m, L.t[T_WO]); P.rows[0] = (int)D; P.nsets = 1; P.nblk = (int)(QD / 32);
-    P.X = m->att; P.ldx = (int)QD; P.bias[0] = (const half_t *)L.t[T_WO_B].data;
-    P.Y = m->a; P.ldy = (int)D; P.res = x; P.ldres = (int)D;
-    if ((rc = gemm_rows_mfma_launch(P, GM_RESIDUAL, 0, m->stream))) return rc;
+    P = gm_wo(m, L, n, R.gm, x);
+    if ((rc = gm_launch(m, L.t[T_WO], P, R.gm, R.gm, GM_RESIDUAL, 0))) return rc;
     if (c.experts > 0 && L.t[T_MOE_GATE].present()) {
         // mixture of experts: norm, the device-routed expert FFNs over the n rows (moe_ffn_device), residual
         Tensor none;
@@ -552,20 +606,12 @@ int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext
         return ifa_add(m->f, m->a, (size_t)n * D, 0, xnext, (ifa_stream)m->stream);
     }
     // 4. RmsNorm -> w1, w3 -> act(w1 x) * (w3 x)
-    clear();
-    P.W[0] = rows_w(m, L.t[T_W1]); P.W1 = rows_w(m, L.t[T_W3]); P.mo = rows_mo(m, L.t[T_W1]); P.rows[0] = (int)F; P.nsets = 1; P.nblk = (int)(D / 32);
     if (!norm_fused && (rc = norm_rows(m, m->a, n, L.t[T_FFN_NORM], nob, m->hn, c.ffn_norm_base))) return rc;
-    P.X = norm_fused ? m->a : m->hn; P.ldx = (int)D;
-    if (norm_fused) { P.norm_w = (const half_t *)L.t[T_FFN_NORM].data; P.multi_base = c.ffn_norm_base; }
-    P.bias[0] = (const half_t *)L.t[T_W1_B].data; P.bias1 = (const half_t *)L.t[T_W3_B].data;
-    P.Y = m->t1; P.ldy = (int)F;
-    if ((rc = gemm_rows_mfma_launch(P, GM_GLU, norm_fused ? 1 : 0, m->stream))) return rc;
+    P = gm_w13(m, L, n, R.gm, norm_fused);
+    if ((rc = gm_launch(m, L.t[T_W1], P, R.gm, R.gm, GM_GLU, norm_fused))) return rc;
     // 5. w2 (+ bias) + residual -> the next layer's input
-    clear();
-    P.W[0] = rows_w(m, L.t[T_W2]); P.mo = rows_mo(m, L.t[T_W2]); P.rows[0] = (int)D; P.nsets = 1; P.nblk = (int)(F / 32);
-    P.X = m->t1; P.ldx = (int)F; P.bias[0] = (const half_t *)L.t[T_W2_B].data;
-    P.Y = xnext; P.ldy = (int)D; P.res = m->a; P.ldres = (int)D;
-    return gemm_rows_mfma_launch(P, GM_RESIDUAL, 0, m->stream);
+    P = gm_w2(m, L, n, R.gm, xnext);
+    return gm_launch(m, L.t[T_W2], P, R.gm, R.gm, GM_RESIDUAL, 0);
 }
 
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
@@ -609,22 +655,12 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     const int *tok_d = pos_d + n;
     // Everything the device does in a step depends on the step only through the tables above (fixed addresses), so
     // for dense models the whole step -- table upload included -- is captured once per batch size and replayed.
-    bool has_moe = false;
-    for (const Layer &Lc : m->layers) has_moe = has_moe || (c.experts > 0 && Lc.t[T_MOE_GATE].present());
-    // (measured on Llama-2-7B Q4: the batched step is bound by the small-T GEMM kernels, ~6.7 ms with or without the
-    //  graph, so replay is opt-in: set_option("batch_graph", 1))
-    bool fused = batch_fused_ok(m, n);          // five launches per layer: launch-bound without a graph, so it is replayed
-    if (fused) {
-        int rcm = ensure_mo(m); if (rcm) return rcm;
-        // ensure_mo may have DOWNGRADED the model (the copies did not fit: opt_rows_mo = 0): what batch_fused_ok answered with the
-        // copies in view -- up to 32 rows, the 64-weight formats -- no longer holds, so it is asked again before a path or a graph
-        // is chosen; a step the tiled kernels do not cover takes the op-by-op rows below
-        fused = batch_fused_ok(m, n);
-        if (fused && (rcm = gemm_rows_kparts_reserve(m->stream))) return rcm;
-    }
-    if (has_moe && m->opt_moe_overlap) { int rcs = ensure_side_stream(m); if (rcs) return rcs; }
-    // (MoE layers of the fused step route on the device -- no host round trip -- so they are captured too)
-    const bool use_graph = (m->opt_batch_graph || fused) && m->opt_graph && (!has_moe || fused) && !logits_out && !tp;
+    // (measured on Llama-2-7B Q4: the op-by-op step is bound by the small-T GEMM kernels, ~6.7 ms with or without the graph, so its replay
+    //  is opt-in: set_option("batch_graph", 1).  The fused step -- five launches per layer, MoE layers routed on the device -- is
+    //  launch-bound without a graph, so it is replayed)
+    BatchRoute R;
+    if ((rc = batch_route_ready(m, n, logits_out != nullptr, false, R))) return rc;
+    const bool fused = R.kind == BATCH_FUSED, use_graph = R.captured != 0;
     const int attn_ctx = use_graph ? c.max_ctx : max_ctx;     // LDS sizing of the attention kernel must not depend on the step
     std::map<int, hipGraphExec_t> &graphs = draft ? m->draft_graphs : m->batch_graphs;
     if (use_graph) {
@@ -656,7 +692,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     bool xn_ready = false;           // see forward_ops: every residual Add is fused with the norm that follows it
     if (fused) {
         for (int l = 0; l < c.layers; l++) {
-            if ((rc = batch_fused_layer(m, l, n, x, m->f, rows_d + (size_t)l * (size_t)n, draft))) return rc;
+            if ((rc = batch_fused_layer(m, R, l, n, x, m->f, rows_d + (size_t)l * (size_t)n, draft))) return rc;
             std::swap(m->x, m->f);
             x = m->x;
         }
@@ -735,29 +771,29 @@ int ifa_model_forward(ifa_model *m, const int *tokens_host, int n_tokens, int pr
     IFA_REQUIRE(m && m->finalized, "ifa_model_forward: model not finalized");
     IFA_REQUIRE(tokens_host, "ifa_model_forward: null tokens");
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
-    if (m->opt_exact_order) {      // order-exact: the tokens one by one through the single-row step (the reference's T = 1 branch for every row)
-        const size_t V = m->g[T_LM_HEAD].present() ? m->g[T_LM_HEAD].rows : 0;
+    PromptRoute R;
+    int rc = prompt_route_ready(m, n_tokens, prefix_len, true, R);
+    if (rc) return rc;
+    const size_t V = m->g[T_LM_HEAD].present() ? m->g[T_LM_HEAD].rows : 0;
+    if (R.kind == PROMPT_EXACT) {      // order-exact: the tokens one by one through the single-row step (the reference's T = 1 branch for every row)
         for (int t = 0; t < n_tokens; t++) {
-            int rc = forward_exact(m, tokens_host[t], prefix_len + t, logits_out_dev ? (char *)logits_out_dev + (size_t)t * V * 2 : nullptr,
-                                   t == n_tokens - 1 ? next_token_host : nullptr);
+            rc = forward_exact(m, tokens_host[t], prefix_len + t, logits_out_dev ? (char *)logits_out_dev + (size_t)t * V * 2 : nullptr,
+                               t == n_tokens - 1 ? next_token_host : nullptr);
             if (rc) return rc;
         }
         return IFA_OK;
     }
-    // Round 5: prompts of 34..48 tokens as TWO passes of the rows GEMM (32 tokens, then 2..16: the weights stream into registers five
-    // groups deep) instead of one pass of the op-by-op layer: 40 tokens 7.08 -> 6.35 ms, 48 tokens 7.26 -> 6.67 (profiles/r05_prompt_lengths.log;
-    // two passes of 17..32 rows each -- 49..64 tokens -- measured no faster than the tile kernels).  The second pass reads the first
-    // one's K / V rows from the cache like any continued prompt; every row goes through the kernels of a prompt of <= 32 tokens.  Never
-    // a one-token pass: a single row takes the int8 GEMV (the reference's rule for ONE row), which is not how a prompt's rows are computed.
-    if (m->opt_prefill_chunk && !m->topo && n_tokens >= 34 && n_tokens <= 48 && m->cfg.experts == 0 && !prefill_mid_ok(m, n_tokens, false) && batch_fused_ok(m, 32)
-        && prefix_len >= 0 && prefix_len + n_tokens <= m->cfg.max_ctx) {
-        const int t1 = 32;
-        const size_t V = m->g[T_LM_HEAD].rows;
-        int rc = forward_ops(m, tokens_host, t1, prefix_len, logits_out_dev, nullptr, true);
-        if (rc) return rc;
-        return forward_ops(m, tokens_host + t1, n_tokens - t1, prefix_len + t1, logits_out_dev ? (char *)logits_out_dev + (size_t)t1 * V * 2 : nullptr, next_token_host);
-    }
-    return forward_ops(m, tokens_host, n_tokens, prefix_len, logits_out_dev, next_token_host);
+    if (!R.first_pass) return forward_ops(m, tokens_host, n_tokens, prefix_len, logits_out_dev, next_token_host, false, &R);
+    // Two passes (round 5: 32 tokens, then 2..16 through the rows GEMM, whose weights stream into registers five groups deep, instead of
+    // one pass of the op-by-op layer: 40 tokens 7.08 -> 6.35 ms, 48 tokens 7.26 -> 6.67, profiles/r05_prompt_lengths.log; two passes of 17..32
+    // rows each -- 49..64 tokens -- measured no faster than the tile kernels).  The second pass reads the first one's K / V rows from the
+    // cache like any continued prompt; every row goes through the kernels of a prompt of <= 32 tokens.  Never a one-token pass: a single
+    // row takes the int8 GEMV (the reference's rule for ONE row), which is not how a prompt's rows are computed.  Each pass plans itself.
+    const int t1 = R.first_pass;
+    if ((rc = forward_ops(m, tokens_host, t1, prefix_len, logits_out_dev, nullptr, true))) return rc;
+    rc = forward_ops(m, tokens_host + t1, n_tokens - t1, prefix_len + t1, logits_out_dev ? (char *)logits_out_dev + (size_t)t1 * V * 2 : nullptr, next_token_host);
+    m->prompt_route = R;
+    return rc;
 }
 
 int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host,
@@ -766,7 +802,9 @@ int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const in
     IFA_REQUIRE(m && m->finalized, "ifa_model_decode_batch: model not finalized");
     IFA_REQUIRE(n >= 1 && n <= ifa_model::RING && tokens_host && positions_host && kv_slots_host, "ifa_model_decode_batch: bad arguments");
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
-    if (m->opt_exact_order) {      // order-exact: every query's row through the single-row step on ITS cache set (a batched step of the
+    BatchRoute R;
+    { int rc = batch_route_ready(m, n, logits_out_dev != nullptr, true, R); if (rc) return rc; }
+    if (R.kind == BATCH_EXACT) {      // order-exact: every query's row through the single-row step on ITS cache set (a batched step of the
         // reference is n independent rows; its T > 1 linear branch has no order-exact form here, so the rows go one by one)
         const int back = m->cur_slot;
         const size_t V = m->g[T_LM_HEAD].present() ? m->g[T_LM_HEAD].rows : 0;
@@ -782,13 +820,12 @@ int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const in
     }
     // more queries than the fused five-launch step takes (16): balanced chunks of <= 16, each its own step (the queries are
     // independent; 32 queries op-by-op took 6.7 ms against 2 x 3.1 ms for two fused steps)
-    const int fused_max = batch_fused_ok(m, 32) ? 32 : 16;
-    if (n > fused_max && batch_fused_ok(m, 16)) {
+    if (R.chunk) {
         for (int c0 = 0; c0 < n; c0++) if (kv_slots_host[c0] < 0) return ifa_fail(IFA_ERR_ARG, "decode_batch: KV slot %d", kv_slots_host[c0]);
         for (int a = 0; a < n; a++)
             for (int b = 0; b < a; b++)
                 if (kv_slots_host[a] == kv_slots_host[b]) return ifa_fail(IFA_ERR_ARG, "decode_batch: KV slot %d used twice", kv_slots_host[a]);
-        const int k = (n + fused_max - 1) / fused_max, per = (n + k - 1) / k;
+        const int per = R.chunk;
         for (int c0 = 0; c0 < n; c0 += per) {
             const int nc = std::min(per, n - c0);
             m->pool.chunk0 = c0; m->pool.last_chunk = c0 + nc >= n;

@@ -36,6 +36,7 @@
 #include "ifa_decode_singles.h"
 #include "ifa_decode_qkv_attn.h"
 #include "ifa_decode_chain.h"
+#include "ifa_prompt_route.h"
 
 using namespace ifa;
 
@@ -137,6 +138,7 @@ struct ifa_model : Scratch {
     // What the decode step of the last planned call runs (ifa_decode_route.h: the attention launch, its kernel instance, the chained
     // FFN launch) and the reach it was planned for; the captured steps hold it (decode_route_ready)
     DecRoute route; int route_reach = 256;
+    PromptRoute prompt_route;      // what the last prompt call ran (ifa_prompt_route.h, prompt_route_ready)
     // attention as the tail of the QKV launch (ifa_decode_qkv_attn.h): granules [layers][(heads + 2 kv_heads) * head_dim], the
     // decode-call counter the tags are built from, its own error word
     int opt_fuse_attn = 1, opt_fuse_attn_timeout_us = 20000;
@@ -196,7 +198,7 @@ struct ifa_model : Scratch {
     // debug_layers = N: layers [layer0, layer0 + N)) and, with debug_hidden_in, takes its input from the buffer "x" as the caller
     // left it instead of gathering the token's embedding row -- the SAME captured launches the bench times, fed the oracle's state
     int opt_debug_layer0 = 0, opt_debug_hidden_in = 0;
-    // prompts ABOVE this many tokens take the four large-tile launches per layer (forward_ops, pf_big).  Round 4: 128.  Round 5: 47 -- with
+    // prompts ABOVE this many tokens take the four large-tile launches per layer (forward_ops on a Big route).  Round 4: 128.  Round 5: 47 -- with
     // four parts of K for the products that offer 32..96 tiles, 64 / 96 / 128 tokens run 5 / 8 / 9 % faster than the op-by-op layer
     // (7 products + 4 element-wise launches), 40 tokens the same (profiles/r05_prompt_lengths.log)
     int opt_prefill_big_min = 47;
@@ -334,11 +336,6 @@ extern "C" int ifa_attention_rows(const void *q, const void *rows_dev, int kv_dt
 extern "C" int ifa_rope_rows(void *x, int head_dim, int heads, int tokens, const int *positions_dev, float theta, int order,
                              float partial_rotary_factor, ifa_stream stream);
 
-// weight pointer of a rows-GEMM launch: the MO copy when it exists (all sets of a launch alike: ensure_mo builds all or none)
-static inline const uint8_t *rows_w(const ifa_model *m, const Tensor &t) { return (const uint8_t *)(m->opt_rows_mo && t.mo ? t.mo.get() : t.tiled.get()); }
-
-static inline int rows_mo(const ifa_model *m, const Tensor &t) { return m->opt_rows_mo && t.mo ? 1 : 0; }
-
 namespace ifae {
 
 // "raise the dynamic-LDS attribute when over 48 KiB, then launch"
@@ -434,11 +431,9 @@ int norm_rows(ifa_model *m, const half_t *x, int T, const Tensor &w, const Tenso
 int ffn_dense(ifa_model *m, const half_t *x, int T, const Tensor &w1, const Tensor &b1, const Tensor &w3, const Tensor &b3,
                      const Tensor &w2, const Tensor &b2, half_t *out, int perf_base = 0);
 int layer_tail_ops(ifa_model *m, int l, int T, half_t *&x, const half_t *attn_in, bool &xn_ready);
-int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, bool no_head = false);
-bool batch_fused_ok(const ifa_model *m, int n);
-bool prefill_big_ok(const ifa_model *m);
-bool prefill_mid_ok(ifa_model *m, int T, bool any_length);
-int batch_fused_layer(ifa_model *m, int l, int n, const half_t *x, half_t *xnext, const void *rows_l, bool draft = false);
+int prompt_route_ready(ifa_model *m, int T, int prefix_len, bool entry, PromptRoute &R);
+int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, bool no_head = false,
+                const PromptRoute *planned = nullptr);
 // ifa_decode_draft_kv.hip: RoPE + cache rows of the n rows of a draft step (rows_l: the layer's AttnRowH[n]) in one launch
 int draft_kv_store_launch(ifa_model *m, int n, const half_t *k, const half_t *v, int stride, const void *rows_l);
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,

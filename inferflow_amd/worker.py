@@ -280,6 +280,18 @@ class DecodeWorker:
         d["kind"] = self.ROUTE_KINDS[d["kind"]]
         return d
 
+    PROMPT_ROUTE_FIELDS = ("kind", "first_pass", "norm_fused", "res_mid") + tuple(
+        p + "_" + k for p in ("qkv", "wo", "w13", "w2") for k in ("kernel", "src", "mo", "no_waits")) + ("need_mo", "need_x32")
+    PROMPT_ROUTE_KINDS = ("exact", "op_by_op", "rows", "mid", "big")
+
+    def prompt_route(self):
+        """the route of the last prompt call (csrc/ifa_prompt_route.h) as a dict; kind as one of PROMPT_ROUTE_KINDS"""
+        out = (C.c_int * len(self.PROMPT_ROUTE_FIELDS))()
+        check(lib().ifa_model_prompt_route(self._h, out, len(out)))
+        d = dict(zip(self.PROMPT_ROUTE_FIELDS, out))
+        d["kind"] = self.PROMPT_ROUTE_KINDS[d["kind"]]
+        return d
+
     def get_tensor_host(self, layer, tid):
         """(dtype, uint8/uint16 numpy copy, rows, cols) of a loaded tensor in reference layout, or None."""
         d, p, r, c = C.c_int(), C.c_void_p(), C.c_size_t(), C.c_size_t()
