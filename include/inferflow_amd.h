@@ -656,6 +656,20 @@ int ifa_decode_route_plan(const int *facts, int n_facts, int *out, int n_out);
  * visible_cus and waits (1: launches whose workgroups wait for each other are allowed) as the engine sees them now. */
 int ifa_model_decode_route(ifa_model *m, int *out, int n_out);
 
+/* The decode GEMV launch plan (csrc/ifa_decode_gemv_plan.h): which fused GEMV instance a launch runs.  Host-only, no GPU needed.
+ * facts[8], in the order of DecGemvFacts: dtype (an element type id, or 99 for Q3H_B64T1 streamed in its native 32-byte form: option
+ * q3h_native), epi (0 plain, 1 residual, 2 gated pair, 3 activation, 4 - 7 the expert epilogues), norm
+ * (0 none, 1 RMS-norm prologue, 2 the activation arrives quantised), x_add, cols, total_rows (gated: row pairs), num_cus, rpw (the
+ * rpw_* option).  out[13], in the order of DecGemvPlan: kind (0 none, 1 k_dec_gemv, 2 k_dec_gemv_long, 3 k_dec_gemv_h), nj, nchunk,
+ * njl, rw, threads, np, grid, waves, npass, partial (the last pass is short), lds, error (0 ok, 1 dtype, 2 columns, 3 more than 4
+ * chunks / 32768 columns, 4 too many blocks per lane for a normalised / gated input, 5 packed launch scalars, 6 no such instance). */
+int ifa_decode_gemv_plan(const int *facts, int n_facts, int *out, int n_out);
+/* The same for the launch of one role (0 qkv, 1 wo, 2 w1 / w3, 3 w2) of a layer as the engine would enqueue it now: out[21] = the 13
+ * values above, then single (0: the step would not run this launch on its own: the fused QKV + attention tail, the chained FFN
+ * launch or the op-by-op step takes its place), dtype, epi, norm, cols, total_rows, num_cus, launches (3: q / k / v of different
+ * formats get one launch each, the plan is wq's). */
+int ifa_model_gemv_plan(ifa_model *m, int layer, int role, int *out, int n_out);
+
 /* The prompt and batched-step route plans (csrc/ifa_prompt_route.h, DESIGN.md "Prompt route plan"): which kernels the linears of a
  * prompt's / a batched step's layers go through, from which copy of the weights, and what is built first.  Host-only, no GPU needed.
  * Prompt: facts[19], in the order of PromptRouteFacts: T, exact_order, perf_stat, prefill_chunk, prefill_mid, prefill_mid_max,

@@ -139,6 +139,8 @@ SIGNATURES = {
     "ifa_model_time_kernel": (_i, [_vp, _i, _i, _vp]),
     "ifa_decode_route_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_model_decode_route": (_i, [_vp, _vp, _i]),
+    "ifa_decode_gemv_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_model_gemv_plan": (_i, [_vp, _i, _i, _vp, _i]),
     "ifa_prompt_route_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_batch_route_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_model_prompt_route": (_i, [_vp, _vp, _i]),

@@ -4,13 +4,9 @@
 #pragma once
 #include "ifa_host.h"
 #include "ifa_decode_kernels.h"
+#include "ifa_decode_gemv_plan.h"      // DecGemvLimits, dec_rw / dec_threads / dec_np, plan_dec_gemv
 
 namespace ifa {
-
-// blocks-per-lane limit of each format's instantiations (cols <= 64 * capacity * MAXNJ)
-template <int DT> struct DecGemvLimits { static constexpr int MAXNJ = 4; };
-template <> struct DecGemvLimits<Q4_B32T1A> { static constexpr int MAXNJ = 8; };
-template <> struct DecGemvLimits<Q8_B32T2> { static constexpr int MAXNJ = 6; };
 
 // true if the fused GEMV can stream a [rows][cols] tensor of this dtype
 bool dec_gemv_supported(int w_dtype, size_t cols);
@@ -29,6 +25,13 @@ template <int DT>
 int dec_gemv_launch_dt(int epi, int norm, const DecGemvParams &P, int wgs_per_cu, hipStream_t s);
 
 int dec_num_cus();
+
+// What dec_gemv_launch / dec_gemv_h_launch would run for these facts (ifa_decode_gemv_plan.h), by the run-time dtype as the engine's
+// launch_dec_gemv dispatches: the int8-path formats and Q3H_NATIVE to the first, every other format to the second.  Pure host code.
+template <int DT>
+DecGemvPlan dec_gemv_plan_dt(const DecGemvFacts &f);
+DecGemvPlan dec_gemv_plan(const DecGemvFacts &f);
+DecGemvPlan dec_gemv_h_plan(const DecGemvFacts &f);
 
 // Q3H_B64T1 reference-layout rows -> the native 32-byte streaming copy of ifa_decode_formats.h WRowQ3HN (ifa_dgemv_q3hn.hip)
 int q3h_native_rows(const void *aos, size_t rows, size_t cols, void *dst, hipStream_t s);

@@ -28,6 +28,7 @@
 #include "ifa_math.h"
 #include "ifa_tiled.h"
 #include "ifa_decode_formats.h"
+#include "ifa_decode_gemv_plan.h"      // DEC_THREADS / DEC_WAVES, DecEpilogue, xlds_bytes, dec_fmt_dw: one definition for the plan and the kernels
 
 namespace ifa {
 
@@ -93,8 +94,6 @@ __device__ __forceinline__ void q8x4_dequant_h(uint32_t w, half2_t sc2, half2_t 
 #ifndef IFA_NT_WEIGHTS
 #define IFA_NT_WEIGHTS 1            // stream weights with the non-temporal policy (read once per token)
 #endif
-constexpr int DEC_THREADS = 512;   // 8 waves per workgroup
-constexpr int DEC_WAVES = DEC_THREADS / 64;
 
 // ------------------------------------------------------------------ LDS image
 // of the (normalised and) quantised activation vector
@@ -106,16 +105,7 @@ struct XLds {
     half_t *xh;      // [cols] staged input
 };
 
-__host__ __device__ inline size_t xlds_bytes(int cols)
-{
-    size_t nb = (size_t)cols / 32;
-    size_t off = ((size_t)cols + 15) / 16 * 16 + nb * 8;
-    off = (off + 15) / 16 * 16;
-    off += 132 * 4;
-    off = (off + 15) / 16 * 16;
-    off += (size_t)cols * 2;
-    return off + 16;
-}
+// (xlds_bytes: ifa_decode_gemv_plan.h)
 
 __device__ __forceinline__ XLds xlds_carve(char *smem, int cols)
 {
@@ -428,21 +418,16 @@ struct WRowQ4 {
 
 // format -> register images.  DW = VGPRs one block of one row costs a lane (sizes the rows in flight).
 template <int DT, int NJ> struct DecFmt;
-template <int NJ> struct DecFmt<Q4_B32T1A, NJ> { using X = XRegsQ4<NJ>; using W = WRowQ4<NJ>; static constexpr int DW = 5; };
-template <int NJ> struct DecFmt<Q8_B32T2, NJ> { using X = XRegsNat<NJ>; using W = WRowQ8T2<NJ>; static constexpr int DW = 9; };
-template <int NJ> struct DecFmt<Q4_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ4B64<NJ>; static constexpr int DW = 9; };
-template <int NJ> struct DecFmt<Q3H_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ4B64<NJ>; static constexpr int DW = 9; };      // nibble-pair tiled form (ifa_tiled.h)
-template <int NJ> struct DecFmt<Q3H_NATIVE, NJ> { using X = XRegsB64<NJ>; using W = WRowQ3HN<NJ>; static constexpr int DW = 8; };       // native 32-byte form (option q3h_native)
-template <int NJ> struct DecFmt<Q5_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ5B64<NJ>; static constexpr int DW = 11; };
-template <int NJ> struct DecFmt<Q6_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ6B64<NJ>; static constexpr int DW = 13; };
+template <int NJ> struct DecFmt<Q4_B32T1A, NJ> { using X = XRegsQ4<NJ>; using W = WRowQ4<NJ>; static constexpr int DW = dec_fmt_dw(Q4_B32T1A); static_assert(DW == 5, ""); };
+template <int NJ> struct DecFmt<Q8_B32T2, NJ> { using X = XRegsNat<NJ>; using W = WRowQ8T2<NJ>; static constexpr int DW = dec_fmt_dw(Q8_B32T2); static_assert(DW == 9, ""); };
+template <int NJ> struct DecFmt<Q4_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ4B64<NJ>; static constexpr int DW = dec_fmt_dw(Q4_B64T1); static_assert(DW == 9, ""); };
+template <int NJ> struct DecFmt<Q3H_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ4B64<NJ>; static constexpr int DW = dec_fmt_dw(Q3H_B64T1); static_assert(DW == 9, ""); };      // nibble-pair tiled form (ifa_tiled.h)
+template <int NJ> struct DecFmt<Q3H_NATIVE, NJ> { using X = XRegsB64<NJ>; using W = WRowQ3HN<NJ>; static constexpr int DW = dec_fmt_dw(Q3H_NATIVE); static_assert(DW == 8, ""); };       // native 32-byte form (option q3h_native)
+template <int NJ> struct DecFmt<Q5_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ5B64<NJ>; static constexpr int DW = dec_fmt_dw(Q5_B64T1); static_assert(DW == 11, ""); };
+template <int NJ> struct DecFmt<Q6_B64T1, NJ> { using X = XRegsB64<NJ>; using W = WRowQ6B64<NJ>; static constexpr int DW = dec_fmt_dw(Q6_B64T1); static_assert(DW == 13, ""); };
 
 // ------------------------------------------------------------- kernel params
-// EPI_MOE_ACC / EPI_MOE_LAST: y = hfma(product, w_expert, y) (AddByRowIdx_Kernel); LAST also adds the residual(s)
-// EPI_MOE_GLU / EPI_MOE_ACT: EPI_GLU / EPI_ACT of an expert.  Only the MOE epilogues contain the table lookup: a
-// run-time `if (P.w_table)` in the dense kernels cost them ~2 us each (weight pointers forced through VGPRs).
-enum DecEpilogue { EPI_PLAIN = 0, EPI_RESIDUAL = 1, EPI_GLU = 2, EPI_ACT = 3, EPI_MOE_ACC = 4, EPI_MOE_LAST = 5, EPI_MOE_GLU = 6, EPI_MOE_ACT = 7 };
-constexpr bool epi_is_moe(int epi) { return epi >= EPI_MOE_ACC; }
-constexpr bool epi_is_glu(int epi) { return epi == EPI_GLU || epi == EPI_MOE_GLU; }
+// (DecEpilogue, epi_is_moe, epi_is_glu: ifa_decode_gemv_plan.h)
 
 // Kernel arguments.  Kept under 256 bytes with the fields the prologue needs first: when the struct grew past 256 B
 // the kernels whose first instructions read the tail (xn_out, trace) started ~0.7 us later (second kernarg fetch).
@@ -570,7 +555,7 @@ __device__ __forceinline__ void dec_finish_row(const DecGemvParams &P, const Dec
 //   5. every wave reduces its RW rows as independent chains, then lane i finishes row i
 //      (bias / residual / activation) so the epilogue's loads overlap too.
 // TH = threads per workgroup: 512 (two waves per SIMD, 256 registers each) or 1024 (four waves per SIMD, 128 registers, half
-// the rows in flight per wave) -- chosen per kernel shape by the launcher (ifa_decode_gemv_impl.h)
+// the rows in flight per wave) -- chosen per kernel shape by the launch plan (ifa_decode_gemv_plan.h)
 // NP > 0: WAVE-SPECIALISED prologue (round 4).  Waves [0, NP) request the activation, run the norm + quantiser among
 // themselves (LDS counters, XPre<.., NT>) and only then request their rows; waves [NP, TH/64) request ALL their rows right
 // after the first barrier and wait for the image behind them.  In the classic form every wave takes part in the prologue's

@@ -13,7 +13,7 @@
 
 namespace ifa {
 
-constexpr int DH_ROWS = 2;       // rows (EPI_GLU: row pairs) per wave and pass
+constexpr int DH_ROWS = DEC_H_ROWS;       // rows (EPI_GLU: row pairs) per wave and pass
 
 template <int DT>
 struct HRow {
@@ -146,18 +146,21 @@ __global__ void __launch_bounds__(DEC_THREADS) k_dec_gemv_h(const DecGemvParams 
 
 bool dec_gemv_h_supported(int w_dtype, size_t cols)
 {
-    if (w_dtype == F32 || cols == 0 || cols > 32768 || cols % 8 != 0) return false;
-    const int cap = block_capacity(w_dtype);
-    return cap > 0 && cols % (size_t)cap == 0;
+    return dec_gemv_h_cols_ok(w_dtype, cols);
 }
 
+DecGemvPlan dec_gemv_h_plan(const DecGemvFacts &f) { return plan_dec_gemv_h(f); }
+
+// grid and LDS bytes from the plan (plan_dec_gemv_h)
 template <int DT, int EPI, int NORM, bool XADD>
 static int launch_h(const DecGemvParams &P, hipStream_t s)
 {
-    const size_t smem = (((size_t)P.cols * 2 + 15) & ~(size_t)15) + 132 * 4;
-    const int per_wg = DEC_WAVES * DH_ROWS;
-    int wgs = std::min(dec_num_cus() * 2, (P.total_rows + per_wg - 1) / per_wg);
-    if (wgs < 1) wgs = 1;
+    DecGemvFacts F;
+    F.dtype = DT; F.epi = EPI; F.norm = NORM; F.x_add = XADD; F.cols = P.cols; F.total_rows = P.total_rows; F.num_cus = dec_num_cus();
+    const DecGemvPlan R = plan_dec_gemv_h(F);
+    if (R.error) return ifa_fail(IFA_ERR_ARG, "fused fp16-activation GEMV: dtype %d with %d columns is not supported", DT, P.cols);
+    const size_t smem = (size_t)R.lds;
+    const int wgs = R.grid;
     auto kern = k_dec_gemv_h<DT, EPI, NORM, XADD>;
     if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     kern<<<dim3((unsigned)wgs), dim3(DEC_THREADS), smem, s>>>(P);

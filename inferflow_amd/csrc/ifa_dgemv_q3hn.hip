@@ -3,7 +3,7 @@
 #include "ifa_decode_gemv_impl.h"
 namespace ifa {
 
-template int dec_gemv_launch_dt<Q3H_NATIVE>(int, int, const DecGemvParams &, int, hipStream_t);
+template int dec_gemv_launch_dt<Q3H_NATIVE>(int, int, const DecGemvParams &, int, hipStream_t); template DecGemvPlan dec_gemv_plan_dt<Q3H_NATIVE>(const DecGemvFacts &);
 
 // reference-layout rows (32-byte blocks {base, scale, data_h[4], data_m[8], data[16]}) -> [D0..D3][D4, D5][D6, (base, scale)] planes
 __global__ void __launch_bounds__(256) k_q3h_native_rows(const uint8_t *__restrict__ aos, int rows, int nblk, uint8_t *__restrict__ dst)

@@ -3,7 +3,7 @@
 
 namespace ifa {
 
-template int dec_gemv_launch_dt<Q4_B32T1A>(int, int, const DecGemvParams &, int, hipStream_t);
+template int dec_gemv_launch_dt<Q4_B32T1A>(int, int, const DecGemvParams &, int, hipStream_t); template DecGemvPlan dec_gemv_plan_dt<Q4_B32T1A>(const DecGemvFacts &);
 
 static int g_num_cus = 0;
 int dec_num_cus()
@@ -40,6 +40,35 @@ bool dec_gemv_supported_long(int w_dtype, size_t cols)
     if (mnj == 0 || cols == 0 || cols > 32768) return false;
     const size_t cap = (size_t)block_capacity(w_dtype);
     return cols % cap == 0 && cols / cap <= (size_t)(64 * mnj * 4);
+}
+
+// (the other formats' launchers and plans live in their own units: never instantiated here, where they would read this unit's IFA_T_*
+//  overrides and be second, weak copies of the ones the linker has already)
+extern template int dec_gemv_launch_dt<Q8_B32T2>(int, int, const DecGemvParams &, int, hipStream_t);
+extern template int dec_gemv_launch_dt<Q4_B64T1>(int, int, const DecGemvParams &, int, hipStream_t);
+extern template int dec_gemv_launch_dt<Q3H_B64T1>(int, int, const DecGemvParams &, int, hipStream_t);
+extern template int dec_gemv_launch_dt<Q3H_NATIVE>(int, int, const DecGemvParams &, int, hipStream_t);
+extern template int dec_gemv_launch_dt<Q5_B64T1>(int, int, const DecGemvParams &, int, hipStream_t);
+extern template int dec_gemv_launch_dt<Q6_B64T1>(int, int, const DecGemvParams &, int, hipStream_t);
+extern template DecGemvPlan dec_gemv_plan_dt<Q8_B32T2>(const DecGemvFacts &);
+extern template DecGemvPlan dec_gemv_plan_dt<Q4_B64T1>(const DecGemvFacts &);
+extern template DecGemvPlan dec_gemv_plan_dt<Q3H_B64T1>(const DecGemvFacts &);
+extern template DecGemvPlan dec_gemv_plan_dt<Q3H_NATIVE>(const DecGemvFacts &);
+extern template DecGemvPlan dec_gemv_plan_dt<Q5_B64T1>(const DecGemvFacts &);
+extern template DecGemvPlan dec_gemv_plan_dt<Q6_B64T1>(const DecGemvFacts &);
+
+DecGemvPlan dec_gemv_plan(const DecGemvFacts &f)
+{
+    switch (f.dtype) {
+    case Q4_B32T1A: case Q4_B32T1B: return dec_gemv_plan_dt<Q4_B32T1A>(f);   // same bytes, same arithmetic
+    case Q8_B32T2: return dec_gemv_plan_dt<Q8_B32T2>(f);
+    case Q4_B64T1: return dec_gemv_plan_dt<Q4_B64T1>(f);
+    case Q3H_B64T1: return dec_gemv_plan_dt<Q3H_B64T1>(f);
+    case Q3H_NATIVE: return dec_gemv_plan_dt<Q3H_NATIVE>(f);
+    case Q5_B64T1: return dec_gemv_plan_dt<Q5_B64T1>(f);
+    case Q6_B64T1: return dec_gemv_plan_dt<Q6_B64T1>(f);
+    default: return dec_gemv_h_plan(f);
+    }
 }
 
 int dec_gemv_launch(int w_dtype, int epi, int norm, const DecGemvParams &P0, int wgs_per_cu, hipStream_t s, long long *trace)

@@ -230,6 +230,59 @@ int decode_route_ready(ifa_model *m, int reach, bool own_launches)
     return IFA_OK;
 }
 
+// What the single GEMV launch of a role is -- the kernel format, the epilogue and the prologue -- as ONE definition for the launches
+// below and for the plan the tests ask for (gemv_plan_of): the two cannot drift apart.
+struct GemvRole { int dtype, epi, norm; };
+
+// option q3h_native: the kernel format of a tensor that has its 32-byte-per-block copy (ensure_q3hn)
+static int native_dtype(const ifa_model *m, const Tensor &t) { return (m->opt_q3h_native && t.q3hn && t.dtype == Q3H_B64T1) ? (int)Q3H_NATIVE : t.dtype; }
+
+// QKV: the RMS norm in the prologue, or none behind the op-level std norm; wq's format (q / k / v of mixed formats: one launch each)
+static GemvRole qkv_role(const ifa_model *m, const Layer &L) { return {L.t[T_WQ].dtype, EPI_PLAIN, m->cfg.norm_kind != 0 ? 0 : 1}; }
+
+// Wo: norm 2 where the attention kernel left its output quantised (XqImage) and the row fits a lane's register image -- the chunked
+// kernel keeps the in-kernel quantiser; no residual for a partial product and with parallel attention / a shared input (the residual
+// is added once, after the FFN -- inference_worker.cc:847-851)
+static GemvRole wo_role(const ifa_model *m, const Layer &L, bool partial)
+{
+    const ifa_model_config &c = m->cfg;
+    const Tensor &wo = L.t[T_WO];
+    const bool preq = m->attq && m->opt_attn_q8 && c.head_dim % 32 == 0 && (int)wo.cols == c.heads * c.head_dim && fused_int8(wo.dtype)
+        && dec_gemv_supported(wo.dtype, wo.cols);
+    const bool plain = partial || c.parallel_attn || c.share_input;
+    return {native_dtype(m, wo), plain ? EPI_PLAIN : EPI_RESIDUAL, preq ? 2 : 0};
+}
+
+// dense W1 | W3: gated or plain activation; the FFN pre-norm in the prologue unless the model has none or it is the op-level std norm;
+// both matrices of a pair in the native form, or neither
+static GemvRole ffn13_role(const ifa_model *m, const Layer &L)
+{
+    const Tensor &w1 = L.t[T_W1], &w3 = L.t[T_W3];
+    const bool glu = w3.present();
+    const bool need_norm = L.t[T_FFN_NORM].present() && m->cfg.norm_kind == 0;
+    const int dtw = (m->opt_q3h_native && w1.q3hn && (!glu || w3.q3hn)) ? native_dtype(m, w1) : w1.dtype;
+    return {dtw, glu ? EPI_GLU : EPI_ACT, need_norm ? 1 : 0};
+}
+
+// dense W2: the in-kernel quantiser, the residual(s) unless the product is a partial one
+static GemvRole w2_role(const ifa_model *m, const Layer &L, bool partial) { return {native_dtype(m, L.t[T_W2]), partial ? EPI_PLAIN : EPI_RESIDUAL, 0}; }
+
+// the instance of a role (the combinations the roles above can name)
+static int launch_role(const GemvRole &R, const DecGemvParams &P, int wgs_per_cu_opt, hipStream_t s)
+{
+    const int e = R.epi, n = R.norm;
+    if (e == EPI_PLAIN && n == 1) return launch_dec_gemv<EPI_PLAIN, 1>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_PLAIN && n == 0) return launch_dec_gemv<EPI_PLAIN, 0>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_PLAIN && n == 2) return launch_dec_gemv<EPI_PLAIN, 2>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_RESIDUAL && n == 0) return launch_dec_gemv<EPI_RESIDUAL, 0>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_RESIDUAL && n == 2) return launch_dec_gemv<EPI_RESIDUAL, 2>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_GLU && n == 1) return launch_dec_gemv<EPI_GLU, 1>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_GLU && n == 0) return launch_dec_gemv<EPI_GLU, 0>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_ACT && n == 1) return launch_dec_gemv<EPI_ACT, 1>(R.dtype, P, wgs_per_cu_opt, s);
+    if (e == EPI_ACT && n == 0) return launch_dec_gemv<EPI_ACT, 0>(R.dtype, P, wgs_per_cu_opt, s);
+    return ifa_fail(IFA_ERR_STATE, "fused GEMV: no launch for epilogue %d / norm %d", e, n);
+}
+
 void qkv_params(ifa_model *m, int l, const half_t *x, DecGemvParams &P)
 {
     const ifa_model_config &c = m->cfg;
@@ -277,10 +330,8 @@ int launch_qkv(ifa_model *m, int l, const half_t *x)
         P.x = m->pend.x; P.x_add = m->pend.add; P.x_add_bias = m->pend.bias; P.xsum_out = m->pend.out;
         m->pend.on = false;
     }
-    auto go = [&](int dtype, const DecGemvParams &Q) {
-        if (std_norm) return launch_dec_gemv<EPI_PLAIN, 0>(dtype, Q, m->opt_rpw_qkv, m->stream);
-        return launch_dec_gemv<EPI_PLAIN, 1>(dtype, Q, m->opt_rpw_qkv, m->stream);
-    };
+    const GemvRole R = qkv_role(m, L);
+    auto go = [&](int dtype, const DecGemvParams &Q) { return launch_role(GemvRole{dtype, R.epi, R.norm}, Q, m->opt_rpw_qkv, m->stream); };
     if (same_fmt(L.t[T_WQ].dtype, L.t[T_WK].dtype) && same_fmt(L.t[T_WQ].dtype, L.t[T_WV].dtype)) return go(L.t[T_WQ].dtype, P);
     // mixed formats (e.g. wq quantised, wk / wv left F16 by the threshold rule): one launch per matrix; the first one forms
     // a pending sum, the others read the stored result
@@ -353,14 +404,6 @@ int launch_attn(ifa_model *m, int l)
     });
 }
 
-// partial != nullptr (tensor parallel): write the un-merged product there, no bias, no residual
-// option q3h_native: the launch's matrix and kernel format when the tensor has its 32-byte-per-block copy (ensure_q3hn)
-static int native_fmt(const ifa_model *m, const Tensor &t, const uint8_t *&w)
-{
-    if (m->opt_q3h_native && t.q3hn && t.dtype == Q3H_B64T1) { w = (const uint8_t *)t.q3hn; return Q3H_NATIVE; }
-    return t.dtype;
-}
-
 // Wo over the attention output.  partial: the un-merged product goes there (no bias, no residual); else a = Wo att (+ bias) with the
 // layer input x as the residual operand
 void wo_params(ifa_model *m, int l, const half_t *x, half_t *partial, DecGemvParams &P)
@@ -379,16 +422,10 @@ int launch_wo(ifa_model *m, int l, const half_t *x, half_t *partial)
 {
     Layer &L = m->layers[(size_t)l];
     DecGemvParams P; wo_params(m, l, x, partial, P);
-    // the attention kernel left its output quantised (XqImage): the GEMV needs no prologue.  Rows longer than a lane's
-    // register image (chunked kernel) keep the in-kernel quantiser
-    const bool preq = m->attq && m->opt_attn_q8 && m->cfg.head_dim % 32 == 0 && P.cols == m->cfg.heads * m->cfg.head_dim && fused_int8(L.t[T_WO].dtype)
-        && dec_gemv_supported(L.t[T_WO].dtype, (size_t)P.cols);
-    if (preq) P.x = reinterpret_cast<const half_t *>(m->attq.get());      // NORM == 2 kernels read the quantised image through P.x
-    const int dto = native_fmt(m, L.t[T_WO], P.W0[0]);
-    // (parallel attention / shared input: the residual is added once, after the FFN -- inference_worker.cc:847-851)
-    const bool plain = partial || m->cfg.parallel_attn || m->cfg.share_input;
-    if (preq) return plain ? launch_dec_gemv<EPI_PLAIN, 2>(dto, P, m->opt_rpw_wo, m->stream) : launch_dec_gemv<EPI_RESIDUAL, 2>(dto, P, m->opt_rpw_wo, m->stream);
-    return plain ? launch_dec_gemv<EPI_PLAIN, 0>(dto, P, m->opt_rpw_wo, m->stream) : launch_dec_gemv<EPI_RESIDUAL, 0>(dto, P, m->opt_rpw_wo, m->stream);
+    const GemvRole R = wo_role(m, L, partial != nullptr);
+    if (R.norm == 2) P.x = reinterpret_cast<const half_t *>(m->attq.get());      // NORM == 2 kernels read the quantised image through P.x
+    if (R.dtype == Q3H_NATIVE) P.W0[0] = (const uint8_t *)L.t[T_WO].q3hn;
+    return launch_role(R, P, m->opt_rpw_wo, m->stream);
 }
 
 void moe_params(ifa_model *m, Layer &L, DecGemvParams &P, int slot, int tab_off)
@@ -441,26 +478,23 @@ int launch_ffn13(ifa_model *m, int l, int moe_slot, const half_t *x_layer, int m
     // FFN input (inference_worker.cc:853-872): the attention's normalised input (parallel attention), the layer input
     // (shared input) or the attention output + residual; then the FFN pre-norm if the model has one
     const half_t *ff_in = c.parallel_attn ? m->xn : (c.share_input ? x_layer : m->a);
-    bool need_norm = L.t[T_FFN_NORM].present();
+    const GemvRole R = ffn13_role(m, L);
     P.x = ff_in;
-    if (need_norm && c.norm_kind != 0) {
+    if (L.t[T_FFN_NORM].present() && c.norm_kind != 0) {
         int rc = sep_norm(m, ff_in, L.t[T_FFN_NORM], L.t[T_FFN_NORM_B], m->hn);
         if (rc) return rc;
-        P.x = m->hn; need_norm = false;
+        P.x = m->hn;
     }
-    if (!need_norm) { P.norm_w = nullptr; P.norm_b = nullptr; }
-    const bool glu = L.t[T_W3].present();
-    int dtw = L.t[T_W1].dtype;
-    if (m->opt_q3h_native && L.t[T_W1].q3hn && (!glu || L.t[T_W3].q3hn)) {      // both matrices of the pair in the native form, or neither
-        dtw = native_fmt(m, L.t[T_W1], P.W0[0]);
-        if (glu) (void)native_fmt(m, L.t[T_W3], P.W1);
+    if (R.norm == 0) { P.norm_w = nullptr; P.norm_b = nullptr; }
+    if (R.dtype == Q3H_NATIVE) {
+        P.W0[0] = (const uint8_t *)L.t[T_W1].q3hn;
+        if (L.t[T_W3].present()) P.W1 = (const uint8_t *)L.t[T_W3].q3hn;
     }
-    if (need_norm && m->pend.on && P.x == m->pend.out) {     // the FFN input is the pending sum
+    if (R.norm == 1 && m->pend.on && P.x == m->pend.out) {     // the FFN input is the pending sum
         P.x = m->pend.x; P.x_add = m->pend.add; P.x_add_bias = m->pend.bias; P.xsum_out = m->pend.out;
         m->pend.on = false;
     }
-    if (need_norm) return glu ? launch_dec_gemv<EPI_GLU, 1>(dtw, P, m->opt_rpw_ffn, m->stream) : launch_dec_gemv<EPI_ACT, 1>(dtw, P, m->opt_rpw_ffn, m->stream);
-    return glu ? launch_dec_gemv<EPI_GLU, 0>(dtw, P, m->opt_rpw_ffn, m->stream) : launch_dec_gemv<EPI_ACT, 0>(dtw, P, m->opt_rpw_ffn, m->stream);
+    return launch_role(R, P, m->opt_rpw_ffn, m->stream);
 }
 
 // dense W2 over t1.  partial: the un-merged product goes there; else xnext = W2 t1 (+ bias) + a (+ residual2, the layer input of
@@ -500,8 +534,9 @@ int launch_w2(ifa_model *m, int l, half_t *xnext, half_t *partial, int moe_slot,
         return launch_dec_gemv<EPI_MOE_ACC, 0>(e2.dtype, P, m->opt_rpw_w2, m->stream);
     }
     w2_params(m, l, xnext, partial, residual2, P);
-    const int dt2 = native_fmt(m, L.t[T_W2], P.W0[0]);
-    return partial ? launch_dec_gemv<EPI_PLAIN, 0>(dt2, P, m->opt_rpw_w2, m->stream) : launch_dec_gemv<EPI_RESIDUAL, 0>(dt2, P, m->opt_rpw_w2, m->stream);
+    const GemvRole R = w2_role(m, L, partial != nullptr);
+    if (R.dtype == Q3H_NATIVE) P.W0[0] = (const uint8_t *)L.t[T_W2].q3hn;
+    return launch_role(R, P, m->opt_rpw_w2, m->stream);
 }
 
 // [Wo ->] W1 | W3 -> W2 of layer l as ONE launch (ifa_decode_chain.h); x = the layer input (Wo's residual), xnext = the layer output
@@ -658,9 +693,78 @@ int enqueue_fused_step(ifa_model *m, int tail)
     return IFA_OK;
 }
 
+// What the single GEMV launch of (layer, role) would run if the step were enqueued now (ifa_decode_gemv_plan.h), from the tensors, the
+// options and num_cus, through the role helpers launch_qkv / launch_wo / launch_ffn13 / launch_w2 use.  The route is planned here under
+// the options of NOW for the last call's reach: m->route is what the LAST call planned and stays until the next one.  out: the DecGemvPlan fields, then
+// single (0: the step would not run this launch on its own -- the fused QKV + attention tail, the chained FFN launch, an MoE layer's
+// expert launches or the op-by-op step take its place), dtype, epi, norm, cols, total_rows, num_cus, launches (3: q / k / v of mixed
+// formats, one launch each -- the plan is wq's).
+static int gemv_plan_of(ifa_model *m, int l, int role, int *out)
+{
+    const ifa_model_config &c = m->cfg;
+    const Layer &L = m->layers[(size_t)l];
+    const DecRoute R = plan_decode_route(route_facts(m, std::max(1, m->route_reach), false));
+    const bool moe = c.experts > 0 && L.t[T_MOE_GATE].present();
+    DecGemvFacts f;
+    f.num_cus = num_cus();
+    int single = m->opt_fused && fused_supported(m, nullptr), launches = 1;
+    GemvRole G;
+    if (role == 0) {
+        const Tensor &wq = L.t[T_WQ], &wk = L.t[T_WK], &wv = L.t[T_WV];
+        const bool same = same_fmt(wq.dtype, wk.dtype) && same_fmt(wq.dtype, wv.dtype);
+        G = qkv_role(m, L);
+        f.cols = c.dim; f.rpw = m->opt_rpw_qkv;
+        f.total_rows = (int)(same ? wq.rows + wk.rows + wv.rows : wq.rows);
+        launches = same ? 1 : 3;
+        single = single && R.kind != DEC_ROUTE_FUSED_TAIL;
+    } else if (role == 1) {
+        G = wo_role(m, L, false);
+        f.cols = (int)L.t[T_WO].cols; f.total_rows = (int)L.t[T_WO].rows; f.rpw = m->opt_rpw_wo;
+        single = single && R.chain != 2;
+    } else if (role == 2) {
+        G = ffn13_role(m, L);
+        f.cols = c.dim; f.total_rows = (int)L.t[T_W1].rows; f.rpw = m->opt_rpw_ffn;
+        single = single && R.chain == 0 && !moe;
+    } else {
+        G = w2_role(m, L, false);
+        f.cols = (int)L.t[T_W2].cols; f.total_rows = (int)L.t[T_W2].rows; f.rpw = m->opt_rpw_w2;
+        single = single && R.chain == 0 && !moe;
+    }
+    f.dtype = G.dtype; f.epi = G.epi; f.norm = G.norm;
+    const DecGemvPlan P = dec_gemv_plan(f);
+    memcpy(out, &P, sizeof(P));
+    int *x = out + DEC_GEMV_N_OUT;
+    x[0] = single ? 1 : 0; x[1] = f.dtype; x[2] = f.epi; x[3] = f.norm; x[4] = f.cols; x[5] = f.total_rows; x[6] = f.num_cus; x[7] = launches;
+    return IFA_OK;
+}
+
 } // namespace ifae
 
 extern "C" {
+
+// the decode GEMV launch plan (ifa_decode_gemv_plan.h) for tests: the pure function (no device is touched), and a model's launches
+int ifa_decode_gemv_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    IFA_REQUIRE(facts && out && n_facts == DEC_GEMV_N_FACTS && n_out >= DEC_GEMV_N_OUT, "ifa_decode_gemv_plan: %d facts, %d outputs expected", DEC_GEMV_N_FACTS, DEC_GEMV_N_OUT);
+    DecGemvFacts f;
+    memcpy(&f, facts, sizeof(f));
+    IFA_REQUIRE(f.num_cus >= 1 && f.total_rows >= 1, "ifa_decode_gemv_plan: num_cus %d, total_rows %d", f.num_cus, f.total_rows);
+    const DecGemvPlan r = dec_gemv_plan(f);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
+int ifa_model_gemv_plan(ifa_model *m, int layer, int role, int *out, int n_out)
+{
+    IFA_REQUIRE(m && m->finalized && out && n_out >= DEC_GEMV_N_OUT + 8, "ifa_model_gemv_plan: a finalized model and %d outputs expected", DEC_GEMV_N_OUT + 8);
+    IFA_REQUIRE(layer >= 0 && layer < m->cfg.layers && role >= 0 && role <= 3, "ifa_model_gemv_plan: layer %d, role %d (0 qkv, 1 wo, 2 ffn13, 3 w2)", layer, role);
+    const Layer &L = m->layers[(size_t)layer];
+    const bool have = role == 0 ? (L.t[T_WQ].present() && L.t[T_WK].present() && L.t[T_WV].present()) : role == 1 ? L.t[T_WO].present()
+        : role == 2 ? L.t[T_W1].present() : L.t[T_W2].present();      // (a mixture-of-experts layer has qkv and wo, no dense w1 / w2)
+    IFA_REQUIRE(have, "ifa_model_gemv_plan: layer %d has no dense matrix for role %d", layer, role);
+    IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
+    return gemv_plan_of(m, layer, role, out);
+}
 
 int ifa_model_decode(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms)
 {

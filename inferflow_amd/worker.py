@@ -280,6 +280,20 @@ class DecodeWorker:
         d["kind"] = self.ROUTE_KINDS[d["kind"]]
         return d
 
+    GEMV_PLAN_FIELDS = ("kind", "nj", "nchunk", "njl", "rw", "threads", "np", "grid", "waves", "npass", "partial", "lds", "error")
+    GEMV_MODEL_FIELDS = GEMV_PLAN_FIELDS + ("single", "dtype", "epi", "norm", "cols", "total_rows", "num_cus", "launches")
+    GEMV_KINDS = ("none", "classic", "long", "f16x")
+    GEMV_ROLES = ("qkv", "wo", "ffn13", "w2")
+
+    def gemv_plan(self, layer, role):
+        """what the fused GEMV launch of `role` (one of GEMV_ROLES) of a layer would run if the step were enqueued now
+        (csrc/ifa_decode_gemv_plan.h) as a dict; kind as one of GEMV_KINDS; single = 0: the step would not run this launch on its own"""
+        out = (C.c_int * len(self.GEMV_MODEL_FIELDS))()
+        check(lib().ifa_model_gemv_plan(self._h, int(layer), self.GEMV_ROLES.index(role), out, len(out)))
+        d = dict(zip(self.GEMV_MODEL_FIELDS, out))
+        d["kind"] = self.GEMV_KINDS[d["kind"]]
+        return d
+
     PROMPT_ROUTE_FIELDS = ("kind", "first_pass", "norm_fused", "res_mid") + tuple(
         p + "_" + k for p in ("qkv", "wo", "w13", "w2") for k in ("kernel", "src", "mo", "no_waits")) + ("need_mo", "need_x32")
     PROMPT_ROUTE_KINDS = ("exact", "op_by_op", "rows", "mid", "big")
@@ -397,6 +411,16 @@ def topk_pool(logits, k, excluded_bits=None, stream=None):
                               C.c_void_p(excluded_bits.data_ptr()) if excluded_bits is not None else None,
                               C.c_void_p(ids.data_ptr()), C.c_void_p(vals.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(stream)))
     return ids, vals, cnt
+
+
+def gemv_plan(dtype, epi, norm, cols, total_rows, num_cus=256, rpw=0, x_add=0):
+    """ifa_decode_gemv_plan: the pure launch plan of the fused decode GEMV (no device) as a dict of DecodeWorker.GEMV_PLAN_FIELDS"""
+    facts = (C.c_int * 8)(int(dtype), int(epi), int(norm), int(x_add), int(cols), int(total_rows), int(num_cus), int(rpw))
+    out = (C.c_int * len(DecodeWorker.GEMV_PLAN_FIELDS))()
+    check(lib().ifa_decode_gemv_plan(facts, 8, out, len(out)))
+    d = dict(zip(DecodeWorker.GEMV_PLAN_FIELDS, out))
+    d["kind"] = DecodeWorker.GEMV_KINDS[d["kind"]]
+    return d
 
 
 def rng_state_of_seed(seed):

@@ -3,7 +3,7 @@
 
   build (here, no GPU):   python tools/sweep_variants.py build  [name=FLAGS ...]
         one library per variant under gpurun_out_variants/<name>/libinferflow_amd.so: only csrc/ifa_dgemv_q4b32.hip
-        is recompiled with the -DIFA_T_* overrides of ifa_decode_gemv_impl.h, the other objects come from lib/obj
+        is recompiled with the -DIFA_T_* overrides of ifa_decode_gemv_plan.h, the other objects come from lib/obj
   run   (GPU box):        python tools/sweep_variants.py run [--steps 96]
         bench.py once per variant (IFA_LIB=...), one summary line each -> gpurun_out/sweep.jsonl
 """
