@@ -687,6 +687,20 @@ int ifa_batch_route_plan(const int *facts, int n_facts, int *out, int n_out);
  * shows first_pass 32 and the first pass's route.  Plans nothing, allocates nothing. */
 int ifa_model_prompt_route(ifa_model *m, int *out, int n_out);
 
+/* The launch plans of the prompt GEMMs (csrc/ifa_gemm_plan.h, DESIGN.md "Prompt GEMM launch plans").  Host-only, no GPU needed.
+ * k_gemm_mid: facts[18], in the order of GemmMidFacts: T, nsets, rows0, rows1, rows2, nblk (32-weight blocks per row), epi (0 plain,
+ * 1 residual, 2 gated pair), num_cus, no_waits, waits_on, then the measurement settings (0 = default) max_parts, ta, min_steps, two_per_cu,
+ * no_glu_split, then mo, has_w1, ld_or (the strides read, or-ed).  out[25], in the order of GemmMidPlan: error (0 ok, 1 not an MO copy,
+ * 2 shape, 3 rows % 16, 4 gated pair without one set and W3, 5 a stride % 8), ta, tiles_m, tiles_n, tile0[4], ksteps, n_try, then
+ * parts[5], grid[5], lds[5] of the candidates in the order they are tried (the next one when a waiting grid cannot be resident).
+ * k_gemm_big: facts[14], in the order of GemmBigFacts: T, nsets, rows0, rows1, rows2, nblk (blocks per row), dtype, epi, tiles_bits (the
+ * value of ifa_gemm_big_tiles), num_cus, no_waits, waits_on, has_w1, ld_or.  out[23], in the order of GemmBigPlan: error (0 ok, 1 format,
+ * 2 shape, 3 fused epilogue on another format than Q4_B32T1A / B, 4 gated pair, 5 rows % 8, 6 a stride % 8), pick (1 256 x 256, 2 128 x
+ * 256, 3 128 x 128, 4 - 6 the small tiles), stream_k, n_launch, then (bm, bn, waves, tn0, tn_count, tiles_m, lds) of the two launches,
+ * full_n, rem_n, n_try, ks[2] (parts of K in the order they are tried). */
+int ifa_gemm_mid_plan(const int *facts, int n_facts, int *out, int n_out);
+int ifa_gemm_big_plan(const int *facts, int n_facts, int *out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,8 @@ SIGNATURES = {
     "ifa_prompt_route_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_batch_route_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_model_prompt_route": (_i, [_vp, _vp, _i]),
+    "ifa_gemm_mid_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_gemm_big_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_model_set_stream": (_i, [_vp, _vp]),
     "ifa_model_tp_begin": (_i, [_vp, _i, _i]),
     "ifa_model_tp_begin_hidden": (_i, [_vp, _vp, _i]),

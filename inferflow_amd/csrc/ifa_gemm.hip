@@ -885,15 +885,9 @@ static int launch_gemm_big(const GmArgs &P0, hipStream_t s)
     using std::integral_constant;
     typedef integral_constant<int, 256> I256; typedef integral_constant<int, 128> I128; typedef integral_constant<int, 2> I2; typedef integral_constant<int, 4> I4; typedef integral_constant<int, 64> K64;
     typedef integral_constant<int, 1> S1;
-    const int force = (g_gemm_big >> 8) & 7;        // (measurement: 1 / 2 / 3 force a tile shape; 4 / 5 / 6: the small tiles below)
-    auto rounds = [&](size_t bm, size_t bn, size_t per_cu) { return (double)ifa_cdiv(ifa_cdiv(T, bm) * ntiles(bn), cus * per_cu); };
-    // 256 x 256: whole rounds of the chip; what is left of the last round goes to a second launch of 128-token tiles when
-    // those fit the chip in one go (1024 tokens x 11008 GLU pairs: 86 weight tiles = 64 x 4 workgroups + 22 x 8)
-    const size_t tm256 = ifa_cdiv(T, (size_t)256), tn256 = ntiles(256), per_round = tm256 <= cus ? cus / tm256 : 0;
-    const size_t full_n = per_round ? (tn256 / per_round) * per_round : 0, rem_n = tn256 - full_n;
-    const bool split = full_n > 0 && rem_n > 0 && ifa_cdiv(T, (size_t)128) * rem_n <= cus && tm256 * rem_n < cus * 3 / 4;
-    const size_t n128 = ifa_cdiv(T, (size_t)128) * ntiles(128);
-    double c256 = CAP > 32 ? 1e30 : (split ? (double)(full_n / per_round) + 0.68 : rounds(256, 256, 1));   // (64-value blocks: the 256 x 256 variant would spill)
+    // The choice (plan_gemm_big, ifa_gemm_plan.h): tile shape by estimated time -- rounds of workgroups over the chip x the measured cost of
+    // one round.  256 x 256: whole rounds of the chip; what is left of the last round goes to a second launch of 128-token tiles when
+    // those fit the chip in one go (1024 tokens x 11008 GLU pairs: 86 weight tiles = 64 x 4 workgroups + 22 x 8).
     // Round 6, stream-K on the 256 x 256 tiles (k_gemm_big<.., KS = 0>; OPT-IN, bit 13 of ifa_gemm_big_tiles): every CU takes
     // floor(tiles / CUs) whole tiles and then an equal share of the K steps of the rest.  Built, deterministic, within the F16 rounding of
     // the whole-tile kernel -- and measured SLOWER on the two products it was built for (1024-token prompt, Llama-2-7B Q4, one box,
@@ -903,58 +897,44 @@ static int launch_gemm_big(const GmArgs &P0, hipStream_t s)
     // memory (write-through stores, 64 MB per launch) and the share that ends the tile reads up to three of them -- MI355X_MICROARCH.md
     // prices that at ~12 us out + 4 us per slot in on an idle chip, here it costs 50-65.  Eligible when a share is >= 20 steps (<= 3
     // scratch slots per shared tile at K = 4096).  profiles/r06_stream_k_ab.log.
-    bool sk = false;
-    {
-        const size_t tiles = tm256 * tn256, S = (size_t)P.nblk * CAP / PF_BK, rem = tiles % cus, share = rem * S / cus;
-        const bool may_sk = !force && CAP <= 32 && (g_gemm_big & (1 << 13)) != 0 && !P.no_waits && waits_enabled() && tiles * 4 >= cus * 3;
-        if (may_sk && rem && share >= 20 && ifa_cdiv(S - 1, share) <= 3) {
-            const double csk = (double)(tiles / cus) + (double)rem / (double)cus + 0.10;
-            if (csk < c256) { c256 = csk; sk = true; }
-        }
-    }
-    const double c128x256 = rounds(128, 256, 1) * 0.68;
-    const double c128 = n128 <= cus ? 0.41 : rounds(128, 128, 2) * 0.75;
-    int pick = force;
-    if (!pick) pick = (c256 <= c128x256 && c256 <= c128) ? 1 : (c128x256 <= c128 ? 2 : 3);
+    const GemmBigPlan plan = plan_gemm_big(gemm_big_facts(DT, P, EPI));
+    if (plan.error) return ifa_fail(IFA_ERR_ARG, "large-tile GEMM: plan error %d", plan.error);
+    const GemmBigLaunch &L0 = plan.launch[0], &L1 = plan.launch[1];
     int rc = IFA_OK;
     typedef integral_constant<int, 64> I64;
-    if (pick == 4 && CAP <= 32) rc = run(I64(), I64(), I2(), I2(), 0, (int)ntiles(64), K64(), S1());
-    else if (pick == 5 && CAP <= 32) rc = run(I128(), I64(), I2(), I2(), 0, (int)ntiles(64), K64(), S1());
-    else if (pick == 6 && CAP <= 32) rc = run(I64(), I128(), I2(), I2(), 0, (int)ntiles(128), K64(), S1());
-    else if (pick == 1 && CAP <= 32) {
+    if (L0.bm == 64 && L0.bn == 64) rc = run(I64(), I64(), I2(), I2(), L0.tn0, L0.tn_count, K64(), S1());
+    else if (L0.bm == 128 && L0.bn == 64) rc = run(I128(), I64(), I2(), I2(), L0.tn0, L0.tn_count, K64(), S1());
+    else if (L0.bm == 64 && L0.bn == 128) rc = run(I64(), I128(), I2(), I2(), L0.tn0, L0.tn_count, K64(), S1());
+    else if (L0.bm == 256) {
         rc = 1;
-        if (sk) rc = run(I256(), I256(), I2(), I4(), 0, (int)tn256, K64(), integral_constant<int, 0>());
+        if (plan.stream_k) rc = run(I256(), I256(), I2(), I4(), 0, L0.tn_count + (plan.n_launch == 2 ? L1.tn_count : 0), K64(), integral_constant<int, 0>());
         if (rc != 1) { /* stream-K launched (or failed for another reason than residency) */ }
-        else if (split && !force) {
-            rc = run(I256(), I256(), I2(), I4(), 0, (int)full_n, K64(), S1());
-            if (!rc) rc = run(I128(), I256(), I2(), I4(), (int)full_n, (int)rem_n, K64(), S1());
-        } else rc = run(I256(), I256(), I2(), I4(), 0, (int)tn256, K64(), S1());
-    } else if (pick == 2 || pick == 1)
-        rc = run(I128(), I256(), I2(), I4(), 0, (int)tn256, K64(), S1());
+        else {
+            rc = run(I256(), I256(), I2(), I4(), L0.tn0, L0.tn_count, K64(), S1());
+            if (!rc && plan.n_launch == 2) rc = run(I128(), I256(), I2(), I4(), L1.tn0, L1.tn_count, K64(), S1());
+        }
+    } else if (L0.bn == 256)
+        rc = run(I128(), I256(), I2(), I4(), L0.tn0, L0.tn_count, K64(), S1());
     else {
         // 128 x 128 tiles that fill no more than one workgroup slot per CU (two fit): both halves of K at once -- only for products
         // big enough to matter (>= half the chip), never when a tile shape is forced (measurement / the bit-identity tests).
         // Llama-2-7B prefill: 1024 tokens 51.4K -> 54.2K tok/s, 768: 40.4K -> 44.2K, 512: 35.1K -> 42.4K.  (256 x 256 tiles split four
         // ways -- the efficient tile shape, one part per CU -- measured no better: 53.2K at 1024 tokens, three partial tiles through memory.)
-        const bool may_split = !force && EPI != GM_GLU && (g_gemm_big & (1 << 12)) == 0 && !P.no_waits && waits_enabled();
-        const size_t ksteps = (size_t)P.nblk * CAP / PF_BK;
-        const bool splitk = may_split && n128 <= cus && n128 * 2 >= cus && ksteps % 2 == 0 && P.nblk * CAP >= 2048;
         // Round 5, prompts of 48..128 tokens (ONE token tile; the engine sends them here from `prefill_big_min` + 1 tokens on): wq | wk | wv
         // are 96 tiles, wo and w2 32 -- a quarter or an eighth of the chip.  Four parts of K per tile when that still fits two
         // workgroups per CU and a part keeps >= 1024 columns: 64 tokens 7.46 -> 7.10 ms, 128 tokens 8.22 -> 7.46 (profiles/r05_prompt_lengths.log)
-        const bool splitk4 = may_split && n128 * 2 < cus && n128 * 4 <= 2 * cus && ksteps % 4 == 0 && P.nblk * CAP >= 4096;
         // Eight waves per tile (2 x 4: two per SIMD take turns in the step's serial chain) up to 512 tokens: 64 / 128 / 256 / 512 tokens
         // 7.17 / 7.44 / 8.60 / 12.28 -> 6.86 / 7.09 / 8.47 / 12.15 ms, three alternating runs on one box; four waves above (1024 tokens:
         // 19.0 vs 19.25 ms -- there the tiles are wo / w2 in two halves of K, two workgroups per CU already).  Same products either way.
-        const bool w8 = !force && T <= 512 && CAP <= 32;
+        const bool w8 = L0.waves == 8;
         auto run128 = [&](auto ks) -> int {
-            if (w8) return run(I128(), I128(), I2(), I4(), 0, (int)ntiles(128), K64(), ks);
-            return run(I128(), I128(), I2(), I2(), 0, (int)ntiles(128), K64(), ks);
+            if (w8) return run(I128(), I128(), I2(), I4(), L0.tn0, L0.tn_count, K64(), ks);
+            return run(I128(), I128(), I2(), I2(), L0.tn0, L0.tn_count, K64(), ks);
         };
         if constexpr (EPI != GM_GLU) {
             rc = 1;
-            if (splitk4) rc = run128(integral_constant<int, 4>());
-            else if (splitk) rc = run128(integral_constant<int, 2>());
+            if (plan.ks[0] == 4) rc = run128(integral_constant<int, 4>());
+            else if (plan.ks[0] == 2) rc = run128(integral_constant<int, 2>());
             if (rc == 1) rc = run128(S1());      // (no split, or its grid cannot be resident at once)
         } else rc = run128(S1());      // (K steps of 128 columns -- BK = 128 -- measured: 57 -> 72 us at 1024 x 4096 x 4096)
     }
@@ -1009,15 +989,18 @@ static int launch_gemm(const void *W, size_t N, size_t K, const void *X, size_t 
 
 namespace ifa {
 // cols % 64 == 0, 64 % block capacity == 0; fused epilogues (GM_RESIDUAL / GM_GLU) on the 20-byte Q4 blocks
+GemmBigFacts gemm_big_facts(int w_dtype, const GmArgs &P, int epi)
+{
+    GemmBigFacts f;
+    f.T = P.T; f.nsets = P.nsets; f.rows0 = P.rows[0]; f.rows1 = P.rows[1]; f.rows2 = P.rows[2]; f.nblk = P.nblk; f.dtype = w_dtype; f.epi = epi;
+    f.tiles_bits = g_gemm_big; f.num_cus = gemm_num_cus(); f.no_waits = P.no_waits; f.waits_on = waits_enabled();
+    f.has_w1 = P.W1 != nullptr;
+    f.ld_or = (P.Yset[0] ? (P.ldyset[0] | P.ldyset[1] | P.ldyset[2]) : P.ldy) | (epi == GM_RESIDUAL ? P.ldres : 0);
+    return f;
+}
 bool gemm_big_ok(int w_dtype, const GmArgs &P, int epi)
 {
-    const int cap = w_dtype == F16 ? 32 : block_capacity(w_dtype);
-    if (cap <= 1 || PF_BK % cap != 0 || ((size_t)P.nblk * cap) % PF_BK != 0 || P.T < 1 || P.nsets < 1 || P.nsets > 3) return false;
-    if (epi != GM_PLAIN && w_dtype != Q4_B32T1A && w_dtype != Q4_B32T1B) return false;
-    if (epi == GM_GLU && (P.nsets != 1 || !P.W1)) return false;
-    for (int i = 0; i < P.nsets; i++) if (P.rows[i] % 8 != 0) return false;     // (16-byte pieces of output rows)
-    if ((P.Yset[0] ? (P.ldyset[0] | P.ldyset[1] | P.ldyset[2]) : P.ldy) % 8 != 0 || (epi == GM_RESIDUAL && P.ldres % 8 != 0)) return false;
-    return true;
+    return plan_gemm_big(gemm_big_facts(w_dtype, P, epi)).error == GEMM_BIG_OK;
 }
 int gemm_big(int w_dtype, const GmArgs &P, int epi, hipStream_t s)
 {

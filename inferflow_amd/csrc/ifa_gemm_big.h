@@ -2,6 +2,7 @@
 // workgroup and step into LDS, up to three matrices per launch, residual / GLU epilogues.
 #pragma once
 #include "ifa_gemm_rows_mfma.h"
+#include "ifa_gemm_plan.h"
 
 namespace ifa {
 
@@ -14,12 +15,16 @@ struct BigGeo { int tile0[4]; int tiles_m; int K; int tn0; unsigned long long *p
 constexpr size_t SPLITK_FLAG_BYTES_H = 16384;
 int gemm_splitk_scratch(hipStream_t s, size_t part_bytes, size_t tiles, void **out);
 
+// the facts plan_gemm_big reads of a call, with the bits of ifa_gemm_big_tiles and the CU count of the current device
+GemmBigFacts gemm_big_facts(int w_dtype, const GmArgs &P, int epi);
 bool gemm_big_ok(int w_dtype, const GmArgs &P, int epi);
 int gemm_big(int w_dtype, const GmArgs &P, int epi, hipStream_t s);
 
 // Prompts of 33..512 tokens (ifa_gemm_mid.hip, k_gemm_mid): 128 x 128 tiles, weights in the MO layout (Tensor::mo, P.mo = 1),
 // everything global -> LDS through a ring of direct-to-LDS stages, the weights dequantised from their raw bytes straight into
 // the MFMA operand registers.  Same products, summation order over K and epilogues as gemm_big's 128 x 128 tiles.
+// the facts plan_gemm_mid reads of a call, with the measurement settings of the environment and the CU count of the current device
+GemmMidFacts gemm_mid_facts(const GmArgs &P, int epi);
 bool gemm_mid_ok(int w_dtype, const GmArgs &P, int epi);
 int gemm_mid(const GmArgs &P, int epi, hipStream_t s);
 

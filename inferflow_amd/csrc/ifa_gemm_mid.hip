@@ -44,10 +44,7 @@ typedef const __attribute__((address_space(1))) void md_glb_t;
 #ifndef IFA_MID_LOADERS
 #define IFA_MID_LOADERS 1   // 1: four more waves (one per SIMD) issue the direct-to-LDS requests; 0: the computing waves do, between their MFMAs
 #endif
-constexpr int MD_BN = 128, MD_BK = 64, MD_NW = 4, MD_NT = 256;      // (token rows of a tile: 32 TA, template parameter)
-constexpr int md_a_bytes(int ta) { return 32 * ta * MD_BK * 2; }       // activation tile of a step (TA = 4: 16 KB), rows of 128 bytes, 16-byte chunks swizzled
-constexpr int MD_WC_BYTES = MD_NW * 1024, MD_WS_BYTES = MD_NW * 256; // raw codes (32 rows x 2 blocks x 16 B per wave), (base, scale) words
-constexpr int md_stage(int ta) { return md_a_bytes(ta) + MD_WC_BYTES + MD_WS_BYTES; }    // 21 KB (TA = 4) / 37 KB (TA = 8)
+// (tile and stage geometry -- MD_BN, MD_BK, MD_NW, MD_NT, md_a_bytes, md_stage, IFA_MID_NS: ifa_gemm_plan.h)
 constexpr int MD_THREADS = IFA_MID_LOADERS ? 2 * MD_NT : MD_NT;     // launched threads (MD_NT of them compute and run the tails)
 // measurement builds (-DIFA_MID_ABL=n): 1 = no activation requests, 2 = no MFMA, 3 = no dequantisation, 4 = no barrier, 5 = no weight requests
 #ifndef IFA_MID_ABL
@@ -464,15 +461,42 @@ static int md_num_cus()
     return n;
 }
 
+// the measurement settings of the plan, read from the environment once
+struct MdSettings { int ks_all, ks_epi[3], ta, min_steps, two_per_cu, no_glu_split; };
+static const MdSettings &md_settings()
+{
+    static const MdSettings S = [] {
+        auto num = [](const char *name) { const char *v = getenv(name); return v ? atoi(v) : 0; };
+        MdSettings s;
+        s.ks_all = num("IFA_MID_KS");      // at most this many parts
+        s.ks_epi[GM_PLAIN] = num("IFA_MID_KS_PLAIN"); s.ks_epi[GM_RESIDUAL] = num("IFA_MID_KS_RES"); s.ks_epi[GM_GLU] = num("IFA_MID_KS_GLU");
+        s.ta = num("IFA_MID_TA");
+        s.min_steps = getenv("IFA_MID_MINSTEPS") ? num("IFA_MID_MINSTEPS") : 4;
+        s.two_per_cu = getenv("IFA_MID_TWO_PER_CU") != nullptr;          // the first form's limit
+        s.no_glu_split = getenv("IFA_MID_NO_GLU_SPLIT") != nullptr;      // the gated pair as ONE part of K, like k_gemm_big's -- bit-identical products
+        return s;
+    }();
+    return S;
+}
+
+// the facts of a launch (ifa_gemm_plan.h)
+GemmMidFacts gemm_mid_facts(const GmArgs &P, int epi)
+{
+    GemmMidFacts f;
+    f.T = P.T; f.nsets = P.nsets; f.rows0 = P.rows[0]; f.rows1 = P.rows[1]; f.rows2 = P.rows[2]; f.nblk = P.nblk; f.epi = epi;
+    f.num_cus = md_num_cus(); f.no_waits = P.no_waits; f.waits_on = waits_enabled();
+    const MdSettings &S = md_settings();
+    const int e = epi == GM_GLU ? GM_GLU : (epi == GM_RESIDUAL ? GM_RESIDUAL : GM_PLAIN);
+    f.max_parts = S.ks_epi[e] ? S.ks_epi[e] : S.ks_all; f.ta = S.ta; f.min_steps = S.min_steps; f.two_per_cu = S.two_per_cu; f.no_glu_split = S.no_glu_split;
+    f.mo = P.mo; f.has_w1 = P.W1 != nullptr;
+    f.ld_or = (P.Yset[0] ? (P.ldyset[0] | P.ldyset[1] | P.ldyset[2]) : P.ldy) | (epi == GM_RESIDUAL ? P.ldres : 0) | P.ldx;
+    return f;
+}
+
 bool gemm_mid_ok(int w_dtype, const GmArgs &P, int epi)
 {
     (void)w_dtype;      // (any format the MO copy holds: 4-bit codes with value q * scale + base per 32 weights)
-    if (!P.mo || P.T < 1 || P.nsets < 1 || P.nsets > 3 || P.nblk < 8 || P.nblk % 4 != 0) return false;
-    for (int i = 0; i < P.nsets; i++) if (P.rows[i] % 16 != 0) return false;
-    if (epi == GM_GLU && (P.nsets != 1 || !P.W1 || P.rows[0] % 8 != 0)) return false;
-    for (int i = 0; i < P.nsets; i++) if (P.rows[i] % 8 != 0) return false;
-    if ((P.Yset[0] ? (P.ldyset[0] | P.ldyset[1] | P.ldyset[2]) : P.ldy) % 8 != 0 || (epi == GM_RESIDUAL && P.ldres % 8 != 0) || P.ldx % 8 != 0) return false;
-    return true;
+    return plan_gemm_mid(gemm_mid_facts(P, epi)).error == GEMM_MID_OK;
 }
 
 template <int EPI, int KS, int NS, int TA>
@@ -486,7 +510,7 @@ static int md_run(const GmArgs &P, BigGeo G, int tn_count, hipStream_t s)
         if (rcs) return rcs;
         G.flags = (unsigned *)scratch; G.part = (unsigned long long *)((char *)scratch + SPLITK_FLAG_BYTES_H);
     }
-    const size_t smem = std::max((size_t)NS * md_stage(TA), (size_t)(32 * TA) * (MD_BN * 2 + 64));
+    const size_t smem = md_lds_bytes(TA);
     auto kern = k_gemm_mid<EPI, KS, NS, TA>;
     static std::atomic<uint64_t> attr_set{0};
     int dev = 0;
@@ -524,44 +548,29 @@ static int md_run(const GmArgs &P, BigGeo G, int tn_count, hipStream_t s)
     return IFA_OK;
 }
 
-#ifndef IFA_MID_NS
-#define IFA_MID_NS 3
-#endif
-
 template <int EPI, int TA>
-static int md_launch(const GmArgs &P, hipStream_t s)
+static int md_launch(const GmArgs &P, const GemmMidPlan &plan, hipStream_t s)
 {
-    constexpr int MD_BM = 32 * TA;
-    constexpr int BNE = EPI == GM_GLU ? MD_BN / 2 : MD_BN;
     BigGeo G; memset(&G, 0, sizeof(G));
-    G.tile0[0] = 0;
-    for (int i = 0; i < 3; i++) G.tile0[i + 1] = G.tile0[i] + (i < P.nsets ? (P.rows[i] + BNE - 1) / BNE : 0);
-    const int tn_count = G.tile0[P.nsets];
-    for (int i = P.nsets; i < 3; i++) G.tile0[i] = 1 << 30;
-    G.tiles_m = (P.T + MD_BM - 1) / MD_BM; G.K = P.nblk * 32; G.tn0 = 0;
-    const int ksteps = G.K / MD_BK;
-    // parts of K: the most that still put ONE workgroup on a CU (two fit -- LDS, registers -- but a grid between one and two per CU
-    // ends when the doubly loaded CUs do: wq | wk | wv of 128 tokens, 96 tiles: 384 workgroups 32.3 us, 192 workgroups 27; of 256
+    for (int i = 0; i < 4; i++) G.tile0[i] = plan.tile0[i];
+    const int tn_count = plan.tiles_n;
+    G.tiles_m = plan.tiles_m; G.K = P.nblk * 32; G.tn0 = 0;
+    // parts of K (plan_gemm_mid): the most that still put ONE workgroup on a CU (two fit -- LDS, registers -- but a grid between one and
+    // two per CU ends when the doubly loaded CUs do: wq | wk | wv of 128 tokens, 96 tiles: 384 workgroups 32.3 us, 192 workgroups 27; of 256
     // tokens, 192 tiles: one part beats two; wo / w2 of one token tile, 32 tiles: eight parts, 256 workgroups, beat four -- 128 tokens
     // 5.34 -> 4.86 ms in all, profiles/r06_prefill_mid_parts.log), every part >= MINS steps
-    static const bool two_per_cu = getenv("IFA_MID_TWO_PER_CU") != nullptr;      // (measurement: the first form's limit)
     // (the gated pair keeps two per CU: 172 tiles of one token tile as 344 workgroups 45.7 us, as 172 workgroups 50.5)
-    const long long tiles = (long long)G.tiles_m * tn_count, cap = ((two_per_cu || EPI == GM_GLU) ? 2ll : 1ll) * md_num_cus();
-    static const bool no_glu_split = getenv("IFA_MID_NO_GLU_SPLIT") != nullptr;      // (measurement: the gated pair as ONE part of K, like k_gemm_big's -- bit-identical products)
-    const bool may = !P.no_waits && waits_enabled() && !(EPI == GM_GLU && no_glu_split);
-    int rc = 1;
-    static const int force_all = getenv("IFA_MID_KS") ? atoi(getenv("IFA_MID_KS")) : 0;      // (measurement: at most this many parts)
-    static const int force_epi = getenv(EPI == GM_PLAIN ? "IFA_MID_KS_PLAIN" : (EPI == GM_GLU ? "IFA_MID_KS_GLU" : "IFA_MID_KS_RES"))
-                                     ? atoi(getenv(EPI == GM_PLAIN ? "IFA_MID_KS_PLAIN" : (EPI == GM_GLU ? "IFA_MID_KS_GLU" : "IFA_MID_KS_RES"))) : 0;
-    const int force_ks = force_epi ? force_epi : force_all;
-    static const int mins = getenv("IFA_MID_MINSTEPS") ? atoi(getenv("IFA_MID_MINSTEPS")) : 4;
-    auto fits = [&](int ks) { return may && tiles * ks <= cap && ksteps / ks >= mins && (!force_ks || ks <= force_ks); };
     // (16 parts: the exchanged sums grow with the part count -- 30 MB written and read for wo: 30 us against 17 at 8 -- a measurement setting)
-    if constexpr (TA == 4) { if (force_ks >= 16 && fits(16)) rc = md_run<EPI, 16, IFA_MID_NS, TA>(P, G, tn_count, s); }
-    if (rc == 1 && fits(8)) rc = md_run<EPI, 8, IFA_MID_NS, TA>(P, G, tn_count, s);
-    if (rc == 1 && fits(4)) rc = md_run<EPI, 4, IFA_MID_NS, TA>(P, G, tn_count, s);
-    if (rc == 1 && fits(2)) rc = md_run<EPI, 2, IFA_MID_NS, TA>(P, G, tn_count, s);
-    if (rc == 1) rc = md_run<EPI, 1, IFA_MID_NS, TA>(P, G, tn_count, s);
+    int rc = 1;
+    for (int i = 0; i < plan.n_try && rc == 1; i++) {      // (1: the waiting grid cannot be resident -- the next candidate)
+        switch (plan.parts[i]) {
+        case 16: if constexpr (TA == 4) rc = md_run<EPI, 16, IFA_MID_NS, TA>(P, G, tn_count, s); break;
+        case 8: rc = md_run<EPI, 8, IFA_MID_NS, TA>(P, G, tn_count, s); break;
+        case 4: rc = md_run<EPI, 4, IFA_MID_NS, TA>(P, G, tn_count, s); break;
+        case 2: rc = md_run<EPI, 2, IFA_MID_NS, TA>(P, G, tn_count, s); break;
+        default: rc = md_run<EPI, 1, IFA_MID_NS, TA>(P, G, tn_count, s); break;
+        }
+    }
     if (rc) return rc;
     IFA_LAUNCH_CHECK();
     return IFA_OK;
@@ -569,20 +578,19 @@ static int md_launch(const GmArgs &P, hipStream_t s)
 
 int gemm_mid(const GmArgs &P, int epi, hipStream_t s)
 {
-    if (!gemm_mid_ok(Q4_B32T1A, P, epi)) return ifa_fail(IFA_ERR_ARG, "mid-length GEMM: %d blocks per row / epilogue %d", P.nblk, epi);
+    const GemmMidPlan plan = plan_gemm_mid(gemm_mid_facts(P, epi));
+    if (plan.error) return ifa_fail(IFA_ERR_ARG, "mid-length GEMM: %d blocks per row / epilogue %d (plan error %d)", P.nblk, epi, plan.error);
     // 256-token tiles (TA = 8): the weight stream and its conversion serve twice the products per step
-    static const int force_ta = getenv("IFA_MID_TA") ? atoi(getenv("IFA_MID_TA")) : 0;      // (measurement)
     // (measured round 6: 512 / 768 tokens 10.96 / 16.48 ms with 128-token tiles, 11.37 / 17.50 with 256; 1024 tokens 19.57 / 19.25 -- the
     //  wide tile pays only where the large-tile kernel already ties, so it stays a measurement setting)
-    const bool wide = force_ta == 8;
-    if (wide) {
-        if (epi == GM_PLAIN) return md_launch<GM_PLAIN, 8>(P, s);
-        if (epi == GM_RESIDUAL) return md_launch<GM_RESIDUAL, 8>(P, s);
-        return md_launch<GM_GLU, 8>(P, s);
+    if (plan.ta == 8) {
+        if (epi == GM_PLAIN) return md_launch<GM_PLAIN, 8>(P, plan, s);
+        if (epi == GM_RESIDUAL) return md_launch<GM_RESIDUAL, 8>(P, plan, s);
+        return md_launch<GM_GLU, 8>(P, plan, s);
     }
-    if (epi == GM_PLAIN) return md_launch<GM_PLAIN, 4>(P, s);
-    if (epi == GM_RESIDUAL) return md_launch<GM_RESIDUAL, 4>(P, s);
-    return md_launch<GM_GLU, 4>(P, s);
+    if (epi == GM_PLAIN) return md_launch<GM_PLAIN, 4>(P, plan, s);
+    if (epi == GM_RESIDUAL) return md_launch<GM_RESIDUAL, 4>(P, plan, s);
+    return md_launch<GM_GLU, 4>(P, plan, s);
 }
 
 } // namespace ifa
