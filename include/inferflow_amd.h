@@ -198,6 +198,20 @@ int ifa_exact_activation_mul(int kind, const void *a_f16, const void *gate_f16, 
  * Each returns its previous threshold. */
 int ifa_attention_two_pass_min(int min_tokens);
 int ifa_attention_two_pass_min_keys(int min_keys);
+/* dynamic batching: n_rows query rows, each ONE new token of its own query.  rows_dev: device array of n_rows records
+ * { const void *kcache, *vcache; int n_ctx, pad; } -- row t attends to all n_ctx keys of its own caches; max_ctx: the longest of
+ * them (it sizes the LDS).  q F16 [n_rows][heads][head_dim], out F16 [n_rows][heads*head_dim]; the rest as ifa_attention. */
+int ifa_attention_rows(const void *q_f16, const void *rows_dev, int kv_dtype, int n_rows, int max_ctx, int heads, int kv_heads,
+                       int head_dim, float kq_scale, int alibi, int alibi_base_head, int alibi_total_heads, void *out_f16,
+                       ifa_stream stream);
+/* What a call of ifa_attention / ifa_attention_rows launches (csrc/ifa_attn_plan.h).  Host-only, no GPU needed, no state.
+ * facts[10], in the order of AttnFacts: kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, two_pass_min and
+ * two_pass_min_keys (the values the two setters above return), rows_mode (1: ifa_attention_rows with n_ctx = max_ctx, q_tokens =
+ * n_rows).  out[10], in the order of AttnPlan: error (0 ok, 1 kv dtype, 2 heads / kv_heads, 3 head_dim, 4 n_ctx / q_tokens / prefix,
+ * 5 too long), kind (0 scalar k_attention, 1 MFMA tiles with the score tile in LDS, 2 the same with a global workspace, 3 two-pass
+ * with 64 queries per workgroup, 4 two-pass with 128), queries per workgroup, grid x, grid y, dynamic LDS bytes, sg_nkp (row stride
+ * of the workspace tiles, halfs), xcd_remap, then the workspace bytes as two ints (low half first). */
+int ifa_attention_plan(const int *facts, int n_facts, int *out, int n_out);
 
 /* ---- greedy argmax over F16 logits (SampleTokens top-1) ------------------ */
 /* MoE routing of `tokens` softmaxed router rows [tokens][experts] on the device -- the per-row part of

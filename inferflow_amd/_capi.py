@@ -68,6 +68,8 @@ SIGNATURES = {
     "ifa_gemm": (_i, [_i, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
     "ifa_attention_two_pass_min": (_i, [_i]),
     "ifa_attention_two_pass_min_keys": (_i, [_i]),
+    "ifa_attention_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
+    "ifa_attention_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_big_tiles": (_i, [_i]),
     "ifa_wait_grid_decision": (_i, [_i, _i, C.c_longlong]),
     "ifa_visible_cus_from_mask": (_i, [C.c_char_p, _i, _i]),

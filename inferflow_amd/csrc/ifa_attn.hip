@@ -11,11 +11,13 @@
 // q.k and P.V are accumulated in fp32 in index order (products of halfs are
 // exact in fp32), so S and O match the restated reference bit-for-bit given the
 // same P; P differs by the device expf and the softmax summation order.
+#include <cstring>
 #include <map>
 #include <mutex>
 #include "ifa_host.h"
 #include "ifa_device.h"
 #include "ifa_math.h"
+#include "ifa_attn_plan.h"
 
 namespace ifa {
 
@@ -129,11 +131,7 @@ __device__ __forceinline__ half8v kv_load8(const uint8_t *cache, size_t row_byte
     }
 }
 
-constexpr int PF_QT = 32;            // queries per workgroup
-constexpr int PF_VROW = 40;          // halfs per row of the transposed V block (32 keys + pad: conflict-free b128 reads)
-
-__host__ __device__ inline int pf_nkp(int n_keys) { return (n_keys + 31) / 32 * 32 + 8; }
-
+// (PF_QT queries per workgroup, PF_VROW halfs per row of the transposed V block, pf_nkp halfs per score row: ifa_attn_plan.h)
 __device__ unsigned long long g_attn_trace[8];     // wall_clock64 stamps of the longest tile of head 0 (tools/probes)
 
 // SG: the [32 x n_keys] score tile lives in a global workspace (sg_ws: [heads][tiles][32][sg_nkp] halfs) instead of the LDS
@@ -355,8 +353,7 @@ __global__ void __launch_bounds__(256) k_attention_mfma(const half_t *__restrict
 //   O^T = V^T . P^T: P^T is then already the B operand (lane = query column, 8 keys per k-step); a lane's registers hold keys
 //                  4g + {0-3, 8-11, 16-19, 24-27}, so the V block is transposed into LDS with its key columns in THAT order
 //                  (f2_col) -- the sum over keys does not care.
-constexpr int F2_QT = 128;
-constexpr int F2_VROW = 40;          // halfs per row of the transposed V block (32 key columns + pad)
+// (F2_QT = 128 queries per workgroup, F2_VROW halfs per row of the transposed V block: ifa_attn_plan.h)
 __host__ __device__ constexpr int f2_col(int k) { return (k & 16) | (((k >> 2) & 1) << 3) | (k & 3) | (((k >> 3) & 1) << 2); }
 template <int HD> __device__ __forceinline__ int f2_swz(int row) { return HD == 128 ? (row & 15) : ((row >> 1) & 7); }
 
@@ -831,9 +828,8 @@ using namespace ifa;
 template <int HD>
 static int launch_attention_mfma(const void *q, const void *kcache, const void *vcache, int kv_dtype, int n_ctx, int q_tokens,
                                  int prefix_len, int heads, int kv_heads, float kq_scale, int alibi, int alibi_base,
-                                 int alibi_total, void *out, size_t smem, hipStream_t s, half_t *sg_ws = nullptr, int sg_nkp = 0)
+                                 int alibi_total, void *out, dim3 grid, size_t smem, hipStream_t s, half_t *sg_ws, int sg_nkp)
 {
-    dim3 grid((unsigned)((q_tokens + PF_QT - 1) / PF_QT), (unsigned)heads);
 #define IFA_PFA(Q8V, SGV) { auto kern = k_attention_mfma<HD, Q8V, SGV>; \
         if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
         kern<<<grid, dim3(256), smem, s>>>((const half_t *)q, (const uint8_t *)kcache, (const uint8_t *)vcache, n_ctx, q_tokens, \
@@ -901,26 +897,54 @@ extern "C" int ifa_debug_attn_trace(unsigned long long *out8)
     return IFA_OK;
 }
 
+static AttnFacts attn_facts(int kv_dtype, int n_ctx, int q_tokens, int prefix_len, int heads, int kv_heads, int head_dim, int rows_mode)
+{
+    AttnFacts f;
+    f.kv_dtype = kv_dtype; f.n_ctx = n_ctx; f.q_tokens = q_tokens; f.prefix_len = prefix_len;
+    f.heads = heads; f.kv_heads = kv_heads; f.head_dim = head_dim;
+    f.two_pass_min = g_attn_2pass_min; f.two_pass_min_keys = g_attn_2pass_min_keys; f.rows_mode = rows_mode;
+    return f;
+}
+
+// the launch plan of a call (ifa_attn_plan.h) behind the C ABI, for tests: the pure function, no device is touched
+extern "C" int ifa_attention_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    IFA_REQUIRE(facts && out && n_facts == ATTN_N_FACTS && n_out >= ATTN_N_OUT, "ifa_attention_plan: %d facts, %d outputs expected", ATTN_N_FACTS, ATTN_N_OUT);
+    AttnFacts f;
+    memcpy(&f, facts, sizeof(f));
+    const AttnPlan r = plan_attention(f);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
+template <bool Q8>
+static int launch_attention_scalar(const AttnPlan &pl, const void *q, const void *kcache, const void *vcache, int n_ctx, int q_tokens,
+                                   int prefix_len, int heads, int kv_heads, int head_dim, float kq_scale, int alibi, int alibi_base,
+                                   int alibi_total, void *out, const AttnRow *rows, hipStream_t s)
+{
+    const size_t smem = (size_t)pl.lds;
+    if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_attention<Q8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    k_attention<Q8><<<dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(256), smem, s>>>(
+        (const half_t *)q, (const uint8_t *)kcache, (const uint8_t *)vcache, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, kq_scale,
+        alibi, alibi_base, alibi_total, (half_t *)out, rows);
+    IFA_LAUNCH_CHECK();
+    return IFA_OK;
+}
+
 // engine-internal: n query rows, each one token on its own KV cache (rows_dev[t]); max_ctx = longest context
 extern "C" int ifa_attention_rows(const void *q, const void *rows_dev, int kv_dtype, int n_rows, int max_ctx, int heads, int kv_heads,
                                   int head_dim, float kq_scale, int alibi, int alibi_base_head, int alibi_total_heads, void *out,
                                   ifa_stream stream)
 {
-    IFA_REQUIRE(q && rows_dev && out && n_rows > 0 && max_ctx > 0, "ifa_attention_rows: bad arguments");
-    const size_t smem = (((size_t)max_ctx * 2 + 15) & ~(size_t)15) + 64;
-    dim3 grid((unsigned)heads, (unsigned)n_rows);
+    IFA_REQUIRE(q && rows_dev && out, "ifa_attention_rows: bad arguments");
+    const AttnPlan pl = plan_attention(attn_facts(kv_dtype, max_ctx, n_rows, 0, heads, kv_heads, head_dim, 1));
+    IFA_REQUIRE(pl.error == ATTN_OK, "ifa_attention_rows: bad arguments");
     const int total_heads = alibi_total_heads > 0 ? alibi_total_heads : heads;
-    if (kv_dtype == Q8_B32T2) {
-        if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_attention<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        k_attention<true><<<grid, dim3(256), smem, ifa_s(stream)>>>((const half_t *)q, nullptr, nullptr, max_ctx, n_rows, 0, heads, kv_heads, head_dim, kq_scale,
-                                                                    alibi, alibi_base_head, total_heads, (half_t *)out, (const AttnRow *)rows_dev);
-    } else {
-        if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_attention<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        k_attention<false><<<grid, dim3(256), smem, ifa_s(stream)>>>((const half_t *)q, nullptr, nullptr, max_ctx, n_rows, 0, heads, kv_heads, head_dim, kq_scale,
-                                                                     alibi, alibi_base_head, total_heads, (half_t *)out, (const AttnRow *)rows_dev);
-    }
-    IFA_LAUNCH_CHECK();
-    return IFA_OK;
+    if (kv_dtype == Q8_B32T2)
+        return launch_attention_scalar<true>(pl, q, nullptr, nullptr, max_ctx, n_rows, 0, heads, kv_heads, head_dim, kq_scale, alibi,
+                                             alibi_base_head, total_heads, out, (const AttnRow *)rows_dev, ifa_s(stream));
+    return launch_attention_scalar<false>(pl, q, nullptr, nullptr, max_ctx, n_rows, 0, heads, kv_heads, head_dim, kq_scale, alibi,
+                                          alibi_base_head, total_heads, out, (const AttnRow *)rows_dev, ifa_s(stream));
 }
 
 extern "C" int ifa_attention(const void *q, const void *kcache, const void *vcache, int kv_dtype, int n_ctx,
@@ -928,18 +952,17 @@ extern "C" int ifa_attention(const void *q, const void *kcache, const void *vcac
                              int alibi, int alibi_base_head, int alibi_total_heads, void *out, ifa_stream stream)
 {
     IFA_REQUIRE(q && kcache && vcache && out, "ifa_attention: null pointer");
-    IFA_REQUIRE(kv_dtype == F16 || kv_dtype == Q8_B32T2, "ifa_attention: kv dtype %d", kv_dtype);
-    IFA_REQUIRE(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, "ifa_attention: heads %d kv_heads %d", heads, kv_heads);
-    IFA_REQUIRE(head_dim > 0 && (kv_heads * head_dim) % 32 == 0, "ifa_attention: head_dim %d", head_dim);
-    IFA_REQUIRE(n_ctx > 0 && q_tokens > 0 && prefix_len >= 0, "ifa_attention: n_ctx %d q_tokens %d prefix %d", n_ctx, q_tokens, prefix_len);
-    IFA_REQUIRE(n_ctx <= 65536 && q_tokens <= 65535, "ifa_attention: context too long for the op-level kernel");
+    const AttnPlan pl = plan_attention(attn_facts(kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, 0));
+    IFA_REQUIRE(pl.error == ATTN_OK, "ifa_attention: %s (kv dtype %d, heads %d, kv_heads %d, head_dim %d, n_ctx %d, q_tokens %d, prefix %d)",
+                attn_plan_error_text(pl.error), kv_dtype, heads, kv_heads, head_dim, n_ctx, q_tokens, prefix_len);
     IFA_REQUIRE(kq_scale > 0, "ifa_attention: kq_scale must be > 0");
     const int total_heads = alibi_total_heads > 0 ? alibi_total_heads : heads;
-    // chunks of >= 64 queries: the two-pass kernel with 64 queries per workgroup and the key blocks split over wave pairs
-    if (q_tokens >= g_attn_2pass_min && !(q_tokens >= 128 && n_ctx >= g_attn_2pass_min_keys) && (head_dim == 64 || head_dim == 128)) {
-        hipStream_t hs = ifa_s(stream);
-        dim3 grid((unsigned)((q_tokens + 63) / 64), (unsigned)heads);
-        const size_t smem = (size_t)4 * 32 * head_dim * 2 + (size_t)4 * head_dim * F2_VROW * 2;
+    hipStream_t hs = ifa_s(stream);
+    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
+    const size_t smem = (size_t)pl.lds;
+    switch (pl.kind) {
+    case ATTN_TWO_PASS64: {
+        // chunks of >= 64 queries: the two-pass kernel with 64 queries per workgroup and the key blocks split over wave pairs
 #define IFA_F2K(HDV, Q8V) { auto kern = k_attention_2pass_ks<HDV, Q8V>; \
         if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
         kern<<<grid, dim3(256), smem, hs>>>((const half_t *)q, (const uint8_t *)kcache, (const uint8_t *)vcache, n_ctx, q_tokens, \
@@ -950,11 +973,9 @@ extern "C" int ifa_attention(const void *q, const void *kcache, const void *vcac
         IFA_LAUNCH_CHECK();
         return IFA_OK;
     }
-    // the 128-query variant of it (one wave per 32 queries, every wave walks all key blocks): behind the 64-query one at every
-    // length measured (4096 tokens: 519 vs 492 us), selectable through ifa_attention_two_pass_min_keys
-    if (q_tokens >= 128 && q_tokens >= g_attn_2pass_min && n_ctx >= g_attn_2pass_min_keys && (head_dim == 64 || head_dim == 128)) {
-        hipStream_t hs = ifa_s(stream);
-        dim3 grid((unsigned)((q_tokens + F2_QT - 1) / F2_QT), (unsigned)heads);
+    case ATTN_TWO_PASS128: {
+        // the 128-query variant of it (one wave per 32 queries, every wave walks all key blocks): behind the 64-query one at every
+        // length measured (4096 tokens: 519 vs 492 us), selectable through ifa_attention_two_pass_min_keys
 #define IFA_F2A(HDV, Q8V) k_attention_2pass<HDV, Q8V><<<grid, dim3(256), 0, hs>>>((const half_t *)q, (const uint8_t *)kcache, (const uint8_t *)vcache, n_ctx, q_tokens, \
                                                                                  prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, (half_t *)out)
         if (head_dim == 128) { if (kv_dtype == Q8_B32T2) IFA_F2A(128, true); else IFA_F2A(128, false); }
@@ -963,43 +984,27 @@ extern "C" int ifa_attention(const void *q, const void *kcache, const void *vcac
         IFA_LAUNCH_CHECK();
         return IFA_OK;
     }
-    // prefill: MFMA tiles whenever the [32 x n_keys] score tile fits the 160 KiB LDS (~2300 keys)
-    const size_t smem_mfma = (size_t)PF_QT * pf_nkp(n_ctx) * 2 + (size_t)head_dim * PF_VROW * 2 + 64;
-    if (q_tokens >= 4 && smem_mfma <= 150 * 1024 && (head_dim == 32 || head_dim == 64 || head_dim == 128)) {
-        hipStream_t hs = ifa_s(stream);
-        switch (head_dim) {
-        case 32: return launch_attention_mfma<32>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, smem_mfma, hs);
-        case 64: return launch_attention_mfma<64>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, smem_mfma, hs);
-        default: return launch_attention_mfma<128>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, smem_mfma, hs);
-        }
-    }
-    if (q_tokens >= 4 && (head_dim == 32 || head_dim == 64 || head_dim == 128)) {
-        // longer contexts: the same kernel with its score tiles in a global workspace (the op-level kernel below takes 131 ms
-        // per layer for 2048 queries on 4096 keys)
-        const int nkp = pf_nkp(n_ctx);
-        const size_t tiles = (size_t)((q_tokens + PF_QT - 1) / PF_QT);
+    case ATTN_MFMA_LDS:
+    case ATTN_MFMA_WORKSPACE: {
+        // prefill: MFMA tiles, the [32 x n_keys] score tile in the 160 KiB LDS (~2300 keys); longer contexts: the same kernel with its
+        // score tiles in a global workspace (the op-level kernel below takes 131 ms per layer for 2048 queries on 4096 keys)
         half_t *ws = nullptr;
-        int rc = sg_workspace(ifa_s(stream), (size_t)heads * tiles * PF_QT * (size_t)nkp * 2, &ws);
-        if (rc) return rc;
-        const size_t smem_v = (size_t)head_dim * PF_VROW * 2 + 64;
-        hipStream_t hs = ifa_s(stream);
+        if (pl.kind == ATTN_MFMA_WORKSPACE) {
+            int rc = sg_workspace(hs, (size_t)pl.ws_bytes, &ws);
+            if (rc) return rc;
+        }
         switch (head_dim) {
-        case 32: return launch_attention_mfma<32>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, smem_v, hs, ws, nkp);
-        case 64: return launch_attention_mfma<64>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, smem_v, hs, ws, nkp);
-        default: return launch_attention_mfma<128>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, smem_v, hs, ws, nkp);
+        case 32: return launch_attention_mfma<32>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, grid, smem, hs, ws, pl.sg_nkp);
+        case 64: return launch_attention_mfma<64>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, grid, smem, hs, ws, pl.sg_nkp);
+        default: return launch_attention_mfma<128>(q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base_head, total_heads, out, grid, smem, hs, ws, pl.sg_nkp);
         }
     }
-    size_t smem = (((size_t)n_ctx * 2 + 15) & ~(size_t)15) + 64;
-    dim3 grid((unsigned)heads, (unsigned)q_tokens);
-    if (kv_dtype == Q8_B32T2) {
-        if (smem > 48 * 1024)
-            IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_attention<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        k_attention<true><<<grid, dim3(256), smem, ifa_s(stream)>>>((const half_t *)q, (const uint8_t *)kcache, (const uint8_t *)vcache, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, kq_scale, alibi, alibi_base_head, alibi_total_heads > 0 ? alibi_total_heads : heads, (half_t *)out);
-    } else {
-        if (smem > 48 * 1024)
-            IFA_HIP_CHECK(hipFuncSetAttribute((const void *)k_attention<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        k_attention<false><<<grid, dim3(256), smem, ifa_s(stream)>>>((const half_t *)q, (const uint8_t *)kcache, (const uint8_t *)vcache, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, kq_scale, alibi, alibi_base_head, alibi_total_heads > 0 ? alibi_total_heads : heads, (half_t *)out);
+    default:
+        break;
     }
-    IFA_LAUNCH_CHECK();
-    return IFA_OK;
+    if (kv_dtype == Q8_B32T2)
+        return launch_attention_scalar<true>(pl, q, kcache, vcache, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, kq_scale, alibi,
+                                             alibi_base_head, total_heads, out, nullptr, hs);
+    return launch_attention_scalar<false>(pl, q, kcache, vcache, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, kq_scale, alibi,
+                                          alibi_base_head, total_heads, out, nullptr, hs);
 }
