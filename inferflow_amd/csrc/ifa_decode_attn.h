@@ -159,7 +159,14 @@ struct DecAttnRegs {
 };
 
 // PHASE 0: the whole kernel; 1: the entry requests only; 2: everything behind them (R filled by a PHASE 1 call)
-template <int HD, bool Q8, bool BATCH, int PB, bool KT, bool FUSED, int PHASE = 0>
+// STG (FUSED only; the UL instances of k_dec_qkv_attn): the tail waits TWICE.  Everything up to P.V over the cached keys needs the
+// new token's q and k only, so the first wait is for those granules; the new token's v is needed for the V cache row and for
+// the LAST term of one P.V chain (key `pos` is the largest key of its split), so the second wait sits behind the `opart`
+// barrier, on the threads [0, HD) that hold one element of v each: they round-trip it through the Q8 quantiser (a 32-block is a
+// half wave of these threads -- the expressions of the block loop below), write the V row, and add the term to split
+// pos % NSPLIT's partial sum with the fma thread (pos % NSPLIT, d / 8) would have issued last: every o[e] chain, and the sum over the
+// splits, keep their order bit for bit.  The first look at the v granules is requested in front of P.V and examined behind it.
+template <int HD, bool Q8, bool BATCH, int PB, bool KT, bool FUSED, int PHASE = 0, bool STG = false>
 __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, const uint8_t *pkc, const uint8_t *pvc, int pheads, int pkvh,
                                               const DecAttnParams &P, const int h_in, const DecAttnFusedIn &F, DecAttnRegs<HD, Q8, PB, KT> &R)
 {
@@ -188,6 +195,7 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
     float *opart = red + 16;                                       // [NSPLIT][HD]
     static_assert(!KT || (!Q8 && !BATCH && (DG & (DG - 1)) == 0 && PB % NSPLIT == 0), "K tile through LDS: F16 rows, one query, power-of-two pieces per row");
     static_assert(!(FUSED && BATCH), "the fused tail is a single-query kernel");
+    static_assert(!STG || (FUSED && PHASE == 0), "the two waits are the fused tail's");
     static_assert(PB >= NSPLIT && PB <= DEC_ATTN_MIN_ROWS, "prefetch bucket");
     uint8_t *ktile = reinterpret_cast<uint8_t *>(opart + NSPLIT * HD);                         // KT: [PB][HD] halves, 16-byte pieces XOR-swizzled by key
     half_t *S = reinterpret_cast<half_t *>(ktile + (KT ? (size_t)PB * HD * 2 : 0));            // [n_ctx]
@@ -302,6 +310,17 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
             const unsigned long long *gq = F.gran + (size_t)h * HD + tid, *gk = F.gran + (size_t)(pheads + kvh) * HD + tid,
                                      *gv = F.gran + (size_t)(pheads + pkvh + kvh) * HD + tid;
             const long long t_give_up = wall_clock64() + F.timeout_ticks;
+            if constexpr (STG) {        // the first wait: q and k only (v_in stays 0 until the second wait)
+                for (;;) {
+                    const unsigned long long a = __hip_atomic_load(gq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const unsigned long long b = __hip_atomic_load(gk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const bool ok = (unsigned)(a >> 32) == F.epoch && (unsigned)(b >> 32) == F.epoch;
+                    q_in = __builtin_bit_cast(half_t, (uint16_t)a); k_in = __builtin_bit_cast(half_t, (uint16_t)b);
+                    if (__all(ok)) break;
+                    if (wall_clock64() > t_give_up) { if (lane == 0) atomicExch(F.err, 0x51u); break; }
+                    __builtin_amdgcn_s_sleep(2);
+                }
+            } else
             for (;;) {
                 const unsigned long long a = __hip_atomic_load(gq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const unsigned long long b = __hip_atomic_load(gk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -340,7 +359,8 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
         // one 32-value block per HALF wave (HD = 128: the 4 + 4 blocks of the new k and v rows on the 8 half waves at once; the
         // block maximum by DPP + one permute): two blocks per wave one after the other on 32 lanes with five LDS permutes each was
         // 0.9 us of this kernel.  Same operations per element as before (the maximum does not depend on the order).
-        for (int b = wave * 2 + (lane >> 5); b < 2 * NB; b += 8) {
+        // (STG: the k blocks only -- the v blocks go through the same expressions behind the second wait)
+        for (int b = wave * 2 + (lane >> 5); b < (STG ? NB : 2 * NB); b += 8) {
             half_t *src = b < NB ? kn : vn;
             const int bb = b < NB ? b : b - NB;
             const int l32 = lane & 31;
@@ -364,7 +384,7 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
     } else {
         if (writer && tid < HD) {
             reinterpret_cast<half_t *>(kcw + (size_t)pos * row_bytes + head_off)[tid] = kn[tid];
-            reinterpret_cast<half_t *>(vcw + (size_t)pos * row_bytes + head_off)[tid] = vn[tid];
+            if constexpr (!STG) reinterpret_cast<half_t *>(vcw + (size_t)pos * row_bytes + head_off)[tid] = vn[tid];
         }
     }
 
@@ -514,6 +534,12 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
     }
     if (tr) P.trace[h * 8 + 5] = wall_clock64();
 
+    // STG: a first look at the new token's v granules, requested here and examined behind P.V (unconditional, clamped: a
+    // request under an exec mask would turn the waits of the V pieces below into vmcnt(0))
+    unsigned long long v_look = 0;
+    if constexpr (STG)
+        v_look = __hip_atomic_load(F.gran + (size_t)(pheads + pkvh + kvh) * HD + dq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+
     // ---- O = P.V : thread (sp, dg) accumulates keys j = sp + NSPLIT*i for its 8 dims
     float o[8];
 #pragma unroll
@@ -550,7 +576,7 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
         const int j = sp + NSPLIT * i;
         if (j < n_ctx && vact) {
             const float pj = h2f(S[j]);
-            if (j == pos) acc_new(pj);
+            if (j == pos) { if constexpr (!STG) acc_new(pj); }        // (STG: the chain's last term, added behind the second wait)
             else if constexpr (Q8) acc_q8w(pj, (uint16_t)vqs[i], (uint16_t)(vqc[i][0] & 0xFFFFu), (uint16_t)(vqc[i][0] >> 16), (uint16_t)(vqc[i][1] & 0xFFFFu), (uint16_t)(vqc[i][1] >> 16));
             else acc_v(pj, vreg[i]);
         }
@@ -586,7 +612,7 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
                 const int jj = j + u * NSPLIT;
                 if (jj >= n_ctx) break;
                 const float pj = h2f(S[jj]);
-                if (jj == pos) acc_new(pj);
+                if (jj == pos) { if constexpr (!STG) acc_new(pj); }
                 else if constexpr (Q8) acc_q8w(pj, (uint16_t)ts_c[u], (uint16_t)(tc_c[u][0] & 0xFFFFu), (uint16_t)(tc_c[u][0] >> 16), (uint16_t)(tc_c[u][1] & 0xFFFFu), (uint16_t)(tc_c[u][1] >> 16));
                 else acc_v(pj, tcur[u]);
             }
@@ -604,8 +630,55 @@ __device__ __forceinline__ void dec_attn_body(char *smem, const half_t *pq, cons
     if (tr) P.trace[h * 8 + 6] = wall_clock64();
     __syncthreads();
     if (tid < HD) {
-        float acc = opart[tid];
-        for (int s2 = 1; s2 < NSPLIT; s2++) acc = acc + opart[s2 * HD + tid];
+        float acc;
+        if constexpr (STG) {
+            // ---- the second wait: the new token's v, one element per thread (bounded like the first; error code 0x52)
+            {
+                const unsigned long long *gv = F.gran + (size_t)(pheads + pkvh + kvh) * HD + tid;
+                const long long t_give_up = wall_clock64() + F.timeout_ticks;
+                for (;;) {
+                    const bool ok = (unsigned)(v_look >> 32) == F.epoch;
+                    v_in = __builtin_bit_cast(half_t, (uint16_t)v_look);
+                    if (__all(ok)) break;
+                    if (wall_clock64() > t_give_up) { if (lane == 0) atomicExch(F.err, 0x52u); break; }
+                    __builtin_amdgcn_s_sleep(2);
+                    v_look = __hip_atomic_load(gv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+            if (tr) P.trace[(size_t)(pheads + (int)blockIdx.x) * 8 + 5] = wall_clock64();      // v_seen (the workgroup's own stamp row)
+            // the V row of the new token (SetVRows) and the value GetVRows returns for it: the block loop's expressions, block tid / 32
+            half_t vv = v_in;
+            if constexpr (Q8) {
+                const int bb = tid >> 5, l32 = lane & 31;
+                const float val = h2f(vv);
+                const float mx = half_wave_max(fabsf(val));
+                const float sc = mx / 127;
+                int qv = sc <= 0.000001f ? 0 : (int)roundf(val / sc);
+                qv = min(max(qv, -128), 127);
+                const half_t sch = f2h(sc);
+                if (writer) {
+                    uint8_t *blk = vcw + (size_t)pos * row_bytes + head_off + (size_t)bb * 34;
+                    blk[2 + l32] = (uint8_t)(int8_t)qv;
+                    if (l32 == 0) *reinterpret_cast<uint16_t *>(blk) = __builtin_bit_cast(uint16_t, sch);
+                }
+                vv = f2h((float)qv * h2f(sch));
+            } else {
+                if (writer) reinterpret_cast<half_t *>(vcw + (size_t)pos * row_bytes + head_off)[tid] = vv;
+            }
+            // the sum over the splits in split order; split pos % NSPLIT's partial first takes the term of key `pos` -- acc_new's fma
+            const int sp_new = pos % NSPLIT;
+            const float p_new = h2f(S[pos]), v_new = h2f(vv);
+            acc = opart[tid];
+            if (sp_new == 0) acc = __builtin_fmaf(p_new, v_new, acc);
+            for (int s2 = 1; s2 < NSPLIT; s2++) {
+                float part = opart[s2 * HD + tid];
+                if (s2 == sp_new) part = __builtin_fmaf(p_new, v_new, part);
+                acc = acc + part;
+            }
+        } else {
+            acc = opart[tid];
+            for (int s2 = 1; s2 < NSPLIT; s2++) acc = acc + opart[s2 * HD + tid];
+        }
         const half_t yh = f2h(acc);
         outp[(size_t)h * HD + tid] = yh;
         if constexpr (HD % 32 == 0 && !BATCH) { if (P.xq) dec_attn_emit_q8<HD>(P.xq, P.heads * HD, h, tid, yh); }

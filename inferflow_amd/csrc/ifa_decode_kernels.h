@@ -156,14 +156,19 @@ __host__ __device__ inline XqImage xq_image_carve(void *base, int cols)
 // up, and everybody waits for part[131] == NT / 64 before reading the image (xpre_wait_image).  Same chunk -> lane / group
 // assignment rule (chunk c = tid + k * threads: lane c % 64 of group c / 64), so the statistics and the codes are the
 // same bits for any NT.
+// The counters are reached through pointers whose address space is STATED (LDS): through a generic pointer the compiler emits
+// FLAT instructions, which count on vmcnt as well as on lgkmcnt and may return out of order with the weight requests -- the poll
+// was `flat_load; s_waitcnt vmcnt(0) lgkmcnt(0)`, i.e. every wave waited for ALL its weight rows before its first dot, and a
+// pending flat atomic turned the prologue waves' later counted waits into vmcnt(0) too.
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
 __device__ __forceinline__ void lds_counter_add(float *slot)
 {
     asm volatile("" ::: "memory");      // the wave's earlier LDS writes stay ahead of the counter (the LDS performs a wave's accesses in order)
-    __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(slot), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add((lds_u32 *)reinterpret_cast<uint32_t *>(slot), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ void lds_counter_wait(float *slot, uint32_t target)
 {
-    volatile uint32_t *c = reinterpret_cast<volatile uint32_t *>(slot);
+    volatile lds_u32 *c = (volatile lds_u32 *)reinterpret_cast<uint32_t *>(slot);
     while (__builtin_amdgcn_readfirstlane(*c) < target) __builtin_amdgcn_s_sleep(1);
     asm volatile("" ::: "memory");
 }

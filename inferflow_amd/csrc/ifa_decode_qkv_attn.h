@@ -19,6 +19,13 @@
 //     to differ from the previous step's; the arena (one region per layer) is zeroed once at allocation, tags are never 0.
 // Every wait is bounded (timeout -> error word -> ifa_model_decode fails loudly); the grid is one workgroup per CU, so all
 // producers of a head are resident whenever its consumer waits.
+// The row stream: every wave requests all its RW rows back to back from one piece of code behind the barrier, its dots wait with
+// counted vmcnt, and nothing in front of the publication is a vector load (see load_rows, locate and lds_counter_wait: the three
+// places where the compiler had put a full wait into the stream).
+// Staged hand-off (IFA_QA_STAGED, off by default): UL instances only -- q | k are published before the v-only rows are multiplied
+// and the tail meets the new token's v behind a second wait.  The non-UL instances keep one publication and one wait: their
+// attention waves are the prologue waves and own weight rows, v rows among them, to the end of the stream (known remainder: the
+// tail on the loader waves, with an LDS region of its own).
 #pragma once
 #include "ifa_decode_kernels.h"
 #include "ifa_decode_attn.h"
@@ -46,7 +53,25 @@ struct DecQkvAttnExtra {
 #ifndef IFA_QA_WARM_ROWS
 #define IFA_QA_WARM_ROWS 1
 #endif
+// IFA_QA_STAGED (measurement, default 0): in the UL instances the q | k rows are published before the v-only rows are multiplied,
+// and the tail waits twice (q | k, then v behind P.V over the old keys: dec_attn_body<.., STG>); 0 = one publication, one wait.
+// Bit-identical.  Measured (profiles/r16_staged_handoff.log): the default bench line 799.5 against 796.6 tok/s with the switch off
+// (run-to-run spread 6: a tie), 16-step calls at 250 / 400 keys 768.6 / 721.6 against 761.3 / 714.3 (+1 %).  Applied to the
+// non-UL instances too (their attention waves own weight rows to the end, so only the publication moves) the 20-step line lost
+// 1.9 % (792.9 against 808.0), so the switch never touches them.  What keeps the early publication from paying more: the compiler
+// still waits for ALL rows (vmcnt(0)) in front of the first stage's stores -- see the note at the publication block.
+#ifndef IFA_QA_STAGED
+#define IFA_QA_STAGED 0
+#endif
 constexpr int QA_THREADS = 512;     // 8 waves: two per SIMD, 256 registers each (the attention tail needs ~140)
+
+// f(integral_constant<int, s>) for the runtime (wave-uniform) s in [1, N]
+template <int N, typename F>
+__device__ __forceinline__ void qa_stage_dispatch(int s, F &&f)
+{
+    if constexpr (N <= 1) f(std::integral_constant<int, 1>{});
+    else { if (s >= N) f(std::integral_constant<int, N>{}); else qa_stage_dispatch<N - 1>(s, f); }
+}
 
 // UL ("unloaded heads", the 256-row bucket): a compute unit pulls ~26 GB/s from HBM however idle the chip is, and a head's cache rows
 // (2 x 256 bytes per key) come through ONE unit -- at 250 keys 128 KB, as much as the unit's share of the weights, and the real step
@@ -88,16 +113,22 @@ __global__ void __launch_bounds__(QA_THREADS) k_dec_qkv_attn(const half_t *px, c
     // waves that take rows, and this wave's place among them (UL: the heads' workgroups are left out)
     const int WGV = UL ? (g_gk - group) * (TH / 64) : g_gk * (TH / 64);
     const int lw = UL ? (bg - bg / per - 1) * (TH / 64) + wave : bg * (TH / 64) + wave;
-    struct Row { const uint8_t *w; const half_t *b; half_t *y; int row, vrow; };
-    // (selects over kernel-argument scalars, like dec_locate: an indexed read of P.W0[] would be a vector load with a vmcnt(0) behind it)
+    typedef __attribute__((address_space(1))) half_t g_half;
+    struct Row { const g_half *b; g_half *y; int row, vrow; bool has_b; };
+    // the three bias and output pointers as scalars (filled behind the first weight requests, below), a lane's choice among them
+    // as SUMS of scalars (like wrow below) into pointers whose address space is stated.  Left to itself the compiler reads the
+    // chosen entry of P.b0[] / P.y[] with a VECTOR load per lane (or builds a table in scratch memory and reads it with FLAT loads):
+    // the newest request of the wave, so that the first publication stage waited -- vmcnt(0) -- for the v-only rows
+    uint64_t pb_q = 0, pb_k = 0, pb_v = 0, py_q = 0, py_k = 0, py_v = 0;
     auto locate = [&](int lr) {
         Row r;
         const int nq = group * HD;
         const bool isk = lr >= nq && lr < nq + HD, isv = lr >= nq + HD;
         r.row = isv ? g * HD + (lr - nq - HD) : (isk ? g * HD + (lr - nq) : g * nq + lr);
-        r.w = isv ? P.W0[2] : (isk ? P.W0[1] : P.W0[0]);
-        r.b = isv ? P.b0[2] : (isk ? P.b0[1] : P.b0[0]);
-        r.y = isv ? P.y[2] : (isk ? P.y[1] : P.y[0]);
+        const uint64_t b = pb_q + (isk ? pb_k - pb_q : 0) + (isv ? pb_v - pb_q : 0);
+        r.has_b = b != 0;
+        r.b = (const g_half *)b;
+        r.y = (g_half *)(py_q + (isk ? py_k - py_q : 0) + (isv ? py_v - py_q : 0));
         r.vrow = isv ? (g_heads + g_kvh) * HD + r.row : (isk ? g_heads * HD + r.row : r.row);
         return r;
     };
@@ -111,18 +142,16 @@ __global__ void __launch_bounds__(QA_THREADS) k_dec_qkv_attn(const half_t *px, c
         const uint64_t q = (uint64_t)pwq, dk = (uint64_t)pwk - q, dv = (uint64_t)pwv - q;
         return (const uint8_t *)(q + (isk ? dk : 0) + (isv ? dv : 0)) + (size_t)row * row_bytes;
     };
+    // Every slot is requested, by every wave, on one path: a slot past the set's last row asks for the wave's slot-0 row again (a
+    // cache hit; the product is not published).  The number of requests behind row i is then a constant, which is what lets the
+    // first publication stage wait with a counted vmcnt while the v-only rows are in flight -- with the slots past the last row
+    // skipped on a path of their own, every wait in front of a dot was a vmcnt(0).
     auto load_rows = [&](int i0, int i1) {
-        const bool full = (RW - 1) * WGV + lw < RG;
-        if (full) {
 #pragma unroll
-            for (int i = 0; i < RW; i++) { if (i < i0 || i >= i1) continue; w[i].load(wrow(i * WGV + lw), g_nblk, lane); }
-        } else {
-#pragma unroll
-            for (int i = 0; i < RW; i++) {
-                if (i < i0 || i >= i1) continue;
-                if (i > 0 && i * WGV + lw >= RG) continue;
-                w[i].load(wrow(min(i * WGV + lw, RG - 1)), g_nblk, lane);
-            }
+        for (int i = 0; i < RW; i++) {
+            if (i < i0 || i >= i1) continue;
+            const int lr = i * WGV + lw;
+            w[i].load(wrow(lr < RG ? lr : min(lw, RG - 1)), g_nblk, lane);
         }
     };
     // the attention tail: workgroup bg == a * (gk / group) of the set runs query head g * group + a, on its waves 0-3 (the
@@ -131,13 +160,14 @@ __global__ void __launch_bounds__(QA_THREADS) k_dec_qkv_attn(const half_t *px, c
     static_assert(NP == 4, "the prologue waves are the attention waves");
     const bool ul_head = UL && attn_wg;
     if (!ul_head && threadIdx.x == TH - 1) { L.part[130] = 0.0f; L.part[131] = 0.0f; }
-    if (!ul_head && wave >= NP) load_rows(0, 1);          // (before the barrier: see k_dec_gemv)
     // the position and the step's tag: scalar loads through pointers of the argument block -- read BEHIND the first weight
     // requests, which need nothing but preloaded scalars
     const int pos = *(const __attribute__((address_space(4))) int *)(A.state + 1);
     // tag of this step's granules: (decode call, position) -- every granule is rewritten every step, so a tag only has to differ
     // from the previous step's (next position of the same call, or another call)
     const unsigned epoch = ((*(const __attribute__((address_space(4))) unsigned *)(E.epoch) + E.epoch_add) << 20) | ((unsigned)pos & 0xFFFFFu);
+    pb_q = (uint64_t)P.b0[0]; pb_k = (uint64_t)P.b0[1]; pb_v = (uint64_t)P.b0[2];
+    py_q = (uint64_t)P.y[0]; py_k = (uint64_t)P.y[1]; py_v = (uint64_t)P.y[2];
     DecAttnFusedIn F;
     F.gran = E.gran; F.epoch = epoch; F.pos = pos; F.err = E.err; F.timeout_ticks = (long long)E.timeout_us * 100;
     F.att_gran = nullptr;
@@ -167,17 +197,23 @@ __global__ void __launch_bounds__(QA_THREADS) k_dec_qkv_attn(const half_t *px, c
                 return;
             }
             DecAttnRegs<HD, Q8, PB, KT> RU;
-            dec_attn_body<HD, Q8, false, PB, KT, true>(smem, nullptr, A.kcache, A.vcache, A.heads, A.kv_heads, A, head, F, RU);
+            // (STG: this workgroup has nothing else to do, so its tail starts at the q | k publication and meets v behind P.V.  The
+            //  other instances' attention waves are the prologue waves: they own weight rows -- v rows among them -- to the end of
+            //  the stream and enter the body when they did, with one wait.  Moving their tail to the loader waves needs a second
+            //  LDS region: the known remainder)
+            dec_attn_body<HD, Q8, false, PB, KT, true, 0, (IFA_QA_STAGED != 0)>(smem, nullptr, A.kcache, A.vcache, A.heads, A.kv_heads, A, head, F, RU);
             return;
         }
     }
     __syncthreads();
     DecAttnRegs<HD, Q8, PB, KT> R;
-    if (wave >= NP) {
-        load_rows(1, RW);
-    } else {
-        pre.finish(P.norm_w, P.norm_b, P.multi_base, P.eps, P.cols, L, P.xn_out, nullptr);
-        load_rows(0, RW);
+    // Every row is requested by ONE piece of code, behind the barrier, by both kinds of wave.  (The loader waves used to request
+    // row 0 in front of the barrier and rows 1 .. behind it, the prologue waves all rows behind their quantiser: at the join the rows
+    // sat in different registers, and the compiler's copies and register reuse put a vmcnt(0) between row 0 and row 1 and a
+    // vmcnt(3) in front of the last row's requests -- twice per launch the stream of a wave stood still for a memory latency.)
+    if (wave < NP) pre.finish(P.norm_w, P.norm_b, P.multi_base, P.eps, P.cols, L, P.xn_out, nullptr);
+    load_rows(0, RW);
+    if (wave < NP) {
 #if IFA_QA_EARLY_KV
         if (attn_wg) dec_attn_body<HD, Q8, false, PB, KT, true, 1>(smem, nullptr, A.kcache, A.vcache, A.heads, A.kv_heads, A, head, F, R);
 #endif
@@ -186,22 +222,54 @@ __global__ void __launch_bounds__(QA_THREADS) k_dec_qkv_attn(const half_t *px, c
     typename Fmt::X X;
     X.load(L.codes, L.scale, L.xsum, lane, g_nblk);
     {
+        // Two-stage publication (IFA_QA_STAGED, UL instances): slots [0, s1) hold every q and k row of the set, slots [s1, RW) v rows
+        // only (s1 = the first slot with i * WGV >= (group + 1) * HD; wave-uniform, from the preloaded geometry).  The first group is
+        // multiplied, reduced and published before the v-only rows are multiplied, so that the heads' workgroups start the tail
+        // early (dec_attn_body<.., STG>).  Per row the arithmetic, the tag, the granule and the r.y store are what they were: only
+        // the order of the instructions moves.  The slots of a stage are compile-time constants (the dots and the reductions of
+        // a stage interleave as before).  Known remainder (ISA of the Q4_B32T1A UL instance): the dots of both stages wait with
+        // counted vmcnt(N), but in front of the first stage's stores the compiler still puts a vmcnt(0) -- the q | k rows
+        // leave a stage of dots early, not the v-share of the stream the hand-off was designed for.
         float a[RW];
 #pragma unroll
-        for (int i = 0; i < RW; i++) a[i] = w[i].dot(X);
+        for (int i = 0; i < RW; i++) a[i] = 0.0f;
+        auto stage = [&](auto lo_c, auto hi_c) {
+            constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value;
+            if constexpr (LO < HI) {
 #pragma unroll
-        for (int i = 0; i < RW; i++) a[i] = wave_sum(a[i]);
-        float a0 = 0.0f;
+                for (int i = LO; i < HI; i++) a[i] = w[i].dot(X);
 #pragma unroll
-        for (int i = 0; i < RW; i++) { if (lane == i) a0 = a[i]; }
-        const int lr = lane * WGV + lw;
-        if (lane < RW && lr < RG) {
-            const Row r = locate(lr);
-            half_t y = dec_bias(a0, r.b, r.row);
-            if (P.pre_scale != 0.0f) y = f2h(h2f(y) * P.pre_scale);
-            r.y[r.row] = y;                                     // (the q | k | v buffer stays available to the debug / op paths)
-            __hip_atomic_store(E.gran + r.vrow, ((unsigned long long)epoch << 32) | (unsigned long long)__builtin_bit_cast(uint16_t, y),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int i = LO; i < HI; i++) a[i] = wave_sum(a[i]);
+                // lane i finishes row slot i.  EVERY lane stores: a lane without a row of this stage repeats the wave's slot-0 row (the
+                // bits of its first publication).  Stores under an exec mask are skipped by a branch, the compiler's count of the
+                // requests in flight then leaves them out, and the waits of the second stage's dots, meant for its last rows, sat
+                // out the first stage's stores instead -- a write-through round trip in front of the v rows' publication.
+                const bool mine = lane >= LO && lane < HI && lane * WGV + lw < RG;
+                float a0 = a[0];
+#pragma unroll
+                for (int i = (LO > 1 ? LO : 1); i < HI; i++) { if (lane == i) a0 = a[i]; }
+                const Row r = locate(mine ? lane * WGV + lw : min(lw, RG - 1));      // (the row slot 0 requested: load_rows)
+                half_t y = f2h(a0);                                  // (dec_bias, through the global pointer)
+                if (r.has_b) y = f2h(h2f(y) + h2f(r.b[r.row]));
+                if (P.pre_scale != 0.0f) y = f2h(h2f(y) * P.pre_scale);
+                r.y[r.row] = y;                                     // (the q | k | v buffer stays available to the debug / op paths)
+                __hip_atomic_store(E.gran + r.vrow, ((unsigned long long)epoch << 32) | (unsigned long long)__builtin_bit_cast(uint16_t, y),
+                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        };
+        auto staged = [&](auto s1_c) {
+            constexpr int S1 = decltype(s1_c)::value;
+            stage(std::integral_constant<int, 0>{}, s1_c);
+            if constexpr (S1 < RW) {
+                if (A.trace && threadIdx.x == 0) A.trace[(size_t)(A.heads + (int)blockIdx.x) * 8 + 2] = wall_clock64();      // qk_published
+            }
+            stage(s1_c, std::integral_constant<int, RW>{});
+        };
+        if constexpr (IFA_QA_STAGED != 0 && UL) {
+            const int s1 = min(RW, ((group + 1) * HD + WGV - 1) / WGV);
+            qa_stage_dispatch<RW>(s1, staged);
+        } else {
+            staged(std::integral_constant<int, RW>{});
         }
     }
     if (A.trace && threadIdx.x == 0) {      // tuning: every workgroup's start / rows-published stamps behind the heads' attention stamps

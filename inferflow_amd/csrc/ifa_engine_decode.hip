@@ -931,7 +931,7 @@ int ifa_model_time_kernel(ifa_model *m, int which, int iters, float *avg_us)
     if (rc) return rc;
     if (m->opt_q3h_native && (rc = ensure_q3hn(m))) return rc;
     hipStream_t s = m->stream;
-    m->host_pinned[0] = 1; m->host_pinned[1] = std::min(m->cfg.max_ctx - 1, 64); m->host_pinned[2] = 0;
+    m->host_pinned[0] = 1; m->host_pinned[1] = std::min(m->cfg.max_ctx - 1, m->opt_time_pos >= 0 ? m->opt_time_pos : 64); m->host_pinned[2] = 0;
     IFA_HIP_CHECK(hipMemcpyAsync(m->state, m->host_pinned, 3 * sizeof(int), hipMemcpyHostToDevice, s));
     auto touch_layer = [&](int l) {
         const int ids[] = {T_WQ, T_WK, T_WV, T_WO, T_W1, T_W3, T_W2};

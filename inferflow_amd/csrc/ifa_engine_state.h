@@ -112,6 +112,7 @@ struct ifa_model : Scratch {
     DevBuf<float> rope_tab;        // device: [head_dim/2][2]
     DevBuf<long long> trace;       // device: [2048][8] optional kernel phase stamps
     int opt_trace = 0, opt_bench_mode = 0, opt_touch_stride = 65536;
+    int opt_time_pos = -1;               // ifa_model_time_kernel: position of the timed launches (-1: 64); the route is the last call's
     PinBuf<int> host_pinned;       // pinned staging for state / tokens
     int scratch_tokens = 0;
     size_t kv_row_bytes = 0;
