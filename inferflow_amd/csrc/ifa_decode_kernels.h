@@ -94,6 +94,9 @@ __device__ __forceinline__ void q8x4_dequant_h(uint32_t w, half2_t sc2, half2_t 
 #ifndef IFA_NT_WEIGHTS
 #define IFA_NT_WEIGHTS 1            // stream weights with the non-temporal policy (read once per token)
 #endif
+#ifndef IFA_DG_EARLY
+#define IFA_DG_EARLY 0              // k_dec_gemv<.., NP>: the loader waves' first row in front of the barrier (measurement switch, see there)
+#endif
 
 // ------------------------------------------------------------------ LDS image
 // of the (normalised and) quantised activation vector
@@ -507,6 +510,95 @@ __device__ __forceinline__ DecRow dec_locate(const DecGemvParams &P, int v)
     return d;
 }
 
+// The same choice with a LANE's virtual row (the epilogue: lane i finishes row i).  dec_locate's `in2 ? P.b0[2] : ...` on a
+// lane-dependent v is compiled into a select of ADDRESSES inside the argument block and one global_load_dwordx2 per pointer from
+// there (cold in the vector cache after every kernel boundary), and the bias value was a second, dependent load: every wave's last
+// store sat behind two vector-memory round trips.  Here the candidates are scalars (read once, behind the first weight requests),
+// a lane's pointer is a SUM of scalars -- base + (in set 1 ? distance of set 1 : 0) + (in set 2 ? ... : 0): a select between three
+// pointers would be turned back into a select of addresses, or into a table in scratch memory -- and the values the epilogue
+// adds (bias, residual) are requested with clamped, unconditional addresses right behind the pass's weights (DecEpiIn::request).
+typedef __attribute__((address_space(1))) half_t dec_g_half;
+constexpr int DEC_NO_SET = 0x7FFFFFFF;
+
+struct DecSets {
+    int e1, e2;                       // first virtual row of set 1 / set 2 (DEC_NO_SET: there is none); e1 <= e2
+    __device__ __forceinline__ void none() { e1 = DEC_NO_SET; e2 = DEC_NO_SET; }
+    __device__ __forceinline__ void from(const DecGemvParams &P)
+    {
+        e1 = P.nsets > 1 ? P.rows[0] : DEC_NO_SET;
+        e2 = P.nsets > 2 ? P.rows[0] + P.rows[1] : DEC_NO_SET;
+    }
+    __device__ __forceinline__ int row(int v) const { return v - (v >= e2 ? e2 : (v >= e1 ? e1 : 0)); }
+    // set 0's pointer, or the pointer of v's set, d1 / d2 being the distances of set 1 / set 2 from set 0
+    __device__ __forceinline__ uint64_t pick(int v, uint64_t p0, uint64_t d1, uint64_t d2) const
+    {
+        return p0 + ((v >= e1 && v < e2) ? d1 : (uint64_t)0) + (v >= e2 ? d2 : (uint64_t)0);
+    }
+};
+
+struct DecEpiPtrs {
+    uint64_t y0, yd1, yd2, b0, bd1, bd2, b1, res, res2, dummy;
+    // (entries of sets a launch does not have are read too -- the argument block is there -- and never chosen)
+    __device__ __forceinline__ void from(const DecGemvParams &P)
+    {
+        y0 = (uint64_t)P.y[0]; yd1 = (uint64_t)P.y[1] - y0; yd2 = (uint64_t)P.y[2] - y0;
+        b0 = (uint64_t)P.b0[0]; bd1 = (uint64_t)P.b0[1] - b0; bd2 = (uint64_t)P.b0[2] - b0;
+        b1 = (uint64_t)P.b1; res = (uint64_t)P.residual; res2 = (uint64_t)P.residual2;
+        dummy = (uint64_t)P.x;            // what an absent vector's request reads instead (two bytes that exist in every launch)
+        asm volatile("" : "+s"(dummy));   // (an opaque scalar from here on: the select in DecEpiIn::request stays a select between two numbers)
+    }
+};
+
+// what lane i adds to row i of a pass: requested behind the pass's weights, used by dec_finish_lane
+struct DecEpiIn {
+    half_t bias0 = (half_t)0, bias1 = (half_t)0, res = (half_t)0, res2 = (half_t)0;
+    template <int EPI>
+    __device__ __forceinline__ void request(const DecSets &S, const DecEpiPtrs &E, int v)      // v: a row of the launch (clamped by the caller)
+    {
+        const int row = S.row(v);
+        auto at = [&](uint64_t p) { return *(const dec_g_half *)(p != 0 ? p + (uint64_t)row * 2 : E.dummy); };
+        bias0 = at(S.pick(v, E.b0, E.bd1, E.bd2));
+        if constexpr (EPI == EPI_GLU || EPI == EPI_MOE_GLU) bias1 = at(E.b1);
+        if constexpr (EPI == EPI_RESIDUAL) { res = at(E.res); res2 = at(E.res2); }
+    }
+};
+
+// lane-local end of a row from those values: dec_row_value's arithmetic and rounding points, nothing read but P's scalars
+template <int EPI>
+__device__ __forceinline__ void dec_finish_lane(const DecGemvParams &P, const DecSets &S, const DecEpiPtrs &E, int v, float a0, float a1, const DecEpiIn &in)
+{
+    const int row = S.row(v);
+    half_t y = f2h(a0);
+    if (S.pick(v, E.b0, E.bd1, E.bd2) != 0) y = f2h(h2f(y) + h2f(in.bias0));          // dec_bias
+    if constexpr (EPI == EPI_RESIDUAL || EPI == EPI_PLAIN) {
+        if (P.pre_scale != 0.0f) y = f2h(h2f(y) * P.pre_scale);      // TensorOpr::Scale (k_scale)
+    }
+    if constexpr (EPI == EPI_RESIDUAL) {
+        y = f2h(h2f(in.res) + h2f(y));                      // TensorOpr::Add (half add)
+        if (E.res2 != 0) y = f2h(h2f(y) + h2f(in.res2));
+        if (P.post_scale != 0.0f) y = f2h(h2f(y) * P.post_scale);
+    } else if constexpr (EPI == EPI_GLU || EPI == EPI_MOE_GLU) {
+        half_t t2 = f2h(a1);
+        if (E.b1 != 0) t2 = f2h(h2f(t2) + h2f(in.bias1));
+        half_t act = f2h(act_fn(h2f(y), P.act_kind));       // TensorOpr::Activation -> F16
+        y = f2h(h2f(act) * h2f(t2));                        // TensorOpr::Mul
+    } else if constexpr (EPI == EPI_ACT || EPI == EPI_MOE_ACT) {
+        y = f2h(act_fn(h2f(y), P.act_kind));
+    } else if constexpr (EPI == EPI_MOE_ACC || EPI == EPI_MOE_LAST) {
+        // (the expert sums: their own vectors are still read here -- no flagship launch, and the step's last expert only)
+        const half_t wexp = P.moe_w[P.moe_slot];
+        const half_t prev = P.moe_slot == 0 ? (half_t)0 : P.moe_acc[row];
+        y = __builtin_fmaf16(y, wexp, prev);                // TensorOpr::AddByRowIndex
+        if constexpr (EPI == EPI_MOE_LAST) {
+            if (P.pre_scale != 0.0f) y = f2h(h2f(y) * P.pre_scale);
+            y = f2h(h2f(y) + h2f(P.residual[row]));         // + residual (Add(ff_out, residual))
+            if (P.residual2) y = f2h(h2f(y) + h2f(P.residual2[row]));
+            if (P.post_scale != 0.0f) y = f2h(h2f(y) * P.post_scale);
+        }
+    }
+    ((dec_g_half *)S.pick(v, E.y0, E.yd1, E.yd2))[row] = y;
+}
+
 // lane-local end of a row: bias, then the epilogue of the fused op sequence
 // res / res2: P.residual[row] / P.residual2[row], requested right behind the row's weights (EPI_RESIDUAL)
 template <int EPI>
@@ -628,49 +720,59 @@ __global__ void __launch_bounds__(TH) k_dec_gemv(const half_t *px, const half_t 
             if constexpr (NM == 2) moeW1c = P.w_table[4 * e2 + P.moe_tab_off + 1];
         }
     }
-    auto moe_pick = [](int si, const uint8_t *a, const uint8_t *b, const uint8_t *c) { return si == 2 ? c : (si == 1 ? b : a); };
-    typename Fmt::W w[NM][RW];
-    auto load_rows = [&](int pass, int i0, int i1) {
-        // rows past the end are not requested at all: clamped re-reads of the last row used to fill the CU's request
-        // window with duplicates (2 of 3 requests of the Wo kernel, 10 % of W1/W3).  `full` is wave-uniform (gw is an
-        // SGPR): a wave whose pass is complete -- every wave of most launches -- takes the straight-line path without
-        // per-row branches; only the first row of a pass is clamped, so that every wave owns defined registers
-        const bool full = (pass * RW + RW - 1) * W + gw < total_rows;
-        auto one = [&](int i) {
-            const int v = min((pass * RW + i) * W + gw, total_rows - 1);
-            if (single) {      // (a uniform branch, not a select: the other arm waits for the argument block)
-                w[0][i].load(pw0 + (size_t)v * row_bytes, nblk_k, lane);
-                if constexpr (NM == 2) w[1][i].load(pw1 + (size_t)v * row_bytes, nblk_k, lane);
-                return;
-            }
-            const DecRow d = dec_locate(P, v);
-            const uint8_t *W0 = epi_is_moe(EPI) ? moe_pick(d.si, moeW0, moeW0b, moeW0c) : d.W0;
-            w[0][i].load(W0 + (size_t)d.row * row_bytes, nblk_k, lane);
-            if constexpr (NM == 2) { const uint8_t *W1 = epi_is_moe(EPI) ? moe_pick(d.si, moeW1, moeW1b, moeW1c) : d.W1; w[1][i].load(W1 + (size_t)d.row * row_bytes, nblk_k, lane); }
-        };
-        if (full) {
-#pragma unroll
-            for (int i = 0; i < RW; i++) { if (i < i0 || i >= i1) continue; one(i); }
+    // The sets of the launch and the matrices' addresses as scalars, fixed HERE, in front of the first request: set 0's matrix and
+    // the distances of set 1 / set 2 from it (DecSets::pick).  A single-matrix launch takes them from the preloaded arguments (a
+    // uniform branch, not a select: the other arm waits for the argument block); the requests behind it are one piece of code for
+    // both kinds of launch, with no scalar load between two of them.
+    DecSets S;
+    uint64_t wa0, wa0d1 = 0, wa0d2 = 0, wa1 = 0, wa1d1 = 0, wa1d2 = 0;
+    if (single) {
+        S.none();
+        wa0 = (uint64_t)pw0; wa1 = (uint64_t)pw1;
+    } else {
+        asm volatile("" ::: "memory");      // (keeps this arm an arm: its loads must not be speculated in front of the branch)
+        S.from(P);
+        if constexpr (epi_is_moe(EPI)) {
+            wa0 = (uint64_t)moeW0; wa0d1 = (uint64_t)moeW0b - wa0; wa0d2 = (uint64_t)moeW0c - wa0;
+            wa1 = (uint64_t)moeW1; wa1d1 = (uint64_t)moeW1b - wa1; wa1d2 = (uint64_t)moeW1c - wa1;
         } else {
+            wa0 = (uint64_t)P.W0[0]; wa0d1 = (uint64_t)P.W0[1] - wa0; wa0d2 = (uint64_t)P.W0[2] - wa0;
+            // (pw1 = P.W1 in every launch, the same matrix for every set.  Written as P.W1 here, the merge of the two arms' values --
+            //  one a preloaded argument, one a field of the argument block -- crashes the compiler's instcombine pass (ROCm 7.2))
+            wa1 = (uint64_t)pw1;
+        }
+    }
+    typename Fmt::W w[NM][RW];
+    // Every slot of a pass is requested, by every wave, on ONE path, back to back: a slot past the launch's last row asks for the
+    // wave's slot-0 row again (clamped to the last row: every address is inside a matrix for every wave, idle ones included; the
+    // product is not stored).  With the slots past the end skipped on a path of their own -- and the rows of the two kinds of
+    // launch requested by two copies of the code -- the compiler's count of the requests in flight differed between the paths and
+    // it put full waits (vmcnt(0)) between the rows of a pass: docs/decode_gemv_stream.md.  v is wave-uniform: scalar arithmetic.
+    auto load_rows = [&](int pass, int i0, int i1) {
+        const int vs0 = min(pass * RW * W + gw, total_rows - 1);
 #pragma unroll
-            for (int i = 0; i < RW; i++) {
-                if (i < i0 || i >= i1) continue;
-                if (i > 0 && (pass * RW + i) * W + gw >= total_rows) continue;
-                one(i);
-            }
+        for (int i = 0; i < RW; i++) {
+            if (i < i0 || i >= i1) continue;
+            const int vi = (pass * RW + i) * W + gw;
+            const int v = vi < total_rows ? vi : vs0;
+            // (such a slot costs one 16-byte block, not a row: every lane asks for the row's LAST block -- the loads clamp the block
+            //  index to nblk - 1.  Whole rows asked for twice were 10 % more requests in the Q4 W1 | W3 launch and 37 % in the Q8 one,
+            //  whose second pass has nothing in slot 1: 494 against 538 tok/s)
+            const int ln = vi < total_rows ? lane : nblk_k;
+            const size_t off = (size_t)S.row(v) * row_bytes;
+            w[0][i].load((const uint8_t *)S.pick(v, wa0, wa0d1, wa0d2) + off, nblk_k, ln);
+            if constexpr (NM == 2) w[1][i].load((const uint8_t *)S.pick(v, wa1, wa1d1, wa1d2) + off, nblk_k, ln);
         }
     };
     auto load_pass = [&](int pass) { load_rows(pass, 0, RW); };
-    // the residual value(s) lane i adds to row i of a pass are requested right behind that pass's weights (clamped,
-    // unconditional): issued from the epilogue they were a second memory round trip at the very end of the kernel
-    half_t res = (half_t)0, res2 = (half_t)0;
+    // what lane i adds to row i of a pass (bias, residuals) is requested right behind that pass's weights (clamped, unconditional:
+    // DecEpiIn): issued from the epilogue these were memory round trips at the very end of the kernel.  The epilogue's pointers are
+    // read as scalars with the first of these requests, i.e. behind the first weight requests.
+    DecEpiPtrs E;
+    DecEpiIn epi_in;
     auto load_epi = [&](int pass) {
-        if constexpr (EPI == EPI_RESIDUAL) {
-            const int v = min((pass * RW + min(lane, RW - 1)) * W + gw, total_rows - 1);
-            const int row = single ? v : dec_locate(P, v).row;
-            res = P.residual[row];
-            if (P.residual2) res2 = P.residual2[row];
-        }
+        if (pass == 0) E.from(P);
+        epi_in.template request<EPI>(S, E, min((pass * RW + min(lane, RW - 1)) * W + gw, total_rows - 1));
     };
     // rows requested BEFORE the cooperative prologue: what the CU's memory pipeline accepts
     // without blocking (~32-48 KiB per CU); a barrier behind blocked loads would only
@@ -700,22 +802,28 @@ __global__ void __launch_bounds__(TH) k_dec_gemv(const half_t *px, const half_t 
             // then costs the prologue waves nothing (they wait ~1 us for the activation anyway) and the stream starts ~0.3 us earlier
             // (NORM == 1 only: the [dim] activation is one or two requests per prologue thread; W2's 11008-value input is six, and weight
             //  requests slipping in between them delayed its quantiser: 8.0 -> 8.7 us)
-            constexpr int EARLY = NORM == 1 ? 1 : 0;
+            // IFA_DG_EARLY (default 0): with it, the rows of a loader wave sit in registers requested on two paths (row 0 in front of the
+            // barrier, the others behind it; the prologue waves request all of theirs behind the quantiser), and at the join the
+            // compiler waited for row 0 -- vmcnt(0) -- in front of row 1's requests: half of the workgroup's waves stood still for a
+            // memory latency before asking for two thirds of their bytes.  Without it every row of both kinds of wave is requested by
+            // the one call below.  Measured both ways: docs/decode_gemv_stream.md.
+            constexpr int EARLY = (IFA_DG_EARLY != 0 && NORM == 1) ? 1 : 0;
             if (EARLY && wave >= NP) load_rows(0, 0, 1);
             trace_on();
             __syncthreads();
-            if (wave >= NP) {
-                load_rows(0, EARLY, RW);
-                load_epi(0);
-                if (P.trace != nullptr && threadIdx.x == NP * 64 && NORM == 1) P.trace[blockIdx.x * 8 + 4] = wall_clock64();
-            } else {
+            if (wave < NP) {
                 if (tr) P.trace[blockIdx.x * 8 + 1] = wall_clock64();
                 pre.finish(P.norm_w, P.norm_b, P.multi_base, P.eps, P.cols, L, P.xn_out,
                            (P.trace != nullptr && threadIdx.x == 0) ? P.trace + blockIdx.x * 8 : nullptr);
-                load_rows(0, 0, RW);
-                load_epi(0);
-                if (tr) P.trace[blockIdx.x * 8 + 2] = wall_clock64();
             }
+            if constexpr (EARLY != 0) {
+                if (wave >= NP) load_rows(0, 1, RW); else load_rows(0, 0, RW);
+            } else {
+                load_rows(0, 0, RW);
+            }
+            load_epi(0);
+            if (wave < NP) { if (tr) P.trace[blockIdx.x * 8 + 2] = wall_clock64(); }
+            else if (P.trace != nullptr && threadIdx.x == NP * 64 && NORM == 1) P.trace[blockIdx.x * 8 + 4] = wall_clock64();
             lds_counter_wait(L.part + 131, NP);
         } else {
         __syncthreads();
@@ -752,9 +860,7 @@ __global__ void __launch_bounds__(TH) k_dec_gemv(const half_t *px, const half_t 
             if (lane == i) { a0 = a[0][i]; if constexpr (NM == 2) a1 = a[1][i]; }
         }
         const int v = (pass * RW + lane) * W + gw;
-        if (lane < RW && v < total_rows) {
-            dec_finish_row<EPI>(P, dec_locate(P, v), a0, a1, res, res2);
-        }
+        if (lane < RW && v < total_rows) dec_finish_lane<EPI>(P, S, E, v, a0, a1, epi_in);
     }
     if (tr) P.trace[blockIdx.x * 8 + 7] = wall_clock64();
 }
@@ -804,10 +910,15 @@ __global__ void __launch_bounds__(DEC_THREADS) k_dec_gemv_long(const DecGemvPara
     float a[RW];
 #pragma unroll
     for (int i = 0; i < RW; i++) a[i] = 0.0f;
+    // the epilogue's pointers as scalars, what lane i adds to row i requested in front of the row's LAST chunk of dots (DecEpiIn)
+    DecSets S; S.from(P);
+    DecEpiPtrs E; E.from(P);
+    DecEpiIn epi_in;
     auto compute = [&](typename Fmt::W (&w)[RW], int q) {
         const int pass = q / nchunk, chunk = q - pass * nchunk;
         typename Fmt::X X;
         X.load(L.codes, L.scale, L.xsum, lane, P.nblk, chunk * 64 * NJ);
+        if (chunk + 1 == nchunk) epi_in.template request<EPI>(S, E, min((pass * RW + min(lane, RW - 1)) * W + gw, P.total_rows - 1));
 #pragma unroll
         for (int i = 0; i < RW; i++) a[i] = w[i].dot(X, a[i]);
         if (chunk + 1 < nchunk) return;
@@ -817,12 +928,7 @@ __global__ void __launch_bounds__(DEC_THREADS) k_dec_gemv_long(const DecGemvPara
 #pragma unroll
         for (int i = 0; i < RW; i++) { if (lane == i) a0 = a[i]; a[i] = 0.0f; }
         const int v = (pass * RW + lane) * W + gw;
-        if (lane < RW && v < P.total_rows) {
-            const DecRow d = dec_locate(P, v);
-            half_t res = (half_t)0, res2 = (half_t)0;
-            if constexpr (EPI == EPI_RESIDUAL) { res = P.residual[d.row]; if (P.residual2) res2 = P.residual2[d.row]; }
-            dec_finish_row<EPI>(P, d, a0, 0.0f, res, res2);
-        }
+        if (lane < RW && v < P.total_rows) dec_finish_lane<EPI>(P, S, E, v, a0, 0.0f, epi_in);
     };
     for (int q = 0; q < Q; q += 2) {
         if (q + 1 < Q) load_q(wb, q + 1, 0, RW);

@@ -116,8 +116,13 @@ __global__ void __launch_bounds__(DEC_THREADS) k_dec_gemv_h(const DecGemvParams 
     const int gw = blockIdx.x * DEC_WAVES + wave;
     const int W = gridDim.x * DEC_WAVES;
     const size_t row_bytes = DT == F16 ? (size_t)P.cols * 2 : (size_t)P.nblk * block_bytes(DT);
+    // the epilogue's pointers as scalars, what lane i adds to row i requested in front of the batch's dots (DecEpiIn, ifa_decode_kernels.h)
+    DecSets S; S.from(P);
+    DecEpiPtrs E; E.from(P);
     for (int v0 = gw; v0 < P.total_rows; v0 += DH_ROWS * W) {
         float a[NM][DH_ROWS];
+        DecEpiIn epi_in;
+        epi_in.template request<EPI>(S, E, min(v0 + min(lane, DH_ROWS - 1) * W, P.total_rows - 1));
 #pragma unroll
         for (int i = 0; i < DH_ROWS; i++) {
             const int v = min(v0 + i * W, P.total_rows - 1);
@@ -135,12 +140,7 @@ __global__ void __launch_bounds__(DEC_THREADS) k_dec_gemv_h(const DecGemvParams 
         for (int i = 0; i < DH_ROWS; i++)
             if (lane == i) { a0 = a[0][i]; if constexpr (NM == 2) a1 = a[1][i]; }
         const int v = v0 + lane * W;
-        if (lane < DH_ROWS && v < P.total_rows) {
-            const DecRow d = dec_locate(P, v);
-            half_t res = (half_t)0, res2 = (half_t)0;
-            if constexpr (EPI == EPI_RESIDUAL) { res = P.residual[d.row]; if (P.residual2) res2 = P.residual2[d.row]; }
-            dec_finish_row<EPI>(P, d, a0, a1, res, res2);
-        }
+        if (lane < DH_ROWS && v < P.total_rows) dec_finish_lane<EPI>(P, S, E, v, a0, a1, epi_in);
     }
 }
 
