@@ -529,7 +529,10 @@ int ifa_model_pool_adjust(ifa_model *m, int n_sel, const int *state_slots_host);
 int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, const int *targets_host,
                             float *lse_host, float *target_logit_host, int *next_token_host);
 /* debugging taps: "logits", "logits_adj" (the rows the last armed pool step adjusted; null before the first), "logit_state" (the
- * logit processors' u32 state rows [slots][vocab]; null before the first reset), "hidden", "kcache", "vcache" (device pointers) */
+ * logit processors' u32 state rows [slots][vocab]; null before the first reset), "hidden", "kcache", "vcache" (device pointers).
+ * "x", "att", "a", "t1", "hidden": ONE row.  "rows_x", "rows_xn", "rows_hn", "rows_att", "rows_a", "rows_t1", "rows_q", "rows_k", "rows_v": all
+ * the rows (scratch_tokens of them: as many as the largest step so far) of the row-major activation buffers a batched or prompt step uses;
+ * "rows_bqkv": the batched step's [32][q | k | v] (null before the first step of <= 32 rows). */
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes);
 void *ifa_model_stream(ifa_model *m);
 /* Test hooks over the worker's memory (every device / pinned block a model owns goes through two counted allocators,
@@ -714,6 +717,23 @@ int ifa_model_prompt_route(ifa_model *m, int *out, int n_out);
  * full_n, rem_n, n_try, ks[2] (parts of K in the order they are tried). */
 int ifa_gemm_mid_plan(const int *facts, int n_facts, int *out, int n_out);
 int ifa_gemm_big_plan(const int *facts, int n_facts, int *out, int n_out);
+/* The launch plan of the rows GEMM (k_gemm_rows_mfma; csrc/ifa_gemm_rows_plan.h, DESIGN.md "Rows GEMM launch plan").  Host-only.
+ * facts[17], in the order of GemmRowsFacts: T, nsets, rows0, rows1, rows2, nblk, epi (0 plain, 1 residual, 2 gated pair), norm, mo, has_w1,
+ * no_waits, waits_on, num_cus, visible_cus, then the settings (0 = default) wgs_per_cu, kparts_off, kparts_min.  out[22], in the order of
+ * GemmRowsPlan: error (0 ok, 1 shape, 2 norm prologue, 3 gated pair, 4 rows, 5 byte offsets past 32 bits, 6 no instance for the epilogue /
+ * norm), total_rows, ntiles, tx (rows staged), ch (1 one chunk, 0 chunk loop, 2 whole rows), chunk_cols, nchunk, n_try, then per attempt in
+ * the order they are tried (kparts, kpm, tiles per workgroup or group, groups, grid, lds, scratch bytes): K parts first where they apply,
+ * the plain launch (kparts 0) last. */
+int ifa_gemm_rows_plan(const int *facts, int n_facts, int *out, int n_out);
+/* The last rows GEMM launches of this process, oldest first; reading clears them.  out[2 + 8 x 23]: out[0] records that follow (at most 8),
+ * out[1] launches since the last read, then per record: T, total_rows, nblk, epi, norm, mo, tx, ch, nchunk, n_try, attempt (index of the
+ * attempt that ran), the attempt's seven plan fields, and -- attempt > 0: the K-parts attempt was declined -- what the residency test saw:
+ * declined_grid, occupancy (workgroups per CU; -1 not asked), visible_cus, waits_on, err_word (the wait-error word exists).  A captured step
+ * records when it is captured, not when it is replayed. */
+int ifa_gemm_rows_launches(int *out, int n_out);
+/* Test hook of that record's ring, host only: rec[23] is pushed as a launch would push it; count_before >= 0 sets the count of launches
+ * since the last read first (the count saturates at 2^31 - 1; the slot index stays in 0 .. 7). */
+int ifa_debug_gemm_rows_record(const int *rec, int n_rec, int count_before);
 
 #ifdef __cplusplus
 }

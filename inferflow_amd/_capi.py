@@ -148,6 +148,9 @@ SIGNATURES = {
     "ifa_model_prompt_route": (_i, [_vp, _vp, _i]),
     "ifa_gemm_mid_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_big_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_gemm_rows_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_gemm_rows_launches": (_i, [_vp, _i]),
+    "ifa_debug_gemm_rows_record": (_i, [_vp, _i, _i]),
     "ifa_model_set_stream": (_i, [_vp, _vp]),
     "ifa_model_tp_begin": (_i, [_vp, _i, _i]),
     "ifa_model_tp_begin_hidden": (_i, [_vp, _vp, _i]),

@@ -662,6 +662,21 @@ int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr,
     else if (!strcmp(name, "attq")) { p = m->attq; b = m->attq ? xq_image_bytes(c.heads * c.head_dim) : 0; }
     else if (!strcmp(name, "a")) { p = m->a; b = (size_t)c.dim * 2; }
     else if (!strcmp(name, "t1")) { p = m->t1; b = (size_t)c.ffn * 2; }
+    else if (!strncmp(name, "rows_", 5)) {      // every row of a step's activation buffers (scratch_tokens rows; bqkv: 32)
+        const size_t R = (size_t)std::max(0, m->scratch_tokens), QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim;
+        const char *n = name + 5;
+        if (!strcmp(n, "x")) { p = m->x; b = R * c.dim * 2; }
+        else if (!strcmp(n, "xn")) { p = m->xn; b = R * c.dim * 2; }
+        else if (!strcmp(n, "hn")) { p = m->hn; b = R * c.dim * 2; }
+        else if (!strcmp(n, "att")) { p = m->att; b = R * QD * 2; }
+        else if (!strcmp(n, "a")) { p = m->a; b = R * c.dim * 2; }
+        else if (!strcmp(n, "t1")) { p = m->t1; b = R * c.ffn * 2; }
+        else if (!strcmp(n, "q")) { p = m->q; b = R * QD * 2; }
+        else if (!strcmp(n, "k")) { p = m->k; b = R * KVD * 2; }
+        else if (!strcmp(n, "v")) { p = m->v; b = R * KVD * 2; }
+        else if (!strcmp(n, "bqkv")) { p = m->bqkv; b = m->bqkv ? (size_t)32 * (QD + 2 * KVD) * 2 : 0; }
+        else return ifa_fail(IFA_ERR_ARG, "ifa_model_get_buffer: unknown buffer '%s'", name);
+    }
     else if (!strcmp(name, "kcache") || !strcmp(name, "vcache")) {
         IFA_REQUIRE(layer >= 0 && layer < c.layers && m->finalized, "ifa_model_get_buffer: layer %d", layer);
         p = name[0] == 'k' ? m->layers[(size_t)layer].kcache : m->layers[(size_t)layer].vcache;

@@ -2,6 +2,7 @@
 #include <cstring>
 #include "ifa_host.h"
 #include "ifa_gemm_plan.h"
+#include "ifa_gemm_rows_plan.h"
 
 using namespace ifa;
 
@@ -25,6 +26,17 @@ int ifa_gemm_big_plan(const int *facts, int n_facts, int *out, int n_out)
     memcpy(&f, facts, sizeof(f));
     IFA_REQUIRE(f.num_cus >= 1, "ifa_gemm_big_plan: num_cus %d", f.num_cus);
     const GemmBigPlan r = plan_gemm_big(f);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
+int ifa_gemm_rows_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    IFA_REQUIRE(facts && out && n_facts == GEMM_ROWS_N_FACTS && n_out >= GEMM_ROWS_N_OUT, "ifa_gemm_rows_plan: %d facts, %d outputs expected", GEMM_ROWS_N_FACTS, GEMM_ROWS_N_OUT);
+    GemmRowsFacts f;
+    memcpy(&f, facts, sizeof(f));
+    IFA_REQUIRE(f.num_cus >= 1 && f.visible_cus >= 0, "ifa_gemm_rows_plan: num_cus %d, visible_cus %d", f.num_cus, f.visible_cus);
+    const GemmRowsPlan r = plan_gemm_rows(f);
     memcpy(out, &r, sizeof(r));
     return IFA_OK;
 }

@@ -24,6 +24,7 @@
 //   * the activation rows sit in LDS as F16, one chunk at a time (row stride + 16 B: conflict-free 16-byte reads); longer
 //     rows (w2) are walked in chunks with the accumulators kept in registers.
 // Measurements behind these choices and what bounds the kernel now: DESIGN.md section 3 "Dynamic batching", section 8.
+#include <atomic>
 #include "ifa_gemm_rows_mfma_body.h"
 
 namespace ifa {
@@ -102,18 +103,6 @@ bool gemm_rows_mfma_ok(size_t rows, size_t cols, size_t tokens)
     return tokens >= 2 && tokens <= 16 && cols % 128 == 0 && rows > 0 && rows < (1u << 24) && cols <= 65536;
 }
 
-static int gm_geometry(size_t rows, int grid_cap, int *wgs, int *maxt)
-{
-    const int ntiles = (int)((rows + 15) / 16);
-    int w = std::min(grid_cap, ntiles);
-    int mt = (ntiles + w - 1) / w;
-    if (mt > 8) { mt = 8; w = (ntiles + 7) / 8; }                // (more workgroups than CUs: they queue)
-    if (mt == 5) mt = 6;
-    if (mt == 7) mt = 8;
-    *wgs = w; *maxt = mt;
-    return IFA_OK;
-}
-
 template <int MT, int TX, int EPI, int NORM>
 static int gm_launch4(int wgs, size_t smem, const GmArgs &P, hipStream_t s)
 {
@@ -147,31 +136,81 @@ static int gm_launch1(int wgs, size_t smem, const GmArgs &P, int epi, int norm, 
     return gm_launch2<MT, 16>(wgs, smem, P, epi, norm, s);
 }
 
+// the settings of the plan, read from the environment once (tuning aids)
+struct RowsSettings { int wgs_per_cu, kparts_off, kparts_min; };
+static const RowsSettings &rows_settings()
+{
+    static const RowsSettings S = [] {
+        RowsSettings s;
+        s.wgs_per_cu = getenv("IFA_ROWS_WGS_PER_CU") ? std::max(1, atoi(getenv("IFA_ROWS_WGS_PER_CU"))) : 1;
+        s.kparts_off = getenv("IFA_ROWS_KPARTS_OFF") ? 1 : 0;       // (A / B)
+        // (from two chunks on: wo of 17..32 queries as two parts 10.5 -> 9.5 us; 32 queries 3.22 -> 3.18 ms)
+        s.kparts_min = getenv("IFA_ROWS_KPARTS_MIN") ? std::max(1, atoi(getenv("IFA_ROWS_KPARTS_MIN"))) : 2;
+        return s;
+    }();
+    return S;
+}
+
+// the facts of a launch (ifa_gemm_rows_plan.h)
+static GemmRowsFacts gemm_rows_facts(const GmArgs &P, int epi, int norm)
+{
+    GemmRowsFacts f;
+    f.T = P.T; f.nsets = P.nsets; f.rows0 = P.rows[0]; f.rows1 = P.rows[1]; f.rows2 = P.rows[2]; f.nblk = P.nblk; f.epi = epi; f.norm = norm;
+    f.mo = P.mo ? 1 : 0; f.has_w1 = P.W1 != nullptr; f.no_waits = P.no_waits; f.waits_on = waits_enabled();
+    f.num_cus = gm_num_cus(); f.visible_cus = visible_cus();
+    const RowsSettings &S = rows_settings();
+    f.wgs_per_cu = S.wgs_per_cu; f.kparts_off = S.kparts_off; f.kparts_min = S.kparts_min;
+    return f;
+}
+
 bool gemm_rows_mfma_fused_ok(const GmArgs &P, int epi, int norm)
 {
-    if (P.T < 2 || P.T > (P.mo ? 32 : 16) || P.nblk <= 0 || P.nblk % 4 != 0 || P.nsets < 1 || P.nsets > 3) return false;      // (17..32 rows: MO layout only)
-    if (norm == 1 && (P.nblk * 32 > GmGeo<32>::CHUNK_COLS || P.T > (P.mo ? 16 : 8))) return false;      // the norm prologue: whole rows in one chunk (tiled layout: <= 8 rows)
-    if (epi == GM_GLU && (P.nsets != 1 || !P.W1)) return false;
-    for (int i = 0; i < P.nsets; i++) if (P.rows[i] <= 0 || (P.nsets > 1 && P.rows[i] % 16 != 0)) return false;
-    for (int i = 0; i < P.nsets; i++)      // 32-bit byte offsets inside a matrix (tiled and MO copies are 20 bytes per block + padding)
-        if (((size_t)P.rows[i] + 16) * ((size_t)P.nblk + 16) * 20 >= ((size_t)1 << 32)) return false;
-    return true;
+    const int e = plan_gemm_rows(gemm_rows_facts(P, epi, norm)).error;
+    return e == GEMM_ROWS_OK || e == GEMM_ROWS_ERR_NO_KERNEL;      // (an instance that does not exist fails the launch with its own message, as ever)
+}
+
+// The last launches (ifa_gemm_rows_launches): plain data behind a flag, one struct copy per launch; nothing here runs at exit.  A captured
+// step records at its capture, never at a replay (the launcher does not run then).
+static GemmRowsLaunchRing g_rows_ring;
+static std::atomic_flag g_rows_rec_busy = ATOMIC_FLAG_INIT;
+static void rows_record(const GemmRowsLaunchRecord &rec)
+{
+    while (g_rows_rec_busy.test_and_set(std::memory_order_acquire)) { }
+    g_rows_ring.push(rec);
+    g_rows_rec_busy.clear(std::memory_order_release);
+}
+static int gemm_rows_launches_take(int *out, int n_out)
+{
+    while (g_rows_rec_busy.test_and_set(std::memory_order_acquire)) { }
+    g_rows_ring.take(out, n_out);
+    g_rows_rec_busy.clear(std::memory_order_release);
+    return IFA_OK;
+}
+// test hook (ifa_debug_gemm_rows_record): count_before >= 0 sets the count of launches since the last read first, then one record is pushed
+static int gemm_rows_record_debug(const int *rec, int count_before)
+{
+    GemmRowsLaunchRecord r;
+    memcpy(&r, rec, sizeof(r));
+    while (g_rows_rec_busy.test_and_set(std::memory_order_acquire)) { }
+    if (count_before >= 0) g_rows_ring.count = count_before;
+    g_rows_ring.push(r);
+    g_rows_rec_busy.clear(std::memory_order_release);
+    return IFA_OK;
 }
 
 int gemm_rows_mfma_launch(const GmArgs &P0, int epi, int norm, hipStream_t s)
 {
     GmArgs P = P0;
-    P.total_rows = 0;
-    for (int i = 0; i < P.nsets; i++) P.total_rows += P.rows[i];
-    if (!gemm_rows_mfma_fused_ok(P, epi, norm)) return ifa_fail(IFA_ERR_ARG, "rows GEMM: shape not covered (T %d, %d blocks, %d sets)", P.T, P.nblk, P.nsets);
-    int wgs, maxt;
-    static const int per_cu = getenv("IFA_ROWS_WGS_PER_CU") ? std::max(1, atoi(getenv("IFA_ROWS_WGS_PER_CU"))) : 1;     // tuning aid
-    gm_geometry((size_t)P.total_rows, gm_num_cus() * (P.T <= 8 ? per_cu : 1), &wgs, &maxt);
-    if (epi == GM_GLU) {                       // pairs of tiles: 1, 2, 3, 4 pairs per workgroup
-        if (maxt > 4) { maxt = 4; wgs = ((P.total_rows + 15) / 16 + 3) / 4; }
-        maxt = maxt == 3 ? 6 : maxt * 2;
-    }
-    const size_t smem = gm_smem(P.T, maxt, P.mo);
+    const GemmRowsPlan plan = plan_gemm_rows(gemm_rows_facts(P, epi, norm));
+    if (plan.error == GEMM_ROWS_ERR_NO_KERNEL) return ifa_fail(IFA_ERR_ARG, "rows GEMM%s: no kernel for epilogue %d / norm %d", P.mo ? " (MO)" : "", epi, norm);
+    if (plan.error) return ifa_fail(IFA_ERR_ARG, "rows GEMM: shape not covered (T %d, %d blocks, %d sets; plan error %d)", P.T, P.nblk, P.nsets, plan.error);
+    P.total_rows = plan.total_rows;
+    const GemmRowsTry &plain = plan.tries[plan.n_try - 1];
+    const int wgs = plain.grid, maxt = plain.tiles;
+    const size_t smem = (size_t)plain.lds;
+    GemmRowsLaunchRecord rec;
+    rec.T = P.T; rec.total_rows = plan.total_rows; rec.nblk = P.nblk; rec.epi = epi; rec.norm = norm; rec.mo = P.mo ? 1 : 0;
+    rec.tx = plan.tx; rec.ch = plan.ch; rec.nchunk = plan.nchunk; rec.n_try = plan.n_try; rec.attempt = plan.n_try - 1; rec.ran = plain;
     static const bool tracing = getenv("IFA_ROWS_TRACE") != nullptr;     // tuning aid: eager launches only (it synchronises)
     static long long *trace_dev = nullptr;
     if (tracing) {
@@ -180,7 +219,7 @@ int gemm_rows_mfma_launch(const GmArgs &P0, int epi, int norm, hipStream_t s)
         P.trace = trace_dev;
     }
     int rc;
-    if (P.mo) rc = gemm_rows_mo_launch(P, epi, norm, wgs, maxt, s);
+    if (P.mo) rc = gemm_rows_mo_launch(P, epi, norm, plan, rec, s);
     else switch (maxt) {
     case 1: rc = gm_launch1<1>(wgs, smem, P, epi, norm, s); break;
     case 2: rc = gm_launch1<2>(wgs, smem, P, epi, norm, s); break;
@@ -189,6 +228,7 @@ int gemm_rows_mfma_launch(const GmArgs &P0, int epi, int norm, hipStream_t s)
     case 6: rc = gm_launch1<6>(wgs, smem, P, epi, norm, s); break;
     default: rc = gm_launch1<8>(wgs, smem, P, epi, norm, s); break;
     }
+    if (rc == IFA_OK) rows_record(rec);
     if (tracing && rc == IFA_OK) {
         std::vector<long long> h((size_t)wgs * 32);
         IFA_HIP_CHECK(hipStreamSynchronize(s));
@@ -256,8 +296,8 @@ int gemm_rows_mfma_grouped(const MoeSmallGroup &grp, size_t rows, size_t cols, c
     if (!gemm_rows_mfma_ok(rows, cols, 2)) return ifa_fail(IFA_ERR_STATE, "grouped rows GEMM: %zu x %zu", rows, cols);
     if (max_groups <= 0) return IFA_OK;
     if (max_rows > 8) return ifa_fail(IFA_ERR_ARG, "grouped rows GEMM: groups of up to %d rows (limit 8)", max_rows);
-    int wgs, maxt;
-    gm_geometry(rows, std::max(32, 2 * gm_num_cus() / max_groups), &wgs, &maxt);     // the experts share the chip
+    int wgs = 0;
+    const int maxt = gm_tiles_per_workgroup((int)((rows + 15) / 16), std::max(32, 2 * gm_num_cus() / max_groups), false, &wgs);     // the experts share the chip
     const size_t smem = gm_smem(8, maxt, 0);
     switch (maxt) {
     case 1: return gm_launch_grouped<1>(wgs, max_groups, smem, grp, rows, cols, X, Y, s);
@@ -318,3 +358,18 @@ int gemm_rows_mo_build(int dtype, const void *tiled, size_t rows, size_t cols, v
 }
 
 } // namespace ifa
+
+// the last rows GEMM launches of this process, oldest first, read and cleared (tests): out[0] = records that follow (<= 8), out[1] = launches
+// since the last read, then GEMM_ROWS_N_RECORD ints per record in the order of GemmRowsLaunchRecord's fields (ifa_gemm_rows_plan.h)
+extern "C" int ifa_gemm_rows_launches(int *out, int n_out)
+{
+    IFA_REQUIRE(out && n_out >= 2 + ifa::GEMM_ROWS_N_RECORD * ifa::GEMM_ROWS_RECORDS, "ifa_gemm_rows_launches: %d outputs expected", 2 + ifa::GEMM_ROWS_N_RECORD * ifa::GEMM_ROWS_RECORDS);
+    return ifa::gemm_rows_launches_take(out, n_out);
+}
+// test hook of the record's ring (host only): rec[23] is pushed as a launch would push it; count_before >= 0: the count of launches since
+// the last read is set to it first (so that a test reaches the count's saturation without two billion launches)
+extern "C" int ifa_debug_gemm_rows_record(const int *rec, int n_rec, int count_before)
+{
+    IFA_REQUIRE(rec && n_rec == ifa::GEMM_ROWS_N_RECORD, "ifa_debug_gemm_rows_record: %d ints expected", ifa::GEMM_ROWS_N_RECORD);
+    return ifa::gemm_rows_record_debug(rec, count_before);
+}

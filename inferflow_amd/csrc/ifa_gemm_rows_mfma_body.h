@@ -12,6 +12,7 @@
 #include "ifa_decode_kernels.h"
 #include "ifa_moe.h"
 #include "ifa_gemm_rows_mfma.h"
+#include "ifa_gemm_rows_plan.h"
 #include "ifa_dequant_q4.h"
 
 namespace ifa {
@@ -21,7 +22,7 @@ typedef float f4m __attribute__((ext_vector_type(4)));
 typedef float f2m __attribute__((ext_vector_type(2)));
 typedef _Float16 h2m __attribute__((ext_vector_type(2)));
 
-constexpr int GM_THREADS = 512, GM_WAVES = 8;
+// (GM_THREADS = 512, GM_WAVES = 8 and the byte counts below: ifa_gemm_rows_plan.h, which sizes the LDS from them)
 // Geometry by CS = supersteps (128 columns) per LDS chunk of the activation rows: 32 (4096 columns: up to 8 rows fit next to
 // the waves' patches) or 16 (2048 columns: up to 16 rows).  A wave's share of a chunk is BPW = CS / 2 blocks per row.
 template <int CS> struct GmGeo {
@@ -38,6 +39,9 @@ template <int CS> struct GmGeo {
     static constexpr int XR = GM_THREADS / PIECES;              // rows staged side by side: 1 or 2
 };
 constexpr int gm_cs(int tx) { return tx > 8 ? 16 : 32; }
+static_assert(GmGeo<32>::CHUNK_COLS == gm_chunk_cols(32) && GmGeo<16>::CHUNK_COLS == gm_chunk_cols(16) && GmGeo<32>::ROW_STRIDE == gm_row_stride(32)
+              && GmGeo<16>::ROW_STRIDE == gm_row_stride(16) && GmGeo<32>::PATCH_BYTES == gm_patch_bytes(32) && GmGeo<16>::PATCH_BYTES == gm_patch_bytes(16),
+              "the plan (ifa_gemm_rows_plan.h) sizes the LDS from the kernel's geometry");
 template <int NI> struct GmGrpT { u32x4 c[NI]; u32x4 sb; };
 
 struct GmTile { const uint8_t *W0; const half_t *b0; half_t *y; int row0, nrows, vrow0, ldy; };
@@ -645,22 +649,10 @@ __global__ void __launch_bounds__(GM_THREADS) k_gemm_rows_mfma(const GmArgs P)
     gemm_rows_mfma_body<MAXT, TX, EPI, NORM, MO, CH, KPM>(P, smem);
 }
 
-static int gm_tx(int T) { return T <= 2 ? 2 : (T <= 4 ? 4 : (T <= 8 ? 8 : 16)); }
-// whole-row staging (CH == 2): tx rows of K columns
-static size_t gm_smem_whole(int tx, int K, int maxt) { return std::max((size_t)tx * ((size_t)K * 2 + 16), (size_t)maxt * GM_WAVES * 256 * 4); }
-static size_t gm_smem(int T, int maxt, int mo)
-{
-    const int tx = mo ? (T <= 2 ? 2 : (T <= 4 ? 4 : (T <= 8 ? 8 : (T <= 16 ? 16 : 32)))) : gm_tx(T);
-    if (mo && tx == 32) return std::max((size_t)32 * GmGeo<16>::ROW_STRIDE, (size_t)2 * maxt * GM_WAVES * 256 * 4);
-    if (mo) return std::max((size_t)tx * GmGeo<32>::ROW_STRIDE + (size_t)16 * GM_WAVES * 4, (size_t)maxt * GM_WAVES * 256 * 4);
-    const size_t row = tx > 8 ? GmGeo<16>::ROW_STRIDE : GmGeo<32>::ROW_STRIDE, patch = tx > 8 ? GmGeo<16>::PATCH_BYTES : GmGeo<32>::PATCH_BYTES;
-    const size_t ximg = (size_t)tx * row + (size_t)GM_WAVES * patch + 8 * GM_WAVES * 4;      // + the norm's group sums
-    const size_t parts = (size_t)maxt * GM_WAVES * 256 * 4;
-    return std::max(ximg, parts);
-}
+// (gm_smem, gm_smem_whole, the rows staged: ifa_gemm_rows_plan.h)
 
-// MO-layout kernels (ifa_gemm_rows_mo.hip); wgs / maxt from gemm_rows_mfma_launch's geometry
-int gemm_rows_mo_launch(const GmArgs &P, int epi, int norm, int wgs, int maxt, hipStream_t s);
+// MO-layout kernels (ifa_gemm_rows_mo.hip): the attempts of the plan in order; rec: the launch record to complete (attempt that ran, what declined)
+int gemm_rows_mo_launch(const GmArgs &P, int epi, int norm, const GemmRowsPlan &plan, GemmRowsLaunchRecord &rec, hipStream_t s);
 // the experts with 2..8 rows of a mixture-of-experts layer on their MO copies; glu: w1 / w3 pairs with act(.) * (.) as the output
 int gemm_rows_mo_grouped(const MoeSmallGroup &grp, size_t rows, size_t cols, const void *X, void *Y, int max_groups, int glu, int act_kind, hipStream_t s);
 

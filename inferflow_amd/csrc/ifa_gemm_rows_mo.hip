@@ -8,19 +8,10 @@
 
 namespace ifa {
 
-static int dec_num_cus_rows()
-{
-    static int ncu = 0;
-    if (!ncu) { int dev = 0; hipDeviceProp_t prop; ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256; }
-    return ncu;
-}
 // per-(device, stream) scratch of the K-parts launches: the parts' tile sums as 8-byte {tag, value} granules, zero between launches
 struct KPartsScratch { void *p = nullptr; size_t bytes = 0; };
 static std::mutex g_kparts_mu;
 static std::map<std::pair<int, hipStream_t>, KPartsScratch> g_kparts;
-static const int g_rows_kparts_off = getenv("IFA_ROWS_KPARTS_OFF") ? 1 : 0;       // tuning aid (A / B)
-// (from two chunks on: wo of 17..32 queries as two parts 10.5 -> 9.5 us; 32 queries 3.22 -> 3.18 ms)
-static const int KPARTS_MIN_CHUNKS = getenv("IFA_ROWS_KPARTS_MIN") ? atoi(getenv("IFA_ROWS_KPARTS_MIN")) : 2;
 static int rows_kparts_scratch(hipStream_t s, size_t need, void **out)
 {
     int dev = 0;
@@ -61,12 +52,12 @@ void rows_kparts_release(int dev, hipStream_t s)
 }
 
 template <int MT, int KPM>
-static int mo_launch_kparts(int wgs, size_t smem, const GmArgs &P, int epi, hipStream_t s)
+static int mo_launch_kparts(int wgs, size_t smem, const GmArgs &P, int epi, WaitGridSeen &seen, hipStream_t s)
 {
     // returns 1 (nothing launched) when the grid cannot be resident at once: the caller takes the launch without K parts
 #define IFA_KP(TXV, EPIV) { auto kern = k_gemm_rows_mfma<MT, TXV, EPIV, 0, true, 0, KPM>; \
         if (smem > 48 * 1024) IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        if (!wait_grid_fits((const void *)kern, GM_THREADS, smem, wgs)) return 1; \
+        if (!wait_grid_fits((const void *)kern, GM_THREADS, smem, wgs, &seen)) return 1; \
         kern<<<dim3((unsigned)wgs), dim3(GM_THREADS), smem, s>>>(P); }
     if (P.T <= 16) { if (epi == GM_PLAIN) IFA_KP(16, GM_PLAIN) else IFA_KP(16, GM_RESIDUAL) }
     else { if (epi == GM_PLAIN) IFA_KP(32, GM_PLAIN) else IFA_KP(32, GM_RESIDUAL) }
@@ -139,12 +130,13 @@ static int mo_launch_whole(int wgs, size_t smem, const GmArgs &P, int epi, hipSt
     return ifa_fail(IFA_ERR_ARG, "rows GEMM (MO, whole rows): no kernel for epilogue %d", epi);
 }
 
-int gemm_rows_mo_launch(const GmArgs &P, int epi, int norm, int wgs, int maxt, hipStream_t s)
+int gemm_rows_mo_launch(const GmArgs &P, int epi, int norm, const GemmRowsPlan &plan, GemmRowsLaunchRecord &rec, hipStream_t s)
 {
-    const bool one = P.nblk * 32 <= GmGeo<32>::CHUNK_COLS && P.T <= 16;
-    const int K = P.nblk * 32;
-    if (!one && norm == 0 && P.T <= 4 && K <= 16384 && (epi == GM_PLAIN || epi == GM_RESIDUAL) && gm_smem_whole(P.T <= 2 ? 2 : 4, K, maxt) <= (size_t)150 * 1024) {
-        const size_t smw = gm_smem_whole(P.T <= 2 ? 2 : 4, K, maxt);
+    const GemmRowsTry &plain = plan.tries[plan.n_try - 1];
+    const int wgs = plain.grid, maxt = plain.tiles;
+    const bool one = plan.ch == 1;
+    if (plan.ch == 2) {      // 2..4 rows longer than one chunk, no norm: staged whole
+        const size_t smw = (size_t)plain.lds;
         switch (maxt) {
         case 1: return mo_launch_whole<1>(wgs, smw, P, epi, s);
         case 2: return mo_launch_whole<2>(wgs, smw, P, epi, s);
@@ -154,50 +146,40 @@ int gemm_rows_mo_launch(const GmArgs &P, int epi, int norm, int wgs, int maxt, h
         default: return mo_launch_whole<8>(wgs, smw, P, epi, s);
         }
     }
-    if (norm == 1 && !one) return ifa_fail(IFA_ERR_ARG, "rows GEMM (MO): the norm prologue needs the whole row in one chunk");
-    // K parts (GmArgs::kparts): 9..32 rows walking two chunks or more (one tile per workgroup before: maxt 1 or 2).  Every workgroup stages T rows of EVERY chunk for its
+    // K parts (GmArgs::kparts; the plan's first attempt where they apply): 9..32 rows walking two chunks or more (one tile per workgroup before: maxt 1 or 2).  Every workgroup stages T rows of EVERY chunk for its
     // tiles: at 32 queries w2 (256 tiles, K = 11008: six 2048-column chunks) moved 180 MB of activations L2 -> LDS for 25 MB of
     // weights and ran at the L2's ~10 TB/s (21 us, rows-trace).  With kparts = the chunk count a workgroup takes ONE chunk of kparts
     // times as many tiles (rows staged once: 33 MB in all) and finishes its share of them (reduce-scatter of the fp32 tile sums).
-    if (!one && norm == 0 && (epi == GM_PLAIN || epi == GM_RESIDUAL) && P.T >= 9 && !g_rows_kparts_off && !P.no_waits && waits_enabled() && (maxt == 1 || maxt == 2)) {
-        const int chunk_sup = P.T <= 16 ? 32 : 16, nsup = P.nblk / 4, nchunk = (nsup + chunk_sup - 1) / chunk_sup;
-        int kparts = 0;
-        // (every workgroup of a group must be resident at once -- the finishers poll their group's other parts: a workgroup that
-        //  waits for a free CU delays its whole group by a kernel's length (w2, 258 workgroups: median end 14.6 us, the last group 27))
-        const int ntiles_all = (P.total_rows + 15) / 16;
-        for (int d = std::min(nchunk, 8 / maxt); d >= 2 && nchunk >= KPARTS_MIN_CHUNKS; d--) {
-            if (nchunk % d != 0 || maxt * d == 5 || maxt * d == 7) continue;
-            if ((ntiles_all + maxt * d - 1) / (maxt * d) * d > std::min(dec_num_cus_rows(), visible_cus())) continue;
-            kparts = d; break;
+    // (every workgroup of a group must be resident at once -- the finishers poll their group's other parts: a workgroup that
+    //  waits for a free CU delays its whole group by a kernel's length (w2, 258 workgroups: median end 14.6 us, the last group 27))
+    if (plan.n_try > 1) {
+        const GemmRowsTry &kp = plan.tries[0];
+        GmArgs Q = P;
+        void *scratch = nullptr;
+        int rc = rows_kparts_scratch(s, (size_t)kp.scratch, &scratch);
+        if (rc) return rc;
+        Q.kparts = kp.kparts; Q.kpart_sums = (unsigned long long *)scratch; Q.wait_err = wait_err_word();
+        const size_t smem_k = (size_t)kp.lds;
+        const int wgs_k = kp.grid;
+        WaitGridSeen seen = {0, 0, 0, 0};
+        int rk = 1;        // 1: not launched (the grid cannot be resident at once) -> the plain launch below
+        if (kp.kpm == 1) switch (kp.tiles) {
+            case 2: rk = mo_launch_kparts<2, 1>(wgs_k, smem_k, Q, epi, seen, s); break;
+            case 3: rk = mo_launch_kparts<3, 1>(wgs_k, smem_k, Q, epi, seen, s); break;
+            case 4: rk = mo_launch_kparts<4, 1>(wgs_k, smem_k, Q, epi, seen, s); break;
+            case 6: rk = mo_launch_kparts<6, 1>(wgs_k, smem_k, Q, epi, seen, s); break;
+            case 8: rk = mo_launch_kparts<8, 1>(wgs_k, smem_k, Q, epi, seen, s); break;
+            default: break;
+        } else switch (kp.tiles) {
+            case 4: rk = mo_launch_kparts<4, 2>(wgs_k, smem_k, Q, epi, seen, s); break;
+            case 6: rk = mo_launch_kparts<6, 2>(wgs_k, smem_k, Q, epi, seen, s); break;
+            case 8: rk = mo_launch_kparts<8, 2>(wgs_k, smem_k, Q, epi, seen, s); break;
+            default: break;
         }
-        if (kparts >= 2) {
-            const int ntiles = (P.total_rows + 15) / 16, maxt_k = maxt * kparts, groups = (ntiles + maxt_k - 1) / maxt_k;
-            const int NTc = P.T > 16 ? 2 : 1;
-            GmArgs Q = P;
-            void *scratch = nullptr;
-            int rc = rows_kparts_scratch(s, (size_t)groups * maxt_k * kparts * NTc * 256 * 8, &scratch);
-            if (rc) return rc;
-            Q.kparts = kparts; Q.kpart_sums = (unsigned long long *)scratch; Q.wait_err = wait_err_word();
-            const size_t smem_k = gm_smem(P.T, maxt_k, 1);
-            const int wgs_k = groups * kparts;
-            int rk = 1;        // 1: not launched (no instance for this shape, or the grid cannot be resident at once) -> the plain launch below
-            if (maxt == 1) switch (maxt_k) {
-                case 2: rk = mo_launch_kparts<2, 1>(wgs_k, smem_k, Q, epi, s); break;
-                case 3: rk = mo_launch_kparts<3, 1>(wgs_k, smem_k, Q, epi, s); break;
-                case 4: rk = mo_launch_kparts<4, 1>(wgs_k, smem_k, Q, epi, s); break;
-                case 6: rk = mo_launch_kparts<6, 1>(wgs_k, smem_k, Q, epi, s); break;
-                case 8: rk = mo_launch_kparts<8, 1>(wgs_k, smem_k, Q, epi, s); break;
-                default: break;
-            } else switch (maxt_k) {
-                case 4: rk = mo_launch_kparts<4, 2>(wgs_k, smem_k, Q, epi, s); break;
-                case 6: rk = mo_launch_kparts<6, 2>(wgs_k, smem_k, Q, epi, s); break;
-                case 8: rk = mo_launch_kparts<8, 2>(wgs_k, smem_k, Q, epi, s); break;
-                default: break;
-            }
-            if (rk != 1) return rk;
-        }
+        if (rk != 1) { rec.attempt = 0; rec.ran = kp; return rk; }
+        rec.declined_grid = wgs_k; rec.occupancy = seen.occupancy; rec.visible_cus = seen.visible_cus; rec.waits_on = seen.waits_on; rec.err_word = seen.err_word;
     }
-    const size_t smem = gm_smem(P.T, maxt, 1);
+    const size_t smem = (size_t)plain.lds;
     switch (maxt) {
     case 1: return mo_launch1<1>(wgs, smem, P, epi, norm, one, s);
     case 2: return mo_launch1<2>(wgs, smem, P, epi, norm, one, s);
@@ -257,15 +239,8 @@ int gemm_rows_mo_grouped(const MoeSmallGroup &grp, size_t rows, size_t cols, con
     if (!ncu) { int dev = 0; hipDeviceProp_t prop; ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256; }
     // the experts share the chip: two workgroups fit a CU (66 KB of LDS each), so up to 2 * CUs / groups workgroups per expert
     const int ntiles = (int)((rows + 15) / 16), cap = std::max(32, 2 * ncu / max_groups);
-    int w = std::min(cap, ntiles), mt = (ntiles + w - 1) / w;
-    if (glu) {                          // pairs (w1 tile, w3 tile): 1..4 pairs per workgroup
-        if (mt > 4) { mt = 4; w = (ntiles + 3) / 4; }
-        mt = mt == 3 ? 6 : mt * 2;
-    } else {
-        if (mt > 8) { mt = 8; w = (ntiles + 7) / 8; }
-        if (mt == 5) mt = 6;
-        if (mt == 7) mt = 8;
-    }
+    int w = 0;
+    const int mt = gm_tiles_per_workgroup(ntiles, cap, glu != 0, &w);      // (glu: pairs (w1 tile, w3 tile), 1..4 pairs per workgroup)
     const bool one = cols <= (size_t)GmGeo<32>::CHUNK_COLS;
     const size_t smem = gm_smem(8, mt, 1);
 #define IFA_MOG(MTV) \

@@ -37,5 +37,7 @@ void waits_disable(const char *why);
 // after a synchronisation of the stream: IFA_OK, or the failure a timed-out wait left (word cleared, waits switched off)
 int wait_err_check(const char *who);
 int visible_cus();                                               // CUs of the current device this process can occupy
-bool wait_grid_fits(const void *kernel, int threads, size_t smem_bytes, long long grid);
+// seen (optional): what the answer was made from -- for a caller that records why a waiting launch was declined
+struct WaitGridSeen { int occupancy, visible_cus, waits_on, err_word; };      // (occupancy -1: not asked, an earlier test had said no)
+bool wait_grid_fits(const void *kernel, int threads, size_t smem_bytes, long long grid, WaitGridSeen *seen = nullptr);
 }

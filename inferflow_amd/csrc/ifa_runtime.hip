@@ -171,10 +171,13 @@ int visible_cus_uncached()
 }
 
 static std::map<std::pair<const void *, size_t>, int> g_occ;
-bool wait_grid_fits(const void *kernel, int threads, size_t smem_bytes, long long grid)
+bool wait_grid_fits(const void *kernel, int threads, size_t smem_bytes, long long grid, WaitGridSeen *seen)
 {
+    if (seen) { seen->occupancy = -1; seen->visible_cus = 0; seen->waits_on = 0; seen->err_word = 0; }
     if (!waits_enabled()) return false;
+    if (seen) seen->waits_on = 1;
     if (!wait_err_word()) return false;      // a timed-out wait could not be reported: the launches that wait are not chosen
+    if (seen) seen->err_word = 1;
     int occ = 0;
     {
         std::lock_guard<std::mutex> lk(g_wait_mu);
@@ -185,6 +188,7 @@ bool wait_grid_fits(const void *kernel, int threads, size_t smem_bytes, long lon
             g_occ[std::make_pair(kernel, smem_bytes * 4096 + (size_t)threads)] = occ;
         }
     }
+    if (seen) { seen->occupancy = occ; seen->visible_cus = visible_cus(); }
     return ifa_wait_grid_decision(occ, visible_cus(), grid) != 0;
 }
 

@@ -423,6 +423,40 @@ def gemv_plan(dtype, epi, norm, cols, total_rows, num_cus=256, rpw=0, x_add=0):
     return d
 
 
+GEMM_ROWS_FACTS = ("T", "nsets", "rows0", "rows1", "rows2", "nblk", "epi", "norm", "mo", "has_w1", "no_waits", "waits_on", "num_cus", "visible_cus",
+                   "wgs_per_cu", "kparts_off", "kparts_min")
+GEMM_ROWS_TRY = ("kparts", "kpm", "tiles", "groups", "grid", "lds", "scratch")
+GEMM_ROWS_RECORD = ("T", "total_rows", "nblk", "epi", "norm", "mo", "tx", "ch", "nchunk", "n_try", "attempt") + GEMM_ROWS_TRY + (
+    "declined_grid", "occupancy", "visible_cus", "waits_on", "err_word")
+
+
+def gemm_rows_plan(T, rows, cols, epi=0, norm=0, mo=1, num_cus=256, visible_cus=None, **over):
+    """ifa_gemm_rows_plan: the pure launch plan of the rows GEMM (csrc/ifa_gemm_rows_plan.h, no device) as a dict: error, total_rows,
+    ntiles, tx, ch, chunk_cols, nchunk, tries = [dict of GEMM_ROWS_TRY] in the order they are tried.  rows: the rows of the 1..3 sets."""
+    rows = tuple(rows) + (0,) * (3 - len(tuple(rows)))
+    f = dict(T=T, nsets=len([r for r in rows if r]) or 1, rows0=rows[0], rows1=rows[1], rows2=rows[2], nblk=cols // 32, epi=epi, norm=norm, mo=mo,
+             has_w1=1, no_waits=0, waits_on=1, num_cus=num_cus, visible_cus=num_cus if visible_cus is None else visible_cus, wgs_per_cu=0,
+             kparts_off=0, kparts_min=0)
+    f.update(over)
+    facts = (C.c_int * len(GEMM_ROWS_FACTS))(*[int(f[k]) for k in GEMM_ROWS_FACTS])
+    out = (C.c_int * 22)()
+    check(lib().ifa_gemm_rows_plan(facts, len(GEMM_ROWS_FACTS), out, 22))
+    v = list(out)
+    d = dict(zip(("error", "total_rows", "ntiles", "tx", "ch", "chunk_cols", "nchunk"), v[:7]))
+    d["tries"] = [dict(zip(GEMM_ROWS_TRY, v[8 + 7 * i:15 + 7 * i])) for i in range(v[7])]
+    return d
+
+
+def gemm_rows_launches():
+    """ifa_gemm_rows_launches: (records, launches since the last read); records: the last (at most 8) rows GEMM launches of this process,
+    oldest first, as dicts of GEMM_ROWS_RECORD.  Reading clears them."""
+    n = len(GEMM_ROWS_RECORD)
+    out = (C.c_int * (2 + 8 * n))()
+    check(lib().ifa_gemm_rows_launches(out, len(out)))
+    v = list(out)
+    return [dict(zip(GEMM_ROWS_RECORD, v[2 + i * n:2 + (i + 1) * n])) for i in range(v[0])], v[1]
+
+
 def rng_state_of_seed(seed):
     """the 48-bit state of the java.util.Random generator right after seeding it with `seed`"""
     return (int(seed) ^ 0x5DEECE66D) & ((1 << 48) - 1)

@@ -42,7 +42,7 @@ the worst row is the oracle's value bit for bit (its distance from float64 is d_
 Flips: no row of any prologue launch (dense and tail-only inputs; 1332 launches) was outside the exact bound -- 0.00 % of the rows on
 the flip term, 0 flips needed, for every format and role -- so F = 0 + 1.
 
-Remaining gaps: the MoE epilogues, the x_add (tensor-parallel seam) instances, the batched rows GEMM; the chained and fused-tail launches
+Remaining gaps: the MoE epilogues, the x_add (tensor-parallel seam) instances (the batched rows GEMM: tests/test_gpu_rows_gemm_edges.py); the chained and fused-tail launches
 have their own bit-identity tests against these single launches (tests/test_gpu_chain.py, tests/test_gpu_fused_attn.py)."""
 import numpy as np
 import pytest

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from inferflow_amd import dtypes as dt, synth
+from inferflow_amd import dtypes as dt, synth, worker as W
 from tests import gpu_util as g
 
 pytestmark = pytest.mark.gpu
@@ -67,13 +67,21 @@ def test_rows_kparts_option_switches_the_waiting_launch_off(n):
     V = s["vocab"]
     wk.kv_slots(n)
     cur, pos = _prefill_slots(wk, V, n, 23)
-    out = {}
+    out, w2 = {}, {}
     for v in (1, 0):
         wk.set_option("rows_kparts", v)
         lg = torch.empty((n, V), dtype=torch.float16, device="cuda")
+        W.gemm_rows_launches()
         out[v] = (wk.decode_batch(cur, pos, list(range(n)), lg), g.host(lg).copy())      # (same position: the step rewrites the same cache rows)
+        recs, total = W.gemm_rows_launches()
+        assert total == 4 * s["layers"], total
+        w2[v] = [r for r in recs if r["epi"] == 1 and r["nblk"] == s["ffn"] // 32]       # (the last launches: W2 of every layer among them)
+        assert len(w2[v]) >= 1, recs
     ok, why = _close(out[1][1], out[0][1])
     assert ok, why
+    # the record of what ran: option 1 a K-parts attempt on W2, option 0 the plain chunk loop
+    assert all(r["attempt"] == 0 and r["kparts"] >= 2 and r["n_try"] == 2 for r in w2[1]), w2[1]
+    assert all(r["kparts"] == 0 and r["n_try"] == 1 for r in w2[0]), w2[0]
     wk.close()
 
 
