@@ -735,6 +735,21 @@ int ifa_gemm_rows_launches(int *out, int n_out);
  * since the last read first (the count saturates at 2^31 - 1; the slot index stays in 0 .. 7). */
 int ifa_debug_gemm_rows_record(const int *rec, int n_rec, int count_before);
 
+/* The plan of a mixture-of-experts layer over the T rows of a step (csrc/ifa_moe_plan.h, DESIGN.md "MoE layer plan").  Host-only, no GPU
+ * needed.  facts[28], in the order of MoeFacts: T, experts, top_k, dim, ffn (rows of an expert's W1), w_dtype, w_ax8, w_q4, full_quant_gemv,
+ * norm_kind, gate_f16, gate_cols_match, has_ffn_norm, experts_uniform, have_table, have_table_aos, have_table_mo (the pointer tables the
+ * layer holds: tiled, reference layout, MO copies), the options moe_device, moe_router_fused, moe_singles, moe_overlap, gemm_rows, rows_mo,
+ * the launchers' predicates rows_use_mfma, rows_mfma_ok, rows_q4_ok, singles_ok, and caller_norm (the caller hands over the rows before the
+ * FFN norm and leaves norm and residual to the layer: the fused batched step).  out[14], in the order of MoePlan: kind (0 host-routed,
+ * 1 device-routed grouped launches, 2 device-routed with the single-row experts as two launches), router (0 norm / gate / softmax / top-k
+ * launches, 1 one launch; T = 1: the router of the fused decode step), device_ok, cap (T x top_k), tile_rows, small_max, max_tiles,
+ * max_singles, max_smalls, rows_kernel, rows_mfma, smalls_mo, side_stream (the singles' launches fork to a second stream), host_sync (the
+ * layer synchronises the stream: never captured).  A host-routed layer has the fields from tile_rows to side_stream at 0. */
+int ifa_moe_plan(const int *facts, int n_facts, int *out, int n_out);
+/* The plan the model would follow for an MoE layer over T rows NOW (its options, the tables it has built so far), out[14] as above.
+ * IFA_ERR_ARG for a layer without experts.  Plans only: launches and allocates nothing. */
+int ifa_model_moe_plan(ifa_model *m, int layer, int T, int caller_norm, int *out, int n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,8 @@ SIGNATURES = {
     "ifa_gemm_mid_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_big_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_rows_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_moe_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_model_moe_plan": (_i, [_vp, _i, _i, _i, _vp, _i]),
     "ifa_gemm_rows_launches": (_i, [_vp, _i]),
     "ifa_debug_gemm_rows_record": (_i, [_vp, _i, _i]),
     "ifa_model_set_stream": (_i, [_vp, _vp]),

@@ -644,6 +644,18 @@ int ifa_model_prompt_route(ifa_model *m, int *out, int n_out)
     return IFA_OK;
 }
 
+// the plan an MoE layer would follow over T rows now (ifa_moe_plan.h; the facts are the engine's own: moe_plan, ifa_engine_moe.hip)
+int ifa_model_moe_plan(ifa_model *m, int layer, int T, int caller_norm, int *out, int n_out)
+{
+    IFA_REQUIRE(m && out && n_out >= MOE_N_OUT, "ifa_model_moe_plan: %d outputs expected", MOE_N_OUT);
+    IFA_REQUIRE(layer >= 0 && layer < m->cfg.layers && T >= 1, "ifa_model_moe_plan: layer %d, %d rows", layer, T);
+    const Layer &L = m->layers[(size_t)layer];
+    IFA_REQUIRE(m->cfg.experts > 0 && L.t[T_MOE_GATE].present(), "ifa_model_moe_plan: layer %d has no experts", layer);
+    const MoePlan r = moe_plan(m, L, T, caller_norm != 0);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes)
 {
     IFA_REQUIRE(m && name && dptr, "ifa_model_get_buffer: null pointer");

@@ -130,7 +130,7 @@ int layer_tail_ops(ifa_model *m, int l, int T, half_t *&x, const half_t *attn_in
     }
     sp_norm.done();
     if (c.experts > 0 && L.t[T_MOE_GATE].present()) {
-        if ((rc = moe_ffn(m, L, ff_n, T))) return rc;
+        if ((rc = moe_layer(m, L, moe_plan(m, L, T, false), ff_n, T))) return rc;
         if ((rc = tp_merge_rows(m, m->f, T, none))) return rc;          // every expert sliced like the dense FFN: one merge of the weighted sums
     } else {
         if ((rc = ffn_dense(m, ff_n, T, L.t[T_W1], L.t[T_W1_B], L.t[T_W3], L.t[T_W3_B], L.t[T_W2], merging ? none : L.t[T_W2_B], m->f, perf_base))) return rc;
@@ -164,7 +164,7 @@ int layer_tail_ops(ifa_model *m, int l, int T, half_t *&x, const half_t *attn_in
 
 // ---- Route plans (ifa_prompt_route.h; rules P1 - P12 / B1 - B5 and the measurements behind their numbers: DESIGN.md, "Prompt route plan").
 // What the plans read of the model, from ONE walk over the seven linears of every layer (minus the FFN of mixture-of-experts layers,
-// which moe_ffn routes):
+// which follows its own plan: ifa_moe_plan.h):
 //   rows_layers  the rows GEMM (ifa_gemm_rows_mfma.hip; the five launches of the batched step, the four of a prompt of 2..32 tokens): dense or
 //                device-routed layers with the sequential RMS wiring, every linear tiled Q4_B32T1 (2) or a 64-weight format with an MO copy (1)
 //   big_layers   the large-tile GEMM (ifa_gemm.hip, k_gemm_big): sequential wiring, every linear a 20-byte-block Q4 tensor or a 64-weight
@@ -195,7 +195,7 @@ static RouteModelFacts route_model_facts(const ifa_model *m)
             const bool b64 = (t.dtype == Q4_B64T1 || t.dtype == Q3H_B64T1) && t.tiled;
             if (!t.present() || (t.dtype != Q4_B32T1A && t.dtype != Q4_B32T1B && !b64)) r.big_layers = 0;
         }
-        if (moe && !moe_device_ok(m, L)) r.rows_layers = 0;
+        if (moe && !moe_plan(m, L, 2, false).device_ok) r.rows_layers = 0;      // (device_ok does not depend on the rows: M1)
         if (!L.t[T_ATTN_NORM].present() || !L.t[T_FFN_NORM].present()) r.rows_layers = r.big_layers = 0;
         if (L.t[T_ATTN_NORM_B].present() || L.t[T_FFN_NORM_B].present()) r.rows_layers = 0;
         if (L.t[T_WK].dtype != L.t[T_WQ].dtype || L.t[T_WV].dtype != L.t[T_WQ].dtype || (!moe && L.t[T_W3].dtype != L.t[T_W1].dtype)) r.big_layers = 0;
@@ -401,7 +401,7 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
         if ((rc = gm_launch(m, L.t[T_WO], P, R.wo, R.qkv, GM_RESIDUAL, 0))) return rc;
         if (!norm_fused && (rc = norm_rows(m, m->a, T, L.t[T_FFN_NORM], rows ? nob : L.t[T_FFN_NORM_B], m->hn, c.ffn_norm_base))) return rc;
         if (c.experts > 0 && L.t[T_MOE_GATE].present()) {      // (Big only) mixture of experts: the attention half fused, the expert FFNs device-routed
-            if ((rc = moe_ffn(m, L, m->hn, T))) return rc;
+            if ((rc = moe_layer(m, L, moe_plan(m, L, T, false), m->hn, T))) return rc;
             if ((rc = ifa_add(m->f, m->a, (size_t)T * D, 0, m->f, s))) return rc;
             std::swap(m->x, m->f);
             x = m->x;
@@ -558,7 +558,9 @@ static int batch_route_ready(ifa_model *m, int n, bool logits_out, bool entry, B
         if (replan) { f.rows_mo = m->opt_rows_mo; R = plan_batch_route(f); }
         if (R.kind == BATCH_FUSED && (rc = gemm_rows_kparts_reserve(m->stream))) return rc;
     }
-    if (f.has_moe && m->opt_moe_overlap && (rc = ensure_side_stream(m))) return rc;
+    // the side stream of the singles' fork (M10) exists before a capture begins (the MO tables its plan reads were built just above)
+    for (const Layer &L : m->layers)
+        if (f.has_moe && L.t[T_MOE_GATE].present() && moe_plan(m, L, n, R.kind == BATCH_FUSED).side_stream) return ensure_side_stream(m);
     return IFA_OK;
 }
 
@@ -596,13 +598,12 @@ static int batch_fused_layer(ifa_model *m, const BatchRoute &R, int l, int n, co
     P = gm_wo(m, L, n, R.gm, x);
     if ((rc = gm_launch(m, L.t[T_WO], P, R.gm, R.gm, GM_RESIDUAL, 0))) return rc;
     if (c.experts > 0 && L.t[T_MOE_GATE].present()) {
-        // mixture of experts: norm, the device-routed expert FFNs over the n rows (moe_ffn_device), residual
+        // mixture of experts: norm, the expert FFNs over the n rows, residual -- all three the layer's with the fused rows router (M5)
         Tensor none;
-        if (moe_device_ok(m, L) && moe_router_rows_ok(m, L, n)) return moe_ffn_device(m, L, m->hn, n, m->a, m->a, xnext);
-        {
-            if ((rc = norm_rows(m, m->a, n, L.t[T_FFN_NORM], none, m->hn, c.ffn_norm_base))) return rc;
-            if ((rc = moe_ffn(m, L, m->hn, n))) return rc;
-        }
+        const MoePlan MP = moe_plan(m, L, n, true);
+        if (MP.router == MOE_ROUTER_FUSED) return moe_layer(m, L, MP, m->hn, n, m->a, m->a, xnext);
+        if ((rc = norm_rows(m, m->a, n, L.t[T_FFN_NORM], none, m->hn, c.ffn_norm_base))) return rc;
+        if ((rc = moe_layer(m, L, MP, m->hn, n))) return rc;
         return ifa_add(m->f, m->a, (size_t)n * D, 0, xnext, (ifa_stream)m->stream);
     }
     // 4. RmsNorm -> w1, w3 -> act(w1 x) * (w3 x)

@@ -164,20 +164,48 @@ __global__ void __launch_bounds__(512) k_dec_moe_router(const half_t *__restrict
     if (wave == 0) moe_topk_wave(lane < E ? h2f(probs[lane]) : -INFINITY, lane, E, top_k, norm_topk, sel, wout, unused_id);
 }
 
-// router of one MoE layer on the device: the same norm / GEMV / softmax kernels the op path runs, then k_moe_topk
+// ---- The layer's plan (ifa_moe_plan.h; rules M1 - M10: DESIGN.md, "MoE layer plan").  moe_facts is the ONLY place that reads the
+// options, the layer's tables and the launchers' predicates; everything below follows the plan it leads to.
+static MoeFacts moe_facts(const ifa_model *m, const Layer &L, int T, bool caller_norm)
+{
+    const ifa_model_config &c = m->cfg;
+    const Tensor &gw = L.t[T_MOE_GATE];
+    MoeFacts f;
+    f.T = T; f.experts = c.experts; f.top_k = c.moe_top_k; f.dim = c.dim; f.full_quant_gemv = c.full_quant_gemv != 0; f.norm_kind = c.norm_kind;
+    f.gate_f16 = gw.dtype == F16; f.gate_cols_match = (int)gw.cols == c.dim; f.has_ffn_norm = L.t[T_FFN_NORM].present();
+    f.have_table = L.moe_table ? 1 : 0; f.have_table_aos = L.moe_table_aos ? 1 : 0; f.have_table_mo = L.moe_table_mo ? 1 : 0;
+    f.moe_device = m->opt_moe_device != 0; f.moe_router_fused = m->opt_moe_router_fused != 0; f.moe_singles = m->opt_moe_singles != 0;
+    f.moe_overlap = m->opt_moe_overlap != 0; f.gemm_rows = m->opt_gemm_rows != 0; f.rows_mo = m->opt_rows_mo != 0;
+    f.rows_use_mfma = gemm_rows_use_mfma(); f.caller_norm = caller_norm;
+    if (c.experts < 1 || (int)L.experts.size() != c.experts * 3) return f;      // (no expert to describe)
+    const Tensor &w1 = L.experts[0];
+    const size_t D = (size_t)c.dim, F = w1.rows;
+    f.ffn = (int)F; f.w_dtype = w1.dtype; f.w_ax8 = ax8_eligible(w1.dtype); f.w_q4 = is_q4(w1.dtype); f.experts_uniform = 1;
+    for (size_t i = 0; i < L.experts.size(); i++) {      // [expert][w1, w2, w3] against the first expert's
+        const Tensor &t = L.experts[i], &r = L.experts[i % 3];
+        if (!t.present() || t.dtype != r.dtype || t.rows != r.rows || t.cols != r.cols) f.experts_uniform = 0;
+    }
+    f.rows_mfma_ok = gemm_rows_mfma_ok(F, D, 2) && gemm_rows_mfma_ok(D, F, 2);
+    f.rows_q4_ok = gemm_rows_q4_grouped_cap(D) > 0 && gemm_rows_q4_grouped_cap(F) > 0;
+    f.singles_ok = dec_singles_supported(w1.dtype, F, D, true) && dec_singles_supported(w1.dtype, D, F, false);
+    return f;
+}
+
+MoePlan moe_plan(const ifa_model *m, const Layer &L, int T, bool caller_norm) { return plan_moe_layer(moe_facts(m, L, T, caller_norm)); }
+
+// router of one MoE layer of the fused decode step on the device: one launch, or the norm / GEMV / softmax kernels the op path runs, then k_moe_topk
 int launch_moe_router(ifa_model *m, int l)
 {
     const ifa_model_config &c = m->cfg;
     Layer &L = m->layers[(size_t)l];
     int rc;
     Tensor none;
-    const Tensor &gw = L.t[T_MOE_GATE];
-    if (m->opt_moe_router_fused && c.norm_kind == 0 && gw.dtype == F16 && c.dim % 8 == 0 && c.dim <= 16384 && c.experts <= 64 && (int)gw.cols == c.dim) {
+    if (moe_plan(m, L, 1, false).router == MOE_ROUTER_FUSED) {
         const bool has_norm = L.t[T_FFN_NORM].present();
         const size_t smem = (((size_t)c.dim * 2 + 15) & ~(size_t)15) + 64 * 4 + 64 * 2;
         k_dec_moe_router<<<1, 512, smem, m->stream>>>(m->a, has_norm ? (const half_t *)L.t[T_FFN_NORM].data : nullptr,
                                                       has_norm ? (const half_t *)L.t[T_FFN_NORM_B].data : nullptr, c.ffn_norm_base, has_norm ? c.eps : -1.0f,
-                                                      c.dim, (const half_t *)gw.data, c.experts, c.moe_top_k, c.moe_norm_topk, m->hn, m->moe_gate, m->moe_route,
+                                                      c.dim, (const half_t *)L.t[T_MOE_GATE].data, c.experts, c.moe_top_k, c.moe_norm_topk, m->hn, m->moe_gate, m->moe_route,
                                                       reinterpret_cast<half_t *>(reinterpret_cast<char *>(m->moe_route.get()) + 32), 0);
         IFA_LAUNCH_CHECK();
         return IFA_OK;
@@ -195,9 +223,10 @@ int launch_moe_router(ifa_model *m, int l)
     return IFA_OK;
 }
 
-int moe_ffn(ifa_model *m, Layer &L, const half_t *ff_n, int T)
+// MOE_HOST: the reference's order of work.  It copies the probabilities to the host and synchronises the stream (plan.host_sync): never
+// inside a capture -- a captured batched step has rows_layers > 0, which route_model_facts grants only where the plan is device_ok.
+static int moe_ffn(ifa_model *m, Layer &L, const MoePlan &P, const half_t *ff_n, int T)
 {
-    if (T > 1 && moe_device_ok(m, L)) return moe_ffn_device(m, L, ff_n, T);
     const ifa_model_config &c = m->cfg;
     const size_t D = (size_t)c.dim; const int E = c.experts;
     ifa_stream s = (ifa_stream)m->stream;
@@ -239,7 +268,7 @@ int moe_ffn(ifa_model *m, Layer &L, const half_t *ff_n, int T)
         }
     }
     // one upload of every (row, weight) list, experts back to back
-    const size_t cap = (size_t)T * (size_t)c.moe_top_k;
+    const size_t cap = (size_t)P.cap;
     int *pin_rows = (int *)m->moe_pin.get(); uint16_t *pin_w = reinterpret_cast<uint16_t *>(pin_rows + cap);
     size_t off = 0;
     std::vector<size_t> start((size_t)E, 0);
@@ -265,28 +294,7 @@ int moe_ffn(ifa_model *m, Layer &L, const half_t *ff_n, int T)
     return IFA_OK;
 }
 
-// The same layer without the host (T > 1 rows; ifa_moe.h): routing and the per-expert row lists are built on the device,
-// the rows of ALL experts are gathered once (experts ascending, token order inside an expert -- the reference's order), and
-// each of the three products is ONE grouped launch over the experts with >= 2 rows (MFMA GEMM tiles, the reference's T > 1
-// branch: F16 activations on dequantised weights) plus ONE over the single-row experts (the int8-activation GEMV of its
-// T = 1 branch, bit-identical to the op-level kernel).  No D2H copy, no stream synchronisation.  Result in m->f.
-bool moe_device_ok(const ifa_model *m, const Layer &L)
-{
-    const ifa_model_config &c = m->cfg;
-    if (!m->opt_moe_device || !L.moe_table_aos || (int)L.experts.size() != c.experts * 3) return false;
-    const Tensor &w1 = L.experts[0], &w2 = L.experts[1], &w3 = L.experts[2];
-    if (!w3.present() || !ax8_eligible(w1.dtype) || !m->cfg.full_quant_gemv || w1.cols % 32 || w2.cols % 32) return false;
-    for (int e = 0; e < c.experts; e++)
-        for (int k3 = 0; k3 < 3; k3++) {
-            const Tensor &t = L.experts[(size_t)e * 3 + k3], &r = L.experts[(size_t)k3];
-            if (!t.present() || t.dtype != r.dtype || t.rows != r.rows || t.cols != r.cols) return false;
-        }
-    return true;
-}
-
-int max_smalls_possible(bool rows_kernel, int E, int cap) { return rows_kernel ? std::min(E, cap / 2) : 0; }
-
-// (also called by the batched step before it starts a capture: nothing is created inside one)
+// (plan.side_stream: batch_route_ready calls this before a step's capture begins -- nothing is created inside one; eager steps on first use)
 int ensure_side_stream(ifa_model *m)
 {
     if (m->side_stream) return IFA_OK;
@@ -296,26 +304,23 @@ int ensure_side_stream(ifa_model *m)
     return IFA_OK;
 }
 
-// can the rows of a batched step be routed by ONE launch (k_dec_moe_router, a workgroup per row: norm, F16 gate GEMV, softmax, top-k)?
-bool moe_router_rows_ok(const ifa_model *m, const Layer &L, int T)
-{
-    const ifa_model_config &c = m->cfg;
-    const Tensor &gw = L.t[T_MOE_GATE];
-    return m->opt_moe_router_fused && T <= 32 && c.norm_kind == 0 && gw.dtype == F16 && c.dim % 8 == 0 && c.dim <= 16384 && c.experts <= 64
-        && (int)gw.cols == c.dim && L.t[T_FFN_NORM].present();
-}
-
-// pre_norm: the rows BEFORE the FFN norm (ff_n is then where the normalised rows go): the batched step's router launch does the norm too
+// MOE_DEVICE_GROUPED / MOE_DEVICE_SINGLES: the same layer without the host (T > 1 rows; ifa_moe.h): routing and the per-expert row
+// lists are built on the device, the rows of ALL experts are gathered once (experts ascending, token order inside an expert -- the
+// reference's order), and each of the three products is ONE grouped launch over the experts with >= 2 rows (MFMA GEMM tiles, the
+// reference's T > 1 branch: F16 activations on dequantised weights) plus ONE over the single-row experts (the int8-activation GEMV
+// of its T = 1 branch, bit-identical to the op-level kernel).  No D2H copy, no stream synchronisation.  Result in m->f.
+// pre_norm (router MOE_ROUTER_FUSED): the rows BEFORE the FFN norm, ff_n is then where the router launch leaves the normalised rows;
 // residual / out: the layer's residual Add in the combine launch, result in `out` (default: the FFN output alone in m->f)
-int moe_ffn_device(ifa_model *m, Layer &L, const half_t *ff_n, int T, const half_t *pre_norm, const half_t *residual, half_t *out)
+static int moe_ffn_device(ifa_model *m, Layer &L, const MoePlan &P, const half_t *ff_n, int T, const half_t *pre_norm, const half_t *residual, half_t *out)
 {
     const ifa_model_config &c = m->cfg;
     const size_t D = (size_t)c.dim, F = L.experts[0].rows;
-    const int E = c.experts, K = c.moe_top_k, cap = T * K;
+    const int E = c.experts, K = c.moe_top_k, cap = P.cap, wdt = L.experts[0].dtype;
     ifa_stream s = (ifa_stream)m->stream;
     int rc;
     Tensor none;
-    if (pre_norm) {
+    IFA_REQUIRE((P.router == MOE_ROUTER_FUSED) == (pre_norm != nullptr), "MoE: the plan's router (%d) and the caller's rows disagree", P.router);
+    if (P.router == MOE_ROUTER_FUSED) {
         // norm + gate + softmax + top-k of every row as one launch instead of four (each with the arithmetic of the decode step's
         // router: the gate product is the F16 GEMV's fp32 chain, not the GEMM tile's): 25 -> 7 us per layer at 8 queries
         const size_t smem = (((size_t)c.dim * 2 + 15) & ~(size_t)15) + 64 * 4 + 64 * 2;
@@ -328,60 +333,47 @@ int moe_ffn_device(ifa_model *m, Layer &L, const half_t *ff_n, int T, const half
         if ((rc = ifa_softmax(m->moe_gate, E, T, 1, -1, 1.0f, s))) return rc;
         if ((rc = ifa_moe_route_topk(m->moe_gate, (size_t)T, E, K, c.moe_norm_topk, m->moe_sel, m->moe_selw, s))) return rc;
     }
-    // rows per expert on average >= 96: 128-row tiles (each decoded weight block feeds four MFMA tiles); else 64-row split-K tiles
-    const int tile_rows = (cap / std::max(1, E) >= 96) ? 128 : 64;
-    // a handful of rows per expert (dynamic batching): experts with 2..small_max rows stream their tiled Q4 weights once
-    // (ifa_gemm_rows.hip) instead of filling a 64-row MFMA tile with mostly padding
-    const int wdt = L.experts[0].dtype;
-    const bool rows_mfma = gemm_rows_use_mfma() && gemm_rows_mfma_ok(F, D, 2) && gemm_rows_mfma_ok(D, F, 2);     // matrix-core variant: up to 16 rows
-    const bool rows_kernel = is_q4(wdt) && m->opt_gemm_rows && L.moe_table && cap <= 8 * E
-        && (rows_mfma || (gemm_rows_q4_grouped_cap(D) > 0 && gemm_rows_q4_grouped_cap(F) > 0));
-    const int small_max = rows_kernel ? 8 : 0;
+    // experts with 2..small_max rows (dynamic batching) stream their tiled Q4 weights once (ifa_gemm_rows.hip; matrix-core variant: up to 16 rows)
     auto rows_grouped = [&](const MoeSmallGroup &q, size_t rows, size_t cols, const void *X, void *Y, int ng) {
-        return rows_mfma ? gemm_rows_mfma_grouped(q, rows, cols, X, Y, ng, small_max, m->stream) : gemm_rows_q4_grouped(q, rows, cols, X, Y, ng, m->stream);
+        return P.rows_mfma ? gemm_rows_mfma_grouped(q, rows, cols, X, Y, ng, P.small_max, m->stream) : gemm_rows_q4_grouped(q, rows, cols, X, Y, ng, m->stream);
     };
-    if ((rc = moe_build_lists(m->moe_sel, m->moe_selw, T, K, E, tile_rows, small_max, m->moe_idx, m->moe_wdev, m->moe_epos, (MoeTile *)m->moe_tiles,
+    if ((rc = moe_build_lists(m->moe_sel, m->moe_selw, T, K, E, P.tile_rows, P.small_max, m->moe_idx, m->moe_wdev, m->moe_epos, (MoeTile *)m->moe_tiles,
                               (MoeSingle *)m->moe_singles, (MoeTile *)m->moe_smalls, m->moe_counts, m->stream))) return rc;
     MoeSmallGroup sg;
     sg.smalls = (const MoeTile *)m->moe_smalls; sg.counts = m->moe_counts; sg.wtab_tiled = (const uint8_t *const *)L.moe_table; sg.which_tiled = 0;
     // MO copies of the experts (ensure_mo, built by the batched step before its capture): the small groups then take ONE launch
     // for w1 / w3 with the gated product as its output, and one for w2 -- instead of three launches and an element-wise pass
-    sg.wtab_mo = (rows_mfma && m->opt_rows_mo) ? (const uint8_t *const *)L.moe_table_mo : nullptr;
-    const bool smalls_mo = sg.wtab_mo != nullptr && max_smalls_possible(rows_kernel, E, cap) > 0;
-    const int max_smalls = rows_kernel ? std::min(E, cap / 2) : 0;
+    sg.wtab_mo = P.smalls_mo ? (const uint8_t *const *)L.moe_table_mo : nullptr;
     if ((rc = moe_gather(ff_n, m->moe_idx, m->moe_counts, cap, (int)D, m->moe_gin, m->stream))) return rc;
     MoeGroup g;
     g.tiles = (const MoeTile *)m->moe_tiles; g.singles = (const MoeSingle *)m->moe_singles; g.counts = m->moe_counts;
     g.wtab = (const uint8_t *const *)L.moe_table_aos; g.on = 1;
-    // (T <= small_max: no expert can collect more rows than the small groups take -- the tile list is empty, its launches are skipped)
-    const int max_tiles = (small_max > 0 && T <= small_max) ? 0 : cap / tile_rows + E, max_singles = std::min(E, cap);
-    // Single-row experts (round 4): when no expert can collect a tile of rows (max_tiles == 0: a batched decode step) and the small
-    // groups gate their own products (MO copies), the singles are the only rows the quantiser / element-wise launches below serve --
-    // they then take two launches of the decode GEMV's structure on the tiled expert tables (ifa_decode_singles.h) instead of six
-    if (m->opt_moe_singles && max_tiles == 0 && (smalls_mo || max_smalls == 0) && L.moe_table && dec_singles_supported(wdt, F, D, true)
-        && dec_singles_supported(wdt, D, F, false)) {
+    // Single-row experts (round 4): when no expert can collect a tile of rows (max_tiles 0: a batched decode step) and the small groups
+    // gate their own products (MO copies), the singles are the only rows the quantiser / element-wise launches below serve -- they then
+    // take two launches of the decode GEMV's structure on the tiled expert tables (ifa_decode_singles.h) instead of six
+    if (P.kind == MOE_DEVICE_SINGLES) {
         DecSinglesParams S; memset(&S, 0, sizeof(S));
         S.singles = (const MoeSingle *)m->moe_singles; S.counts = m->moe_counts; S.wtab = (const uint8_t *const *)L.moe_table; S.act_kind = c.act_kind;
         // the singles' two launches on the side stream, the small groups' two on the main one: disjoint rows of g1 / gout, joined in
         // front of the combine (inside a capture the fork / join become graph edges)
         hipStream_t ss = m->stream;
-        if (m->opt_moe_overlap && max_smalls) {
+        if (P.side_stream) {
             if ((rc = ensure_side_stream(m))) return rc;
             ss = m->side_stream;
             IFA_HIP_CHECK(hipEventRecord(m->ev_fork, m->stream));
             IFA_HIP_CHECK(hipStreamWaitEvent(ss, m->ev_fork, 0));
         }
         S.which = 0; S.X = m->moe_gin; S.ldx = (int)D; S.Y = m->moe_g1; S.ldy = (int)F; S.rows = (int)F; S.cols = (int)D; S.nblk = (int)(D / 32);
-        if ((rc = dec_singles_launch(wdt, S, true, max_singles, ss))) return rc;                      // act(w1 x) * (w3 x)
+        if ((rc = dec_singles_launch(wdt, S, true, P.max_singles, ss))) return rc;                      // act(w1 x) * (w3 x)
         S.which = 2; S.X = m->moe_g1; S.ldx = (int)F; S.Y = m->moe_gout; S.ldy = (int)D; S.rows = (int)D; S.cols = (int)F; S.nblk = (int)(F / 32);
-        if ((rc = dec_singles_launch(wdt, S, false, max_singles, ss))) return rc;                     // w2
-        if (max_smalls) {
+        if ((rc = dec_singles_launch(wdt, S, false, P.max_singles, ss))) return rc;                     // w2
+        if (P.max_smalls) {
             sg.which_tiled = 0;
-            if ((rc = gemm_rows_mo_grouped(sg, F, D, m->moe_gin, m->moe_g1, max_smalls, 1, c.act_kind, m->stream))) return rc;
+            if ((rc = gemm_rows_mo_grouped(sg, F, D, m->moe_gin, m->moe_g1, P.max_smalls, 1, c.act_kind, m->stream))) return rc;
             sg.which_tiled = 2;
-            if ((rc = gemm_rows_mo_grouped(sg, D, F, m->moe_g1, m->moe_gout, max_smalls, 0, c.act_kind, m->stream))) return rc;
+            if ((rc = gemm_rows_mo_grouped(sg, D, F, m->moe_g1, m->moe_gout, P.max_smalls, 0, c.act_kind, m->stream))) return rc;
         }
-        if (ss != m->stream) {
+        if (P.side_stream) {
             IFA_HIP_CHECK(hipEventRecord(m->ev_join, ss));
             IFA_HIP_CHECK(hipStreamWaitEvent(m->stream, m->ev_join, 0));
         }
@@ -390,26 +382,33 @@ int moe_ffn_device(ifa_model *m, Layer &L, const half_t *ff_n, int T, const half
     // single-row experts take the quantised row (TensorOpr::Quantize in front of Gemv_AX, inference_worker.cc:1772-1774)
     if ((rc = ifa_quantize_act_q8(m->moe_gin, (size_t)cap, D, m->moe_xq_in, s))) return rc;
     g.which = 0;
-    if ((rc = gemm_q_grouped(wdt, g, F, D, m->moe_gin, m->moe_g1, max_tiles, tile_rows, m->stream))) return rc;
-    if ((rc = gemv_ax8_grouped(wdt, g, F, D, m->moe_xq_in, m->moe_g1, max_singles, m->stream))) return rc;
-    if (max_smalls && !smalls_mo && (rc = rows_grouped(sg, F, D, m->moe_gin, m->moe_g1, max_smalls))) return rc;
+    if ((rc = gemm_q_grouped(wdt, g, F, D, m->moe_gin, m->moe_g1, P.max_tiles, P.tile_rows, m->stream))) return rc;
+    if ((rc = gemv_ax8_grouped(wdt, g, F, D, m->moe_xq_in, m->moe_g1, P.max_singles, m->stream))) return rc;
+    if (P.max_smalls && !P.smalls_mo && (rc = rows_grouped(sg, F, D, m->moe_gin, m->moe_g1, P.max_smalls))) return rc;
     g.which = 2; sg.which_tiled = 1;
-    if ((rc = gemm_q_grouped(wdt, g, F, D, m->moe_gin, m->moe_g3, max_tiles, tile_rows, m->stream))) return rc;
-    if ((rc = gemv_ax8_grouped(wdt, g, F, D, m->moe_xq_in, m->moe_g3, max_singles, m->stream))) return rc;
-    if (max_smalls && !smalls_mo && (rc = rows_grouped(sg, F, D, m->moe_gin, m->moe_g3, max_smalls))) return rc;
+    if ((rc = gemm_q_grouped(wdt, g, F, D, m->moe_gin, m->moe_g3, P.max_tiles, P.tile_rows, m->stream))) return rc;
+    if ((rc = gemv_ax8_grouped(wdt, g, F, D, m->moe_xq_in, m->moe_g3, P.max_singles, m->stream))) return rc;
+    if (P.max_smalls && !P.smalls_mo && (rc = rows_grouped(sg, F, D, m->moe_gin, m->moe_g3, P.max_smalls))) return rc;
     if ((rc = ifa_activation_mul(c.act_kind, m->moe_g1, m->moe_g3, (size_t)cap * F, m->moe_g1, s))) return rc;
-    if (max_smalls && smalls_mo) {      // (after the element-wise pass over all rows: the small groups' rows of g1 are written here, gated)
+    if (P.max_smalls && P.smalls_mo) {      // (after the element-wise pass over all rows: the small groups' rows of g1 are written here, gated)
         sg.which_tiled = 0;
-        if ((rc = gemm_rows_mo_grouped(sg, F, D, m->moe_gin, m->moe_g1, max_smalls, 1, c.act_kind, m->stream))) return rc;
+        if ((rc = gemm_rows_mo_grouped(sg, F, D, m->moe_gin, m->moe_g1, P.max_smalls, 1, c.act_kind, m->stream))) return rc;
     }
     if ((rc = ifa_quantize_act_q8(m->moe_g1, (size_t)cap, F, m->moe_xq_mid, s))) return rc;
     g.which = 1;
-    if ((rc = gemm_q_grouped(wdt, g, D, F, m->moe_g1, m->moe_gout, max_tiles, tile_rows, m->stream))) return rc;
-    if ((rc = gemv_ax8_grouped(wdt, g, D, F, m->moe_xq_mid, m->moe_gout, max_singles, m->stream))) return rc;
+    if ((rc = gemm_q_grouped(wdt, g, D, F, m->moe_g1, m->moe_gout, P.max_tiles, P.tile_rows, m->stream))) return rc;
+    if ((rc = gemv_ax8_grouped(wdt, g, D, F, m->moe_xq_mid, m->moe_gout, P.max_singles, m->stream))) return rc;
     sg.which_tiled = 2;
-    if (max_smalls && smalls_mo) { if ((rc = gemm_rows_mo_grouped(sg, D, F, m->moe_g1, m->moe_gout, max_smalls, 0, c.act_kind, m->stream))) return rc; }
-    else if (max_smalls && (rc = rows_grouped(sg, D, F, m->moe_g1, m->moe_gout, max_smalls))) return rc;
+    if (P.max_smalls && P.smalls_mo) { if ((rc = gemm_rows_mo_grouped(sg, D, F, m->moe_g1, m->moe_gout, P.max_smalls, 0, c.act_kind, m->stream))) return rc; }
+    else if (P.max_smalls && (rc = rows_grouped(sg, D, F, m->moe_g1, m->moe_gout, P.max_smalls))) return rc;
     return moe_combine(m->moe_gout, m->moe_epos, m->moe_selw, T, K, (int)D, out ? out : m->f, m->stream, residual);
+}
+
+int moe_layer(ifa_model *m, Layer &L, const MoePlan &P, const half_t *ff_n, int T, const half_t *pre_norm, const half_t *residual, half_t *out)
+{
+    if (P.kind != MOE_HOST) return moe_ffn_device(m, L, P, ff_n, T, pre_norm, residual, out);
+    IFA_REQUIRE(!pre_norm && !residual && !out, "MoE: the host-routed layer takes normalised rows and leaves its result in the FFN buffer");
+    return moe_ffn(m, L, P, ff_n, T);
 }
 
 } // namespace ifae

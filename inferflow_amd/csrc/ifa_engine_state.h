@@ -37,6 +37,7 @@
 #include "ifa_decode_qkv_attn.h"
 #include "ifa_decode_chain.h"
 #include "ifa_prompt_route.h"
+#include "ifa_moe_plan.h"
 
 using namespace ifa;
 
@@ -457,12 +458,12 @@ int launch_moe_router(ifa_model *m, int l);
 // host top-k (HostTensorOpr::BuildRowsForMoE, host_tensor_opr.cc:190-244: probabilities below 1e-5 are dropped,
 // optional renormalisation) -> the selected experts' FFNs in ascending expert order, each row on the T=1
 // path -> B[row] = hfma(out, weight, B[row]) (AddByRowIdx_Kernel).  Result in m->f.
-bool moe_device_ok(const ifa_model *m, const Layer &L);
-int moe_ffn_device(ifa_model *m, Layer &L, const half_t *ff_n, int T, const half_t *pre_norm = nullptr, const half_t *residual = nullptr, half_t *out = nullptr);
-int moe_ffn(ifa_model *m, Layer &L, const half_t *ff_n, int T);
-int max_smalls_possible(bool rows_kernel, int E, int cap);
+// moe_plan: what the layer would run over T rows now (ifa_moe_plan.h; caller_norm: the caller leaves the FFN norm and the residual to the
+// layer); moe_layer runs it.  pre_norm / residual / out: with the plan's fused rows router only (the rows before the norm, the residual
+// Add in the combine launch, its result).
+MoePlan moe_plan(const ifa_model *m, const Layer &L, int T, bool caller_norm);
+int moe_layer(ifa_model *m, Layer &L, const MoePlan &P, const half_t *ff_n, int T, const half_t *pre_norm = nullptr, const half_t *residual = nullptr, half_t *out = nullptr);
 int ensure_side_stream(ifa_model *m);
-bool moe_router_rows_ok(const ifa_model *m, const Layer &L, int T);
 // ---- ifa_engine_exact.hip
 bool exact_supported(const ifa_model *m, std::string *why);
 int forward_exact(ifa_model *m, int token, int pos, void *logits_out, int *next_token);

@@ -306,6 +306,13 @@ class DecodeWorker:
         d["kind"] = self.PROMPT_ROUTE_KINDS[d["kind"]]
         return d
 
+    def moe_plan(self, layer, T, caller_norm=0):
+        """what an MoE layer would run over T rows now (csrc/ifa_moe_plan.h) as a dict of MOE_PLAN_FIELDS; kind as one of MOE_KINDS, router
+        as one of MOE_ROUTERS.  caller_norm: the fused batched step's call (norm and residual left to the layer)"""
+        out = (C.c_int * len(MOE_PLAN_FIELDS))()
+        check(lib().ifa_model_moe_plan(self._h, int(layer), int(T), int(caller_norm), out, len(out)))
+        return _moe_plan_dict(out)
+
     def get_tensor_host(self, layer, tid):
         """(dtype, uint8/uint16 numpy copy, rows, cols) of a loaded tensor in reference layout, or None."""
         d, p, r, c = C.c_int(), C.c_void_p(), C.c_size_t(), C.c_size_t()
@@ -445,6 +452,33 @@ def gemm_rows_plan(T, rows, cols, epi=0, norm=0, mo=1, num_cus=256, visible_cus=
     d = dict(zip(("error", "total_rows", "ntiles", "tx", "ch", "chunk_cols", "nchunk"), v[:7]))
     d["tries"] = [dict(zip(GEMM_ROWS_TRY, v[8 + 7 * i:15 + 7 * i])) for i in range(v[7])]
     return d
+
+
+MOE_FACTS = ("T", "experts", "top_k", "dim", "ffn", "w_dtype", "w_ax8", "w_q4", "full_quant_gemv", "norm_kind", "gate_f16", "gate_cols_match",
+             "has_ffn_norm", "experts_uniform", "have_table", "have_table_aos", "have_table_mo", "moe_device", "moe_router_fused", "moe_singles",
+             "moe_overlap", "gemm_rows", "rows_mo", "rows_use_mfma", "rows_mfma_ok", "rows_q4_ok", "singles_ok", "caller_norm")
+MOE_PLAN_FIELDS = ("kind", "router", "device_ok", "cap", "tile_rows", "small_max", "max_tiles", "max_singles", "max_smalls", "rows_kernel",
+                   "rows_mfma", "smalls_mo", "side_stream", "host_sync")
+MOE_KINDS = ("host", "device_grouped", "device_singles")
+MOE_ROUTERS = ("ops", "fused")
+
+
+def _moe_plan_dict(out):
+    d = dict(zip(MOE_PLAN_FIELDS, out))
+    d["kind"] = MOE_KINDS[d["kind"]]
+    d["router"] = MOE_ROUTERS[d["router"]]
+    return d
+
+
+def moe_plan(**facts):
+    """ifa_moe_plan: the pure plan of a mixture-of-experts layer (csrc/ifa_moe_plan.h, no device) from all of MOE_FACTS, as a dict of
+    MOE_PLAN_FIELDS; kind as one of MOE_KINDS, router as one of MOE_ROUTERS"""
+    if set(facts) != set(MOE_FACTS):
+        raise KeyError("moe_plan: facts %s missing, %s unknown" % (sorted(set(MOE_FACTS) - set(facts)), sorted(set(facts) - set(MOE_FACTS))))
+    f = (C.c_int * len(MOE_FACTS))(*[int(facts[k]) for k in MOE_FACTS])
+    out = (C.c_int * len(MOE_PLAN_FIELDS))()
+    check(lib().ifa_moe_plan(f, len(MOE_FACTS), out, len(out)))
+    return _moe_plan_dict(out)
 
 
 def gemm_rows_launches():

@@ -305,6 +305,7 @@ def test_moe_layers_match_oracle(wd, kvd):
     cos, mad = _logits_close(g.host(lg), lg_o)
     assert cos >= 0.9995 and mad <= 0.03, (cos, mad)
     n = 10
+    assert wk.moe_plan(0, 1)["router"] == "fused"      # (which router the step runs: the plan the engine follows, not the option alone)
     fused, _ = wk.decode(tok, len(prompt), n)
     logits_fused = wk.read_buffer("logits").copy()
     cur = tok
@@ -320,6 +321,7 @@ def test_moe_layers_match_oracle(wd, kvd):
     assert np.array_equal(logits_fused, wk.read_buffer("logits"))
     # the router as four launches (norm, gate GEMV, softmax, k_moe_topk) instead of the one-launch k_dec_moe_router: same bits
     wk.set_option("fused", 1); wk.set_option("moe_router_fused", 0)
+    assert wk.moe_plan(0, 1)["router"] == "ops"
     wk.reset(); wk.forward(prompt, 0)
     four, _ = wk.decode(tok, len(prompt), n)
     assert np.array_equal(fused, four)
@@ -327,21 +329,33 @@ def test_moe_layers_match_oracle(wd, kvd):
     wk.close()
 
 
-@pytest.mark.parametrize("T", [2, 8, 37, 128, 300])
+# rows -> (tile_rows, max_tiles, small_max) of the layer's plan (4 experts, top 2: tests/test_moe_plan_cpu.py has the table and the rules)
+MOE_PREFILL_PLANS = {2: (64, 0, 8), 8: (64, 0, 8), 9: (64, 4, 8), 16: (64, 4, 8), 17: (64, 4, 0), 37: (64, 5, 0), 128: (64, 8, 0), 192: (128, 7, 0),
+                     300: (128, 8, 0)}
+
+
+@pytest.mark.parametrize("T", sorted(MOE_PREFILL_PLANS))
 def test_moe_prefill_device_routed_grouped_path(T):
     """MoE over T > 1 rows without the host: device routing, device-built per-expert row lists, ONE grouped MFMA launch
     per product over the experts with >= 2 rows and one grouped int8-GEMV launch over the single-row experts
     (moe_ffn_device) -- against the oracle (which restates the reference's host-routed expert loop, incl. its T = 1
-    branch for single-row experts) and against the host-routed op path of this library."""
+    branch for single-row experts) and against the host-routed op path of this library.  The row counts are those at which
+    the layer's plan changes (small groups / tiles / tile height); the plan the engine follows says which route each run took."""
     max_ctx = 320
     wk, host, s = synth.build("test_moe", dt.Q4_B32T1A, dt.F16, max_ctx=max_ctx, quant_threshold=0, std=0.06, keep_host=True)
     om = oracle_model_from_host(host, s, max_ctx, dt.F16)
     prompt = np.random.default_rng(100 + T).integers(3, s["vocab"], T).astype(np.int32)
     lg = torch.empty((T, s["vocab"]), dtype=torch.float16, device="cuda")
     wk.set_option("moe_device", 1)
+    for layer in range(s["layers"]):
+        p = wk.moe_plan(layer, T)
+        assert p["kind"] in ("device_grouped", "device_singles") and p["host_sync"] == 0 and p["cap"] == 2 * T, p
+        assert (p["tile_rows"], p["max_tiles"], p["small_max"]) == MOE_PREFILL_PLANS[T], p
     tok_dev = wk.forward(prompt, 0, lg)
     lg_dev = g.host(lg).copy()
     wk.set_option("moe_device", 0)
+    p = wk.moe_plan(0, T)
+    assert p["kind"] == "host" and p["host_sync"] == 1 and p["device_ok"] == 0, p
     tok_host = wk.forward(prompt, 0, lg)
     lg_host = g.host(lg).copy()
     cos, mad = _logits_close(lg_dev, lg_host)
@@ -775,7 +789,14 @@ def test_single_row_experts_of_a_batched_moe_step_match_the_grouped_gemv_path(sh
         wk.set_option("moe_singles", 1)
         ta = wk.decode_batch(cur, pos, list(range(n)), la)
         tg = wk.decode_batch(cur, pos, list(range(n)))                       # graph replay of the same step
+        # which route the step took: the plan the engine follows for n rows of the fused batched step (the first step built the MO tables)
+        for layer in range(s["layers"]):
+            p = wk.moe_plan(layer, n, caller_norm=1)
+            assert p["kind"] == "device_singles" and p["router"] == "fused" and p["smalls_mo"] == 1 and p["max_tiles"] == 0, p
+            assert p["max_smalls"] == min(s["experts"], n) and p["side_stream"] == (1 if p["max_smalls"] > 0 else 0), p
         wk.set_option("moe_singles", 0)
+        p = wk.moe_plan(0, n, caller_norm=1)
+        assert p["kind"] == "device_grouped" and p["side_stream"] == 0 and p["smalls_mo"] == 1, p
         tb = wk.decode_batch(cur, pos, list(range(n, 2 * n)), lb)
         assert np.array_equal(g.host(la), g.host(lb)), step
         assert [int(t) for t in ta] == [int(t) for t in tb] == [int(t) for t in tg], step
