@@ -220,6 +220,23 @@ int ifa_attention_plan(const int *facts, int n_facts, int *out, int n_out);
  * order (-1 = unused slot), weights_out [tokens][top_k] F16.  (The reference copies the probabilities to the host.) */
 int ifa_moe_route_topk(const void *probs_f16, size_t tokens, int experts, int top_k, int norm_top_k_prob, int *sel_out_dev,
                        void *weights_out_f16_dev, ifa_stream stream);
+/* The three list kernels of the device-routed MoE layer (csrc/ifa_moe.h) on device pointers.  Enqueue-only, capturable.
+ * ifa_moe_build_lists: from sel / wsel [tokens][top_k] (ifa_moe_route_topk's output; slots with an id outside [0, experts) are
+ *   skipped) the entries in the reference's order -- experts ascending, token order inside an expert: idx_out[pos] = token row,
+ *   wdev_out[pos] = its F16 weight, epos_out[t * top_k + j] = pos of row t's slot j (-1: none; every slot is written).
+ *   tiles_out / smalls_out: records {int expert, row0, nrows, 0}; singles_out: {int expert, pos}; counts_out[0..3] = entries, tiles,
+ *   singles, smalls.  An expert with 1 row is a single, with 2..small_max rows a small, otherwise ceil(rows / tile_rows) tiles in row
+ *   order.  Capacities: tokens * top_k entries, entries / tile_rows + experts tiles, experts singles, min(experts, entries / 2) smalls.
+ *   experts 1..64, top_k 1..8, tile_rows 64 or 128, small_max 0..8.
+ * ifa_moe_gather: dst[pos][:] = src[idx[pos]][:] for pos < counts[0] (<= max_entries, the grid); dim % 8 == 0.
+ * ifa_moe_combine: out[t][d] = residual[t][d] + sum_j y[epos[t][j]][d] * wsel[t][j] -- a half fma chain from 0 over the slots in
+ *   order (AddByRowIdx), slots with epos -1 skipped, then the residual (nullable) as one half addition. */
+int ifa_moe_build_lists(const int *sel_dev, const void *wsel_f16_dev, size_t tokens, int top_k, int experts, int tile_rows, int small_max,
+                        int *idx_out_dev, void *wdev_out_f16_dev, int *epos_out_dev, void *tiles_out_dev, void *singles_out_dev,
+                        void *smalls_out_dev, int *counts_out_dev, ifa_stream stream);
+int ifa_moe_gather(const void *src_f16, const int *idx_dev, const int *counts_dev, size_t max_entries, size_t dim, void *dst_f16, ifa_stream stream);
+int ifa_moe_combine(const void *y_f16, const int *epos_dev, const void *wsel_f16_dev, size_t tokens, int top_k, size_t dim, const void *residual_f16,
+                    void *out_f16, ifa_stream stream);
 /* LayerKVCache::SetKRows / SetVRows (src/transformer/kv_cache.cc:159-249): `tokens` F16 rows [kv_dim] into rows
  * [first_row, first_row + tokens) of a K or V cache of dtype F16 (copy) or Q8_B32T2 (the Alg2 quantiser) */
 int ifa_kv_store(int kv_dtype, const void *rows_f16, size_t tokens, size_t kv_dim, void *cache, size_t first_row, ifa_stream stream);
@@ -532,7 +549,11 @@ int ifa_model_forward_score(ifa_model *m, const int *tokens_host, int n_tokens, 
  * logit processors' u32 state rows [slots][vocab]; null before the first reset), "hidden", "kcache", "vcache" (device pointers).
  * "x", "att", "a", "t1", "hidden": ONE row.  "rows_x", "rows_xn", "rows_hn", "rows_att", "rows_a", "rows_t1", "rows_q", "rows_k", "rows_v": all
  * the rows (scratch_tokens of them: as many as the largest step so far) of the row-major activation buffers a batched or prompt step uses;
- * "rows_bqkv": the batched step's [32][q | k | v] (null before the first step of <= 32 rows). */
+ * "rows_bqkv": the batched step's [32][q | k | v] (null before the first step of <= 32 rows).  "rows_f": the FFN output rows.
+ * The device-routed MoE layer's buffers (models with experts; cap = scratch_tokens x top_k entries): "moe_gate" [rows][experts] F16
+ * probabilities; "moe_sel" / "moe_selw" [cap] int / F16; "moe_idx", "moe_wdev", "moe_epos" [cap]; "moe_counts" (16 ints, the first 4 used);
+ * "moe_tiles" (cap / 64 + experts + 1 records of 4 ints), "moe_singles" (experts + 1 records of 2 ints), "moe_smalls" (experts + 1 records
+ * of 4 ints); "moe_gin", "moe_gout" [cap][dim]; "moe_g1", "moe_g3" [cap][ffn].  For reading: the worker's next step overwrites them. */
 int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr, size_t *bytes);
 void *ifa_model_stream(ifa_model *m);
 /* Test hooks over the worker's memory (every device / pinned block a model owns goes through two counted allocators,

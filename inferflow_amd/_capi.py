@@ -92,6 +92,9 @@ SIGNATURES = {
     "ifa_scale": (_i, [_vp, _f, _sz, _vp, _vp]),
     "ifa_attention": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp, _vp]),
     "ifa_moe_route_topk": (_i, [_vp, _sz, _i, _i, _i, _vp, _vp, _vp]),
+    "ifa_moe_build_lists": (_i, [_vp, _vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_moe_gather": (_i, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "ifa_moe_combine": (_i, [_vp, _vp, _vp, _sz, _i, _sz, _vp, _vp, _vp]),
     "ifa_kv_store": (_i, [_i, _vp, _sz, _sz, _vp, _sz, _vp]),
     "ifa_argmax": (_i, [_vp, _sz, _vp, _vp]),
     "ifa_argmax_masked": (_i, [_vp, _sz, _vp, _vp, _vp]),

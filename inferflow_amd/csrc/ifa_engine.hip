@@ -682,11 +682,32 @@ int ifa_model_get_buffer(ifa_model *m, const char *name, int layer, void **dptr,
         else if (!strcmp(n, "hn")) { p = m->hn; b = R * c.dim * 2; }
         else if (!strcmp(n, "att")) { p = m->att; b = R * QD * 2; }
         else if (!strcmp(n, "a")) { p = m->a; b = R * c.dim * 2; }
+        else if (!strcmp(n, "f")) { p = m->f; b = R * c.dim * 2; }
         else if (!strcmp(n, "t1")) { p = m->t1; b = R * c.ffn * 2; }
         else if (!strcmp(n, "q")) { p = m->q; b = R * QD * 2; }
         else if (!strcmp(n, "k")) { p = m->k; b = R * KVD * 2; }
         else if (!strcmp(n, "v")) { p = m->v; b = R * KVD * 2; }
         else if (!strcmp(n, "bqkv")) { p = m->bqkv; b = m->bqkv ? (size_t)32 * (QD + 2 * KVD) * 2 : 0; }
+        else return ifa_fail(IFA_ERR_ARG, "ifa_model_get_buffer: unknown buffer '%s'", name);
+    }
+    else if (!strncmp(name, "moe_", 4)) {       // the device-routed MoE layer's buffers, sized by the scratch capacity (scratch_tokens rows x top_k entries)
+        IFA_REQUIRE(c.experts > 0, "ifa_model_get_buffer: '%s' of a model without experts", name);
+        const size_t R = (size_t)std::max(0, m->scratch_tokens), cap = R * (size_t)std::max(1, c.moe_top_k), E = (size_t)c.experts, F = c.ffn;
+        const char *n = name + 4;
+        if (!strcmp(n, "gate")) { p = m->moe_gate; b = R * E * 2; }
+        else if (!strcmp(n, "sel")) { p = m->moe_sel; b = cap * sizeof(int); }
+        else if (!strcmp(n, "selw")) { p = m->moe_selw; b = cap * 2; }
+        else if (!strcmp(n, "idx")) { p = m->moe_idx; b = cap * sizeof(int); }
+        else if (!strcmp(n, "wdev")) { p = m->moe_wdev; b = cap * 2; }
+        else if (!strcmp(n, "epos")) { p = m->moe_epos; b = cap * sizeof(int); }
+        else if (!strcmp(n, "counts")) { p = m->moe_counts; b = R ? 16 * sizeof(int) : 0; }
+        else if (!strcmp(n, "tiles")) { p = m->moe_tiles; b = R ? (cap / 64 + E + 1) * sizeof(MoeTile) : 0; }
+        else if (!strcmp(n, "singles")) { p = m->moe_singles; b = R ? (E + 1) * sizeof(MoeSingle) : 0; }
+        else if (!strcmp(n, "smalls")) { p = m->moe_smalls; b = R ? (E + 1) * sizeof(MoeTile) : 0; }
+        else if (!strcmp(n, "gin")) { p = m->moe_gin; b = cap * c.dim * 2; }
+        else if (!strcmp(n, "g1")) { p = m->moe_g1; b = cap * F * 2; }
+        else if (!strcmp(n, "g3")) { p = m->moe_g3; b = cap * F * 2; }
+        else if (!strcmp(n, "gout")) { p = m->moe_gout; b = cap * c.dim * 2; }
         else return ifa_fail(IFA_ERR_ARG, "ifa_model_get_buffer: unknown buffer '%s'", name);
     }
     else if (!strcmp(name, "kcache") || !strcmp(name, "vcache")) {

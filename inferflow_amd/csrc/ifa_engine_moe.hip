@@ -319,6 +319,7 @@ static int moe_ffn_device(ifa_model *m, Layer &L, const MoePlan &P, const half_t
     ifa_stream s = (ifa_stream)m->stream;
     int rc;
     Tensor none;
+    IFA_REQUIRE(E >= 1 && E <= 64 && K >= 1 && K <= 8, "MoE: experts %d / top_k %d out of range", E, K);      // (k_moe_build: cnt[64]; the routers: 8 slots)
     IFA_REQUIRE((P.router == MOE_ROUTER_FUSED) == (pre_norm != nullptr), "MoE: the plan's router (%d) and the caller's rows disagree", P.router);
     if (P.router == MOE_ROUTER_FUSED) {
         // norm + gate + softmax + top-k of every row as one launch instead of four (each with the arithmetic of the decode step's

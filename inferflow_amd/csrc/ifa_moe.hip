@@ -110,3 +110,49 @@ int moe_combine(const void *y, const int *epos, const void *wsel, int T, int top
 }
 
 } // namespace ifa
+
+// ---- the three list kernels as ops (tests/test_gpu_moe_lists.py): thin wrappers that refuse what the kernels cannot take
+// (k_moe_build: cnt[64] / start[64], one wave per expert; the tile split assumes 64 or 128 rows)
+static int moe_args_ok(const char *who, size_t tokens, int experts, int top_k)
+{
+    IFA_REQUIRE(experts >= 1 && experts <= 64 && top_k >= 1 && top_k <= 8, "%s: experts %d / top_k %d out of range", who, experts, top_k);
+    IFA_REQUIRE(tokens <= (size_t)0x7FFFFFFF / 8, "%s: %zu rows", who, tokens);
+    return IFA_OK;
+}
+
+extern "C" {
+
+int ifa_moe_build_lists(const int *sel_dev, const void *wsel_f16_dev, size_t tokens, int top_k, int experts, int tile_rows, int small_max,
+                        int *idx_out_dev, void *wdev_out_f16_dev, int *epos_out_dev, void *tiles_out_dev, void *singles_out_dev,
+                        void *smalls_out_dev, int *counts_out_dev, ifa_stream stream)
+{
+    IFA_REQUIRE(sel_dev && wsel_f16_dev && idx_out_dev && wdev_out_f16_dev && epos_out_dev && tiles_out_dev && singles_out_dev && smalls_out_dev
+                && counts_out_dev, "ifa_moe_build_lists: null pointer");
+    int rc;
+    if ((rc = moe_args_ok("ifa_moe_build_lists", tokens, experts, top_k))) return rc;
+    IFA_REQUIRE(tile_rows == 64 || tile_rows == 128, "ifa_moe_build_lists: tile_rows %d (64 or 128)", tile_rows);
+    IFA_REQUIRE(small_max >= 0 && small_max <= 8, "ifa_moe_build_lists: small_max %d out of range", small_max);
+    return ifa::moe_build_lists(sel_dev, wsel_f16_dev, (int)tokens, top_k, experts, tile_rows, small_max, idx_out_dev, wdev_out_f16_dev, epos_out_dev,
+                                (ifa::MoeTile *)tiles_out_dev, (ifa::MoeSingle *)singles_out_dev, (ifa::MoeTile *)smalls_out_dev, counts_out_dev, ifa_s(stream));
+}
+
+int ifa_moe_gather(const void *src_f16, const int *idx_dev, const int *counts_dev, size_t max_entries, size_t dim, void *dst_f16, ifa_stream stream)
+{
+    IFA_REQUIRE(src_f16 && idx_dev && counts_dev && dst_f16, "ifa_moe_gather: null pointer");
+    IFA_REQUIRE(dim > 0 && dim % 8 == 0 && dim < (1u << 30), "ifa_moe_gather: dim %zu (16-byte chunks: dim %% 8 == 0)", dim);
+    IFA_REQUIRE(max_entries < 65536, "ifa_moe_gather: %zu entries (one grid row each, < 65536)", max_entries);
+    IFA_REQUIRE(!((reinterpret_cast<uintptr_t>(src_f16) | reinterpret_cast<uintptr_t>(dst_f16)) & 15), "ifa_moe_gather: rows not 16-byte aligned");
+    return ifa::moe_gather(src_f16, idx_dev, counts_dev, (int)max_entries, (int)dim, dst_f16, ifa_s(stream));
+}
+
+int ifa_moe_combine(const void *y_f16, const int *epos_dev, const void *wsel_f16_dev, size_t tokens, int top_k, size_t dim, const void *residual_f16,
+                    void *out_f16, ifa_stream stream)
+{
+    IFA_REQUIRE(y_f16 && epos_dev && wsel_f16_dev && out_f16, "ifa_moe_combine: null pointer");
+    IFA_REQUIRE(top_k >= 1 && top_k <= 8, "ifa_moe_combine: top_k %d out of range", top_k);
+    IFA_REQUIRE(dim > 0 && dim < (1u << 30) && tokens < 65536, "ifa_moe_combine: %zu rows of %zu (one grid row each, < 65536)", tokens, dim);
+    if (tokens == 0) return IFA_OK;
+    return ifa::moe_combine(y_f16, epos_dev, wsel_f16_dev, (int)tokens, top_k, (int)dim, out_f16, ifa_s(stream), residual_f16);
+}
+
+} // extern "C"
