@@ -301,6 +301,26 @@ int ifa_sample_pool_rows(const int *counts_dev, const int *ids_dev, const void *
 int ifa_sample_pool_host(const int *ids, const unsigned short *vals_f16, int count, const ifa_sample_params *p,
                          unsigned long long *rng_state_inout, int *token_out, int *index_out, int *cut_len_out, float *weights_out,
                          int *order_ids_out);
+/* The verify step of lookup decoding for seeded sampled queries: `rows` (1..8) pools of ONE query's draft step drawn as a chain.
+ * draft_dev [rows - 1]: draft_dev[i] is the guess for the token row i emits (row i + 1 was computed behind it); ONE
+ * ifa_sample_params and ONE generator state in device memory.  The specification:
+ *   st = *rng; e = 0
+ *   for i in 0 .. rows-1:
+ *       draw row i by the rule of ifa_sample_pool_host with state st -> (tok, st')         (greedy: ids[i][0], st' = st)
+ *       if the row cannot be drawn (empty pool, NaN, unknown strategy): if *err == 0: *err = i + 1; break
+ *       tokens[e++] = tok; st = st'
+ *       if i == rows-1 or tok != draft[i]: break
+ *   *rng = st; *n_out = e; tokens[e..rows) = -1           (index_out_dev, nullable, likewise: the index in the sorted pool)
+ * A row behind the first mismatch is never looked at: it can neither raise an error nor move the generator.  Since every sampled
+ * draw advances the generator by exactly two steps, the tokens are exactly those of a row-by-row loop over the same pools.  One
+ * workgroup of `rows` waves (wave i draws row i from the state 2 i steps on), one barrier, one lane scans; enqueue-only, capturable. */
+int ifa_sample_verify_rows(const int *counts_dev, const int *ids_dev, const void *vals_f16_dev, size_t rows, int k_stride,
+                           const ifa_sample_params *params_dev, const int *draft_dev, unsigned long long *rng_state_dev, int *tokens_out_dev,
+                           int *index_out_dev, int *n_out_dev, int *err_dev, ifa_stream stream);
+/* host-only (no device needed): the same chain on the CPU, built on ifa_sample_pool_host; the arrays are laid out as above.
+ * *err_inout is left alone unless it is 0 and a reached row cannot be drawn.  IFA_ERR_ARG: rows / k_stride out of range, null pointers. */
+int ifa_sample_verify_host(const int *counts, const int *ids, const unsigned short *vals_f16, int rows, int k_stride, const ifa_sample_params *p,
+                           const int *draft, unsigned long long *rng_state_inout, int *tokens_out, int *index_out, int *n_out, int *err_inout);
 
 /* ---- logit processors (csrc/ifa_logit_adjust.hip): repetition / frequency / presence penalties and logit_bias on F16 logits rows.
  * State per slot (one slot per query), dense over the n ids of the vocabulary, all in device memory owned by the caller:
@@ -318,6 +338,14 @@ int ifa_sample_pool_host(const int *ids, const unsigned short *vals_f16, int cou
  * atomics, run-to-run identical.  Slots in state_slot_dev must lie inside the three arrays. */
 int ifa_logit_adjust_rows(const void *logits_f16, size_t row_stride, const int *row_idx_dev, const int *state_slot_dev, size_t rows, size_t n,
                           const unsigned *state_dev, const float *bias_dev, const float *params_dev, void *out_f16_dev, ifa_stream stream);
+/* The rows of ONE slot's draft step (lookup decoding): `rows` (1..8) logits rows [rows][row_stride], row r computed behind the draft
+ * tokens draft_dev[0..r) (draft_dev [rows - 1]); the slot is state_slot_dev[0].  Out row r (compact, stride n) is exactly what
+ * ifa_logit_adjust_rows writes for input row r after ifa_logit_state_add of draft[0..r) to that slot: per id
+ *   w' = w + #{j < r : draft[j] == id}       (bit 31 is kept, the count is w' & 0x7fffffff, the repetition rule fires on w' != 0)
+ * and then the arithmetic above with w' in place of w -- the same inline function, same order, every operation rounded on its own.
+ * Writes no state.  Same grid and access widths as ifa_logit_adjust_rows; enqueue-only, capturable. */
+int ifa_logit_adjust_draft_rows(const void *logits_f16, size_t row_stride, const int *state_slot_dev, size_t rows, size_t n, const int *draft_dev,
+                                const unsigned *state_dev, const float *bias_dev, const float *params_dev, void *out_f16_dev, ifa_stream stream);
 /* clears the state and bias rows of `slot`, sets bit 31 for every prompt id (duplicates welcome), scatters the n_bias
  * (id, value) pairs into the bias row and writes {rep, freq, pres}; ids outside 0..n-1 are skipped.  Two memsets + one launch. */
 int ifa_logit_state_reset(int slot, const int *prompt_tokens_dev, size_t n_prompt, float rep, float freq, float pres, const int *bias_ids_dev,
@@ -488,6 +516,20 @@ int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const in
  * leading i with next[i - 1] == tokens[i]) and later steps overwrite the others.  IFA_ERR_ARG: n outside 2..8, pos0 < 0,
  * pos0 + n > max_ctx; IFA_ERR_STATE: a partitioned worker (tp_size > 1 or a topology), options exact_order or perf_stat. */
 int ifa_model_decode_draft(ifa_model *m, int n, const int *tokens_host, int pos0, int *next_tokens_host, void *logits_out_dev);
+/* The draft step for a seeded SAMPLED query (csrc/ifa_engine_draft_sampled.hip): ifa_model_decode_draft's step on the same n rows --
+ * the same captured graph, cache rows pos0 .. pos0 + n - 1 bit for bit what that call writes -- followed on the worker's stream by
+ * [ifa_logit_adjust_draft_rows with the state of state_slot (-1: no processors), draft = tokens_host[1..n)] -> ifa_topk_pool over the n
+ * rows with k = p->pool_size and the mask of ifa_model_set_pool_excluded -> ifa_sample_verify_rows with *rng_state_inout.  One
+ * synchronisation per call; parameters, drafts and generator state travel through device memory written by the call.
+ * out_tokens_host [n]: the *n_out (1..n) emitted tokens, -1 behind them: token i is the draw of row i, rows 1 .. *n_out - 1 were
+ * reached because tokens_host[i] equalled the draw of row i - 1; the caller keeps cache rows pos0 .. pos0 + *n_out - 1.  The tokens,
+ * *n_out and the generator state equal ifa_sample_verify_host on the pools of the step's (adjusted) logits rows.  The call never
+ * writes the logit state -- the caller counts the emitted tokens -- and leaves the greedy, draft and sampled graphs valid.
+ * IFA_ERR_ARG: n outside 2..8, pos0 < 0, pos0 + n > max_ctx, an unknown strategy, pool_size outside 1..IFA_POOL_MAX, a slot without
+ * logit state; IFA_ERR_STATE: a partitioned worker, lm_head missing, options exact_order or perf_stat, a reached row with an
+ * empty pool (the message names the row; the results are not valid). */
+int ifa_model_decode_draft_sampled(ifa_model *m, int n, const int *tokens_host, int pos0, const ifa_sample_params *p,
+                                   unsigned long long *rng_state_inout, int state_slot, int *out_tokens_host, int *n_out);
 /* ---- steps that end in a candidate pool (sampled decoding without the logits row on the host): ifa_topk_pool runs on the
  * step's logits on the worker's stream, in front of the step's ONE synchronisation, and (count, ids, values) come back
  * in one copy through pinned staging.  Everything after the pool -- softmax, cuts, the draw -- stays with the caller.

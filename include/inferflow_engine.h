@@ -112,7 +112,7 @@ int ifa_engine_perf_stat(ifa_engine *e, unsigned *keys, float *ms, int capacity)
  * generator state goes to the device and comes back, and the tokens are exactly those of the ifa_engine_infer / ifa_engine_commit loop
  * for the same seeded query; a later infer / commit or generate continues the same generator stream.  model_info
  * "device_sampled_steps" counts the steps drawn on the device.  tfs, typical, mirostat, fsd and random_fsd queries, a vocabulary with
- * more than 3 excluded ids and ifa_engine_generate_lookup stay refused; logprobs are not produced by this call.  The device's exp is
+ * more than 3 excluded ids stay refused, and so does ifa_engine_generate_lookup unless `lookup_sampled` is on as well (below); logprobs are not produced by this call.  The device's exp is
  * ocml's (1 ulp), the host's is libm's: see the known gap in DESIGN.md.  The service shell streams through infer / commit and does not
  * use this call. */
 int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_tokens, float *gpu_ms);
@@ -125,7 +125,17 @@ int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_token
  * arithmetic (F16 activations); ifa_engine_generate's single-row step quantises activations to int8, so the two agree wherever the
  * top-2 logit gap exceeds that route difference.  stats5 (nullable): {steps, draft steps, draft tokens offered, draft tokens
  * accepted, milliseconds inside the worker's steps}.  Returns the tokens written (never more than max_new) or -1: conditions of
- * ifa_engine_generate, and model_info "lookup_decoding" = 0 (multi-GPU engine, return_output_tensors = true). */
+ * ifa_engine_generate, and model_info "lookup_decoding" = 0 (multi-GPU engine, return_output_tensors = true).
+ * With `lookup_sampled = true` in the .ini (default false; active only where "device_sampler" and "lookup_decoding" both are 1:
+ * model_info "lookup_sampled") the call also takes the queries the device sampler covers -- seeded sample.std / top_k / sample.top_p /
+ * min_p queries and processed queries, sampled or greedy.  A draft step then ends in the verify chain on the device
+ * (ifa_model_decode_draft_sampled): the rows are drawn one after the other with the query's generator, row i + 1 counts only if
+ * draft i IS the draw of row i, the chain stops at the first draw that differs.  Every draw advances the generator by exactly two
+ * steps, so the tokens are exactly those a row-by-row loop over the same logits rows draws -- no rejection sampling, nothing
+ * approximated -- and the generator is left where that loop leaves it (ifa_engine_query_rng_state).  A step without a draft is one
+ * step of ifa_engine_generate's sampled path.  model_info "lookup_sampled_steps" counts the draft steps taken this way.  With the key
+ * off such queries are refused as before; tfs, typical, mirostat, fsd and random_fsd queries and a vocabulary with more than 3
+ * excluded ids stay refused either way. */
 int ifa_engine_generate_lookup(ifa_engine *e, int query_id, int max_new, const int *prediction, int n_prediction, int *out_tokens,
                                float *stats5);
 /* host-only: the draft rule (host/lookup_draft.h).  For g = ngram_max down to ngram_min (skipped while n_ctx < g): key = the last g
@@ -161,7 +171,9 @@ double ifa_perplexity_token_nll(const uint16_t *logits_f16, int vocab, int token
  * row the logit processors had rewritten), "context_shift" (0 / 1: queries run past max_context_len by default -- the .ini key
  * `context_shift = true` on a single-device engine with return_output_tensors = false; elsewhere the key is accepted and this stays
  * 0), "context_shift_available" (0 / 1: that condition without the key: ifa_engine_shift_query and a per-query context_shift = 1
- * work), "context_shifts" (shifts so far, automatic and explicit), "context_shift_tokens" (the tokens they dropped); -1 if unknown */
+ * work), "context_shifts" (shifts so far, automatic and explicit), "context_shift_tokens" (the tokens they dropped), "lookup_sampled" (0 / 1:
+ * ifa_engine_generate_lookup takes sampled and processed queries -- the .ini key `lookup_sampled = true` where "device_sampler" and
+ * "lookup_decoding" are both 1), "lookup_sampled_steps" (draft steps verified by the draw on the device); -1 if unknown */
 int ifa_engine_model_info(ifa_engine *e, const char *key);
 /* prompt prefix cache: the leading prompt tokens of query_id whose K/V rows AddQuery found in a slot (the query's first Infer runs
  * only the rest; QueryInferenceResult::prefix_len reports the same number); 0 without a hit or with the cache off, -1 unknown id */
@@ -182,6 +194,8 @@ int ifa_engine_query_cached_tokens(ifa_engine *e, int query_id);
 int ifa_context_shift_plan(int n_tokens, int processed, int max_ctx, int keep, int *out2);
 int ifa_engine_shift_query(ifa_engine *e, int query_id, int keep, int discard);
 int ifa_engine_query_shifted_tokens(ifa_engine *e, int query_id);
+/* read-only: the 48-bit state of query_id's generator (java.util.Random's LCG), i.e. what its next draw starts from; 1 ok, 0 unknown id */
+int ifa_engine_query_rng_state(ifa_engine *e, int query_id, unsigned long long *state);
 /* host-only: the cache's slot / reuse policy (host/prefix_cache.h).  Slot i holds the rows of record_lens[i] token ids -- the
  * records lie back to back in records_flat --, is busy (busy[i] != 0: a running query owns it) or free, and was last used at
  * stamps[i].  Match = common prefix of prompt and record, at most n_prompt - 1; the longest wins (ties: free before busy, then the

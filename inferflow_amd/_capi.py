@@ -101,9 +101,12 @@ SIGNATURES = {
     "ifa_topk_pool": (_i, [_vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "ifa_sample_pool_rows": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ifa_sample_pool_host": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_sample_verify_rows": (_i, [_vp, _vp, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_sample_verify_host": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ifa_logsumexp_workspace": (_sz, [_sz, _sz]),
     "ifa_logsumexp_rows": (_i, [_vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ifa_logit_adjust_rows": (_i, [_vp, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ifa_logit_adjust_draft_rows": (_i, [_vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ifa_logit_state_reset": (_i, [_i, _vp, _sz, _f, _f, _f, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "ifa_logit_state_add": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
     "ifa_model_create": (_i, [_vp, C.POINTER(_vp)]),
@@ -130,6 +133,7 @@ SIGNATURES = {
     "ifa_kv_shift_rows": (_i, [_i, _vp, _vp, _sz, _sz, _i, _i, _vp, _sz, _sz, _sz, _vp]),
     "ifa_model_decode_batch": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ifa_model_decode_draft": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
+    "ifa_model_decode_draft_sampled": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "ifa_model_set_pool_excluded": (_i, [_vp, _vp, _i]),
     "ifa_model_decode_pool": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_decode_batch_pool": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
@@ -229,6 +233,7 @@ ENGINE_SIGNATURES = {
     "ifa_context_shift_plan": (_i, [_i, _i, _i, _i, _ip]),
     "ifa_engine_shift_query": (_i, [_vp, _i, _i, _i]),
     "ifa_engine_query_shifted_tokens": (_i, [_vp, _i]),
+    "ifa_engine_query_rng_state": (_i, [_vp, _i, _vp]),
     "ifa_prefix_cache_plan": (_i, [_ip, _ip, _ip, C.POINTER(C.c_longlong), _i, _ip, _i, _i, _ip]),
     "ifa_step_plan_query": (_i, [_i, _i, _i, _i, _i, _ip]),
     "ifa_step_plan_batch": (_i, [_i, _ip, _i, _ip, _ip]),

@@ -101,6 +101,7 @@ static int pool_rows_launch(ifa_model *m, const half_t *logits, const int *idx, 
 
 int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
 {
+    if (m->dsv.k > 0) return draft_sampled_enqueue(m, logits, n_rows);      // (ifa_model_decode_draft_sampled: its own tail, no pool copy)
     ifa_model::PoolReq &R = m->pool;
     if (R.k <= 0) return IFA_OK;
     const int k = R.k, n_sel = R.n_sel;

@@ -268,6 +268,11 @@ struct ifa_model : Scratch {
     std::map<int, SampGraph> samp_graphs;
     DevPin<int> samp_blk;
     int samp_k = 0; bool samp_armed = false;
+    // Sampled draft step (ifa_model_decode_draft_sampled, ifa_engine_draft_sampled.hip).  dsv.k > 0: armed -- the draft step in flight
+    // ends in draft_sampled_enqueue() in place of pool_enqueue()'s pool, in front of its one synchronisation.  dsv_blk: the call's
+    // parameters, state slot, draft tokens, generator state and results in device memory (+ pinned twin).
+    struct DraftSampReq { int k = 0; bool armed = false; } dsv;
+    DevPin<int> dsv_blk;
     static constexpr int RING = 1024;
 };
 
@@ -446,6 +451,8 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
 int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
 // device / pinned staging for n_sel rows of k entries (grown on demand, outside any capture)
 int pool_reserve(ifa_model *m, int n_sel, int k);
+// ifa_engine_draft_sampled.hip: the tail of a sampled draft step on the n rows of `logits` (m->dsv armed), enqueue-only
+int draft_sampled_enqueue(ifa_model *m, const half_t *logits, int n_rows);
 // ---- ifa_engine_score.hip
 static constexpr size_t LSE_PART_FLOATS = 256;      // rows * splits <= 128 pairs whatever the row count (ifa_logprob.hip, lse_splits)
 int lse_part_reserve(ifa_model *m);

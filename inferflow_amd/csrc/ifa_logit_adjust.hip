@@ -21,6 +21,10 @@
 // worker's buffers always) -- with the n % 8 ids behind the last vector going one by one; a row with any base off a boundary (odd
 // n or stride) goes one id per thread and step.  No LDS, no atomics, no reduction: run-to-run identical.
 //
+// ifa_logit_adjust_draft_rows is the same arithmetic (one inline function, la_one) for the rows of ONE slot's draft step: row r sees
+// the state words as they would be after ifa_logit_state_add of draft[0..r) -- w' = w + #{j < r : draft[j] == id} -- and writes no
+// state.  Same grid, same 16-byte / id-by-id paths.
+//
 // The two state kernels use integer vector atomics (atomicOr for the prompt bit -- duplicates are the normal case -- and atomicAdd
 // for the counts): integer addition commutes, the result is deterministic.
 #include <algorithm>
@@ -45,34 +49,40 @@ __device__ __forceinline__ uint16_t la_one(uint16_t in, unsigned w, float b, flo
     return f2hbits(fminf(fmaxf(x, -65504.0f), 65504.0f));
 }
 
-// grid (ceil(n / 2048), rows)
-__global__ void __launch_bounds__(LA_THREADS) k_logit_adjust(const uint16_t *__restrict__ logits, size_t row_stride, const int *__restrict__ row_idx,
-                                                             const int *__restrict__ state_slot, int n, const unsigned *__restrict__ state,
-                                                             const float *__restrict__ bias, const float *__restrict__ params,
-                                                             uint16_t *__restrict__ out)
-{
-    const int tid = threadIdx.x, chunk = blockIdx.x, r = blockIdx.y;
-    const size_t src_row = row_idx ? (size_t)row_idx[r] : (size_t)r;
-    const size_t q = (size_t)state_slot[r];
-    const uint16_t *in_row = logits + src_row * row_stride;
-    uint16_t *out_row = out + (size_t)r * (size_t)n;
-    const unsigned *st = state + q * (size_t)n;
-    const float *bs = bias + q * (size_t)n;
-    const float rep = params[q * 3], freq = params[q * 3 + 1], pres = params[q * 3 + 2];
+// The draft step (ifa_logit_adjust_draft_rows): row r of a slot is adjusted as if draft[0..r) had been counted already,
+//   w' = w + #{j < r : draft[j] == id}
+// (bit 31 is kept, the count is w' & 0x7fffffff, the repetition rule fires on w' != 0), then la_one as ever.  dn = 0: w' = w.
+constexpr int LA_DRAFT_MAX = 7;
+struct LaDraft { int dn; int d[LA_DRAFT_MAX]; };
 
+template <bool DRAFT> __device__ __forceinline__ unsigned la_word(unsigned w, int id, const LaDraft &D)
+{
+    if constexpr (DRAFT) {
+#pragma unroll
+        for (int j = 0; j < LA_DRAFT_MAX; j++) w += (j < D.dn && D.d[j] == id) ? 1u : 0u;
+    }
+    return w;
+}
+
+// one row of the grid (ceil(n / 2048), rows): chunk blockIdx.x of the row at in_row / out_row with the slot's st / bs rows
+template <bool DRAFT>
+__device__ __forceinline__ void la_row_chunk(const uint16_t *__restrict__ in_row, uint16_t *__restrict__ out_row, const unsigned *__restrict__ st,
+                                             const float *__restrict__ bs, int n, float rep, float freq, float pres, const LaDraft &D)
+{
+    const int tid = threadIdx.x, chunk = blockIdx.x;
     const bool aligned = (((uintptr_t)in_row | (uintptr_t)out_row | (uintptr_t)st | (uintptr_t)bs) & 15u) == 0;
     if (!aligned) {                     // (uniform per row) one id per thread and step, coalesced
 #pragma unroll
         for (int e = 0; e < 8; e++) {
             const int id = chunk * LA_PER_WG + e * LA_THREADS + tid;
-            if (id < n) out_row[id] = la_one(in_row[id], st[id], bs[id], rep, freq, pres);
+            if (id < n) out_row[id] = la_one(in_row[id], la_word<DRAFT>(st[id], id, D), bs[id], rep, freq, pres);
         }
         return;
     }
     const int nvec = n >> 3, tail0 = nvec << 3;
     if (chunk == (int)gridDim.x - 1 && tail0 + tid < n) {
         const int id = tail0 + tid;
-        out_row[id] = la_one(in_row[id], st[id], bs[id], rep, freq, pres);
+        out_row[id] = la_one(in_row[id], la_word<DRAFT>(st[id], id, D), bs[id], rep, freq, pres);
     }
     const int v = chunk * LA_THREADS + tid;
     if (v >= nvec) return;
@@ -86,11 +96,42 @@ __global__ void __launch_bounds__(LA_THREADS) k_logit_adjust(const uint16_t *__r
     unsigned o[4];
 #pragma unroll
     for (int p = 0; p < 4; p++) {
-        const unsigned lo = la_one((uint16_t)(xw[p] & 0xFFFFu), w[2 * p], b[2 * p], rep, freq, pres);
-        const unsigned hi = la_one((uint16_t)(xw[p] >> 16), w[2 * p + 1], b[2 * p + 1], rep, freq, pres);
+        const unsigned lo = la_one((uint16_t)(xw[p] & 0xFFFFu), la_word<DRAFT>(w[2 * p], id0 + 2 * p, D), b[2 * p], rep, freq, pres);
+        const unsigned hi = la_one((uint16_t)(xw[p] >> 16), la_word<DRAFT>(w[2 * p + 1], id0 + 2 * p + 1, D), b[2 * p + 1], rep, freq, pres);
         o[p] = lo | (hi << 16);
     }
     *reinterpret_cast<uint4 *>(out_row + id0) = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// grid (ceil(n / 2048), rows)
+__global__ void __launch_bounds__(LA_THREADS) k_logit_adjust(const uint16_t *__restrict__ logits, size_t row_stride, const int *__restrict__ row_idx,
+                                                             const int *__restrict__ state_slot, int n, const unsigned *__restrict__ state,
+                                                             const float *__restrict__ bias, const float *__restrict__ params,
+                                                             uint16_t *__restrict__ out)
+{
+    const int r = blockIdx.y;
+    const size_t src_row = row_idx ? (size_t)row_idx[r] : (size_t)r;
+    const size_t q = (size_t)state_slot[r];
+    LaDraft D;
+    D.dn = 0;
+    la_row_chunk<false>(logits + src_row * row_stride, out + (size_t)r * (size_t)n, state + q * (size_t)n, bias + q * (size_t)n, n, params[q * 3],
+                        params[q * 3 + 1], params[q * 3 + 2], D);
+}
+
+// grid (ceil(n / 2048), rows): the rows of ONE slot's draft step, row r behind draft[0..r)
+__global__ void __launch_bounds__(LA_THREADS) k_logit_adjust_draft(const uint16_t *__restrict__ logits, size_t row_stride, const int *__restrict__ state_slot,
+                                                                   int n, const int *__restrict__ draft, const unsigned *__restrict__ state,
+                                                                   const float *__restrict__ bias, const float *__restrict__ params,
+                                                                   uint16_t *__restrict__ out)
+{
+    const int r = blockIdx.y;
+    const size_t q = (size_t)state_slot[0];
+    LaDraft D;
+    D.dn = min(r, LA_DRAFT_MAX);
+#pragma unroll
+    for (int j = 0; j < LA_DRAFT_MAX; j++) D.d[j] = j < D.dn ? draft[j] : -1;
+    la_row_chunk<true>(logits + (size_t)r * row_stride, out + (size_t)r * (size_t)n, state + q * (size_t)n, bias + q * (size_t)n, n, params[q * 3],
+                       params[q * 3 + 1], params[q * 3 + 2], D);
 }
 
 // after the slot's two rows have been cleared: the prompt bit of every prompt id, the bias entries, the parameters
@@ -129,6 +170,15 @@ int logit_adjust_rows(const void *logits, size_t row_stride, const int *row_idx_
     return IFA_OK;
 }
 
+int logit_adjust_draft_rows(const void *logits, size_t row_stride, const int *state_slot_dev, size_t rows, size_t n, const int *draft_dev,
+                            const unsigned *state_dev, const float *bias_dev, const float *params_dev, void *out, hipStream_t s)
+{
+    k_logit_adjust_draft<<<dim3(ifa_cdiv(n, LA_PER_WG), (unsigned)rows), dim3(LA_THREADS), 0, s>>>((const uint16_t *)logits, row_stride, state_slot_dev, (int)n,
+                                                                                                   draft_dev, state_dev, bias_dev, params_dev, (uint16_t *)out);
+    IFA_LAUNCH_CHECK();
+    return IFA_OK;
+}
+
 } // namespace ifa
 
 extern "C" {
@@ -141,6 +191,17 @@ int ifa_logit_adjust_rows(const void *logits_f16, size_t row_stride, const int *
     IFA_REQUIRE(rows > 0 && rows <= 65535, "ifa_logit_adjust_rows: rows %zu", rows);
     IFA_REQUIRE(logits_f16 != out_f16_dev, "ifa_logit_adjust_rows: the op is out of place");
     return ifa::logit_adjust_rows(logits_f16, row_stride, row_idx_dev, state_slot_dev, rows, n, state_dev, bias_dev, params_dev, out_f16_dev, ifa_s(stream));
+}
+
+int ifa_logit_adjust_draft_rows(const void *logits_f16, size_t row_stride, const int *state_slot_dev, size_t rows, size_t n, const int *draft_dev,
+                                const unsigned *state_dev, const float *bias_dev, const float *params_dev, void *out_f16_dev, ifa_stream stream)
+{
+    IFA_REQUIRE(logits_f16 && state_slot_dev && state_dev && bias_dev && params_dev && out_f16_dev, "ifa_logit_adjust_draft_rows: null pointer");
+    IFA_REQUIRE(n > 0 && n < 0x7FFFFFFFu && row_stride >= n, "ifa_logit_adjust_draft_rows: n %zu, row stride %zu", n, row_stride);
+    IFA_REQUIRE(rows >= 1 && rows <= (size_t)ifa::LA_DRAFT_MAX + 1, "ifa_logit_adjust_draft_rows: rows %zu outside 1..%d", rows, ifa::LA_DRAFT_MAX + 1);
+    IFA_REQUIRE(rows == 1 || draft_dev, "ifa_logit_adjust_draft_rows: %zu rows without draft tokens", rows);
+    IFA_REQUIRE(logits_f16 != out_f16_dev, "ifa_logit_adjust_draft_rows: the op is out of place");
+    return ifa::logit_adjust_draft_rows(logits_f16, row_stride, state_slot_dev, rows, n, draft_dev, state_dev, bias_dev, params_dev, out_f16_dev, ifa_s(stream));
 }
 
 int ifa_logit_state_reset(int slot, const int *prompt_tokens_dev, size_t n_prompt, float rep, float freq, float pres, const int *bias_ids_dev,

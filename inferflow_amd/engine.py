@@ -143,7 +143,8 @@ class InferenceEngine:
     def generate_lookup(self, query_id, max_new_tokens, prediction=None):
         """Lookup decoding (InferenceEngine::GenerateLookup): up to max_new_tokens greedy tokens, draft tokens taken from
         `prediction` (token ids the output is expected to repeat; None: none) and from the query's own tokens, verified in one
-        batched step per draft.  Returns (tokens, {steps, draft_steps, drafted, accepted, gpu_ms})."""
+        batched step per draft.  With `lookup_sampled = true` in the .ini also seeded sampled and processed queries: a draft is
+        accepted where it equals the token drawn on the device.  Returns (tokens, {steps, draft_steps, drafted, accepted, gpu_ms})."""
         out = (C.c_int * max(1, max_new_tokens))()
         st = (C.c_float * 5)()
         pred = list(prediction) if prediction is not None else []
@@ -180,6 +181,13 @@ class InferenceEngine:
     def query_shifted_tokens(self, query_id):
         """Tokens the query's context shifts have dropped so far; -1: unknown id"""
         return _capi.lib().ifa_engine_query_shifted_tokens(self._h, int(query_id))
+
+    def query_rng_state(self, query_id):
+        """The 48-bit state of the query's generator: what its next draw starts from (read-only)"""
+        st = C.c_ulonglong(0)
+        if not _capi.lib().ifa_engine_query_rng_state(self._h, int(query_id), C.byref(st)):
+            raise EngineError(self._err())
+        return st.value
 
     def prefix_cache_stats(self):
         """{active, hits, tokens, copies} of the prompt prefix cache (model_info keys prefix_cache*)"""

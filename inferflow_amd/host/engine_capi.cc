@@ -318,6 +318,8 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "prefix_cache_hits") return (int)std::min<long long>(e->engine.prefix_cache_hits(), 0x7FFFFFFF);
     if (k == "prefix_cache_tokens") return (int)std::min<long long>(e->engine.prefix_cache_tokens(), 0x7FFFFFFF);
     if (k == "lookup_decoding") return e->engine.lookup_decoding_active() ? 1 : 0;
+    if (k == "lookup_sampled") return e->engine.lookup_sampled_active() ? 1 : 0;
+    if (k == "lookup_sampled_steps") return (int)std::min<long long>(e->engine.lookup_sampled_steps(), 0x7FFFFFFF);
     if (k == "logit_processors") return e->engine.SupportsLogitProcessors() ? 1 : 0;
     if (k == "processed_steps") return (int)std::min<long long>(e->engine.processed_steps(), 0x7FFFFFFF);
     if (k == "context_shift") return e->engine.ShiftsContext() ? 1 : 0;
@@ -331,6 +333,12 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
 int ifa_engine_query_cached_tokens(ifa_engine *e, int query_id) { return e ? e->engine.QueryCachedTokens(query_id) : -1; }
 
 int ifa_engine_query_shifted_tokens(ifa_engine *e, int query_id) { return e ? e->engine.QueryShiftedTokens(query_id) : -1; }
+
+int ifa_engine_query_rng_state(ifa_engine *e, int query_id, unsigned long long *state)
+{
+    if (!e || !state) { EngineSetError("ifa_engine_query_rng_state: bad arguments"); return 0; }
+    return e->engine.QueryRngState(query_id, state) ? 1 : 0;
+}
 
 int ifa_engine_shift_query(ifa_engine *e, int query_id, int keep, int discard)
 {

@@ -130,6 +130,7 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "lookup_ngram_max", config.lookup_ngram_max);
     cfg.GetItem(section, "lookup_ngram_min", config.lookup_ngram_min);
     if (!LookupConfigOk(config)) return false;
+    cfg.GetItem(section, "lookup_sampled", config.lookup_sampled);
     cfg.GetItem(section, "is_study_mode", config.debug.is_study_mode);
     cfg.GetItem(section, "show_tensors", config.debug.show_tensors);
     return true;

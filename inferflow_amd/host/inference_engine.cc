@@ -30,7 +30,7 @@ void InferenceEngine::Clear()
     use_clock_ = prefix_hits_ = prefix_tokens_ = prefix_copies_ = 0;
     processed_steps_ = 0;
     shift_active_ = false; context_shifts_ = context_shift_tokens_ = 0;
-    device_sampler_active_ = false; device_sampled_steps_ = 0;
+    device_sampler_active_ = false; device_sampled_steps_ = 0; lookup_sampled_steps_ = 0;
 }
 
 bool InferenceEngine::Init(const InferenceConfig &cfg)
@@ -645,17 +645,22 @@ InferenceEngine::Query *InferenceEngine::FindQuery(int query_id)
 bool InferenceEngine::DeviceGreedyOk(const Query &q, int n_new, bool lookup)
 {
     if (q.ended) { EngineSetError("Query %d has ended", q.id); return false; }
-    // device sampler: Generate (not GenerateLookup) draws on the device for the strategies its rule covers and runs the processors there
-    const bool drawn = !lookup && DeviceDrawn(q);
+    // device sampler: Generate -- and with lookup_sampled GenerateLookup -- draws on the device for the strategies its rule covers and
+    // runs the processors there
+    const bool sampler = lookup ? lookup_sampled_active() : device_sampler_active_;
+    const bool drawn = sampler && DeviceDrawn(q);
     if (drawn && host_greedy_)
-        EngineSetError("Generate() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size());
+        EngineSetError(lookup ? "GenerateLookup() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)"
+                              : "Generate() decodes on the device, whose argmax excludes at most 3 token ids; this vocabulary has %zu (use Infer / CommitInferenceResult)", default_sampling_.excluded_ids.size());
     else if (drawn && (PoolLen(q) < 1 || PoolLen(q) > IFA_POOL_MAX))
-        EngineSetError("Generate() draws from a device pool of at most %d candidates; query %d asks for %d (use Infer / CommitInferenceResult)", IFA_POOL_MAX, q.id, PoolLen(q));
+        EngineSetError(lookup ? "GenerateLookup() draws from a device pool of at most %d candidates; query %d asks for %d (use Infer / CommitInferenceResult)"
+                              : "Generate() draws from a device pool of at most %d candidates; query %d asks for %d (use Infer / CommitInferenceResult)", IFA_POOL_MAX, q.id, PoolLen(q));
     else if (drawn) {
         if (q.shift_on || (int)q.tokens.size() + n_new <= MaxContextLen()) return true;
-        EngineSetError("Generate: %zu tokens + %d steps exceed max_context_len %d", q.tokens.size(), n_new, MaxContextLen());
-    } else if (device_sampler_active_ && !lookup && q.strategy != SamplingStrategyId::Greedy)
-        EngineSetError("Generate() draws on the device for sample.std, top_k, sample.top_p and min_p; query %d uses strategy %d (tfs, typical, mirostat, fsd and random_fsd stay with Infer / CommitInferenceResult)", q.id, (int)q.strategy);
+        EngineSetError(lookup ? "GenerateLookup: %zu tokens + %d new tokens exceed max_context_len %d" : "Generate: %zu tokens + %d steps exceed max_context_len %d", q.tokens.size(), n_new, MaxContextLen());
+    } else if (sampler && q.strategy != SamplingStrategyId::Greedy)
+        EngineSetError(lookup ? "GenerateLookup() draws on the device for sample.std, top_k, sample.top_p and min_p; query %d uses strategy %d (tfs, typical, mirostat, fsd and random_fsd stay with Infer / CommitInferenceResult)"
+                              : "Generate() draws on the device for sample.std, top_k, sample.top_p and min_p; query %d uses strategy %d (tfs, typical, mirostat, fsd and random_fsd stay with Infer / CommitInferenceResult)", q.id, (int)q.strategy);
     else if (q.options.Processed())
         EngineSetError(lookup ? "GenerateLookup() feeds the token back on the device without logit processors; query %d has penalties or a logit_bias (use Infer / CommitInferenceResult)"
                               : "Generate() feeds the token back on the device without logit processors; query %d has penalties or a logit_bias (use Infer / CommitInferenceResult)", q.id);
@@ -691,6 +696,14 @@ bool InferenceEngine::PrefillPending(Query &q, std::vector<int> &new_tokens, int
     if (st) { st->gpu_ms += MsSince(t0); st->steps++; }
     q.processed = (int)q.tokens.size();
     q.tokens.push_back(next); new_tokens.push_back(next); left--;
+    return true;
+}
+
+bool InferenceEngine::QueryRngState(int query_id, unsigned long long *state)
+{
+    Query *q = FindQuery(query_id);
+    if (!q || !state) return false;
+    *state = q->rng.State();
     return true;
 }
 
@@ -797,7 +810,18 @@ bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vect
     const int max_ctx = MaxContextLen();
     int left = max_new_tokens;
     if (!ShiftIfFull(q)) return false;
-    if (!PrefillPending(q, new_tokens, left, &st)) return false;
+    // lookup_sampled: the query's tokens are drawn on the device (the queries DeviceGreedyOk has just let through)
+    const bool drawn = lookup_sampled_active() && DeviceDrawn(q);
+    const bool processed = drawn && q.options.Processed();
+    if (drawn) {
+        const size_t had = new_tokens.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!PrefillPendingDrawn(q, new_tokens, left)) return false;
+        if (new_tokens.size() > had) { st.gpu_ms += MsSince(t0); st.steps++; }
+    } else if (!PrefillPending(q, new_tokens, left, &st)) return false;
+    ifa_sample_params sp;
+    sp.strategy_id = (int)q.strategy; sp.temperature = q.options.temperature; sp.top_p = q.sampling.top_p; sp.max_k = q.sampling.max_k;
+    sp.min_p = q.sampling.min_p; sp.pool_size = drawn ? PoolLen(q) : 1;
     const int *pred = prediction && !prediction->empty() ? prediction->data() : nullptr;
     const int n_pred = pred ? (int)prediction->size() : 0;
     int row[8], next[8];
@@ -814,7 +838,8 @@ bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vect
         st.steps++;
         if (m == 0) {                                  // nothing to guess: one plain step
             float ms = 0;
-            if (ifa_model_decode(model_, q.tokens.back(), pos0, 1, next, &ms) != IFA_OK) { EngineSetError("decode failed: %s", ifa_last_error()); if (stats) *stats = st; return false; }
+            if (drawn) { if (!DecodeDrawn(q, 1, next, &ms)) { if (stats) *stats = st; return false; } }
+            else if (ifa_model_decode(model_, q.tokens.back(), pos0, 1, next, &ms) != IFA_OK) { EngineSetError("decode failed: %s", ifa_last_error()); if (stats) *stats = st; return false; }
             st.gpu_ms += ms;
             q.tokens.push_back(next[0]); new_tokens.push_back(next[0]);
             q.processed = pos0 + 1;
@@ -823,16 +848,32 @@ bool InferenceEngine::GenerateLookup(int query_id, int max_new_tokens, std::vect
         }
         row[0] = q.tokens.back();
         const auto t0 = std::chrono::steady_clock::now();
-        if (ifa_model_decode_draft(model_, m + 1, row, pos0, next, nullptr) != IFA_OK) { EngineSetError("draft step failed: %s", ifa_last_error()); if (stats) *stats = st; return false; }
-        st.gpu_ms += MsSince(t0);
         int a = 0;
-        while (a < m && next[a] == row[a + 1]) a++;
+        if (drawn) {
+            // the rows drawn one after the other on the device with the query's generator: draft i is accepted exactly where it IS the
+            // draw of row i - 1, so the emitted tokens are what a row-by-row loop over these logits rows draws
+            if (processed && !CountQuery(q)) { if (stats) *stats = st; return false; }      // every committed token counted before the step reads the slot
+            unsigned long long state = q.rng.State();
+            int emitted = 0;
+            if (ifa_model_decode_draft_sampled(model_, m + 1, row, pos0, &sp, &state, processed ? q.kv_slot : -1, next, &emitted) != IFA_OK) {
+                EngineSetError("sampled draft step failed: %s", ifa_last_error()); if (stats) *stats = st; return false;
+            }
+            q.rng.SetState(state);
+            a = emitted - 1;
+            lookup_sampled_steps_++;
+            if (processed) processed_steps_++;
+        } else {
+            if (ifa_model_decode_draft(model_, m + 1, row, pos0, next, nullptr) != IFA_OK) { EngineSetError("draft step failed: %s", ifa_last_error()); if (stats) *stats = st; return false; }
+            while (a < m && next[a] == row[a + 1]) a++;
+        }
+        st.gpu_ms += MsSince(t0);
         st.draft_steps++; st.drafted += m; st.accepted += a;
         // rows pos0 .. pos0 + a hold the last token and the a accepted drafts -- the tokens in front of the newest one; the rejected
         // rows behind them lie outside tokens[0 .. processed) (the prefix cache's record) and the next step overwrites them
         for (int i = 0; i <= a; i++) { q.tokens.push_back(next[i]); new_tokens.push_back(next[i]); }
         q.processed = pos0 + a + 1;
         left -= a + 1;
+        if (processed && !CountQuery(q)) { if (stats) *stats = st; return false; }      // (the draft step counts nothing itself)
     }
     if (stats) *stats = st;
     return true;

@@ -123,6 +123,13 @@ struct InferenceConfig {
     // (host/lookup_draft.h).  Applies to a single-device engine with return_output_tensors = false; elsewhere the keys are accepted
     // and GenerateLookup is refused (model_info "lookup_decoding" = 0).
     int lookup_draft_len = 4, lookup_ngram_max = 3, lookup_ngram_min = 1;
+    // extension: lookup decoding for the queries the device sampler covers.  GenerateLookup also takes seeded sampled queries
+    // (sample.std, top_k, sample.top_p, min_p) and processed queries (sampled or greedy): a draft step ends in the verify chain on
+    // the device (ifa_model_decode_draft_sampled: the rows drawn one after the other with the query's generator, a draft accepted
+    // exactly where it equals the draw), so the tokens are the ones a row-by-row loop over the same logits rows draws.  Active only
+    // where device_sampler and lookup decoding both are (model_info "lookup_sampled"); off by default: GenerateLookup then refuses
+    // such queries as before.
+    bool lookup_sampled = false;
     // extension: context shift (host/context_shift.h; DESIGN.md "Context shift").  A query whose tokens reach max_context_len does not
     // end: the engine keeps its first context_shift_keep cache rows, drops the older half of the rows behind them and moves the rest
     // down on the device (ifa_model_kv_shift: K rows re-rotated to their new positions), then goes on.  An approximation by design
@@ -151,7 +158,7 @@ struct QueryOptions {               // SamplingStrategy::QueryOptions (sampling_
     // generated ids (x - (f * count + (count > 0 ? p : 0))); logit_bias: (id, value) pairs added last, -inf bans the id.  A query
     // with any of them non-neutral is PROCESSED: its steps end in the device pool whatever device_sampling_pool says, a greedy one
     // takes the pool's best entry, logprobs are those of the processed distribution at temperature 1.  Single-device engines with
-    // return_output_tensors = false only; GenerateLookup refuses a processed query, Generate takes one only with device_sampler on.
+    // return_output_tensors = false only; Generate takes a processed query only with device_sampler on, GenerateLookup only with lookup_sampled on as well.
     float repetition_penalty = 1.0f, presence_penalty = 0.0f, frequency_penalty = 0.0f;
     std::vector<std::pair<int, float>> logit_bias;
     static const int MAX_LOGIT_BIAS = 1024;
@@ -276,6 +283,11 @@ public:
     bool GenerateLookup(int query_id, int max_new_tokens, std::vector<int> &new_tokens, const std::vector<int> *prediction = nullptr,
                         LookupStats *stats = nullptr);
     bool lookup_decoding_active() const { return model_ && !multi_ && !config_.return_output_tensors; }
+    // InferenceConfig::lookup_sampled: whether GenerateLookup takes sampled / processed queries here; draft steps taken that way
+    bool lookup_sampled_active() const { return config_.lookup_sampled && device_sampler_active_ && lookup_decoding_active(); }
+    long long lookup_sampled_steps() const { return lookup_sampled_steps_; }
+    // the 48-bit state of the query's generator (read-only: what the next draw starts from)
+    bool QueryRngState(int query_id, unsigned long long *state);
 
     // id of a strategy name ("sample.top_p" ...); empty: the model's own decoding_strategy
     SamplingStrategyId GetSamplingStrategyId(const std::string &str = "") const override;
@@ -394,6 +406,7 @@ private:
     long long sampled_fused_steps_ = 0, processed_steps_ = 0;
     bool device_sampler_active_ = false;       // the device_sampler key on a single-device engine without output tensors
     long long device_sampled_steps_ = 0;
+    long long lookup_sampled_steps_ = 0;       // draft steps of GenerateLookup verified by the draw on the device
     bool shift_active_ = false;     // the context_shift key on an engine that can shift
     long long context_shifts_ = 0, context_shift_tokens_ = 0;
     bool pool_lse_on_ = false;      // the worker's option pool_lse as last set

@@ -128,6 +128,18 @@ class DecodeWorker:
                                            C.c_void_p(logits_out.data_ptr()) if logits_out is not None else None))
         return out
 
+    def decode_draft_sampled(self, tokens, pos0, params, rng_state, state_slot=-1):
+        """The draft step for a seeded sampled query (ifa_model_decode_draft_sampled): decode_draft's rows, drawn as a chain on the
+        device.  params: _capi.SampleParams (pool_size = the step's pool length); rng_state: the query's generator state; state_slot:
+        the logit-processor slot, -1 for none.  Returns (emitted tokens int32 [n_out], generator state afterwards)."""
+        toks = np.ascontiguousarray(tokens, np.int32)
+        out = np.full(toks.size, -2, np.int32)
+        st, n_out = C.c_ulonglong(int(rng_state)), C.c_int(0)
+        check(lib().ifa_model_decode_draft_sampled(self._h, toks.size, toks.ctypes.data_as(C.c_void_p), int(pos0), C.byref(params), C.byref(st),
+                                                   int(state_slot), out.ctypes.data_as(C.c_void_p), C.byref(n_out)))
+        assert np.all(out[n_out.value:] == -1), out
+        return out[:n_out.value].copy(), st.value
+
     def decode(self, first_token, start_pos, n_steps, timed=True):
         """Greedy batch-1 decode with the fused kernels; returns (tokens, gpu_ms)."""
         out = np.zeros(n_steps, np.int32)
@@ -538,6 +550,44 @@ def sample_pool_rows(counts, ids, vals, params, rng_states, err, weights=None, s
     return tokens, index
 
 
+def sample_verify_host(counts, ids, vals_f16_bits, params, draft, rng_state, err=0):
+    """ifa_sample_verify_host (no device): the rows of a draft step drawn as a chain.  counts int32 [rows], ids int32 / vals uint16
+    F16 bits [rows][k], params a row of sample_params_array (or _capi.SampleParams), draft int32 [rows - 1] (draft[i]: the guess for
+    the token row i emits), rng_state the query's generator state, err the error word's value before the call.
+    Returns (tokens int32 [rows], index int32 [rows], n_out, generator state afterwards, err)."""
+    counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+    ids = np.ascontiguousarray(ids, np.int32)
+    vals = np.ascontiguousarray(vals_f16_bits).view(np.uint16)
+    rows, k = ids.shape
+    assert counts.size == rows and vals.shape == ids.shape
+    draft = np.ascontiguousarray(draft, np.int32).reshape(-1)
+    assert draft.size >= rows - 1
+    if isinstance(params, np.void):
+        params = np.array([params], params.dtype)
+    pp = C.c_void_p(params.ctypes.data) if isinstance(params, np.ndarray) else C.cast(C.pointer(params), C.c_void_p)
+    st, n_out, e = C.c_ulonglong(int(rng_state)), C.c_int(-1), C.c_int(int(err))
+    tokens, index = np.full(rows, -2, np.int32), np.full(rows, -2, np.int32)
+    check(lib().ifa_sample_verify_host(counts.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p), rows, int(k), pp,
+                                       draft.ctypes.data_as(C.c_void_p) if draft.size else None, C.cast(C.pointer(st), C.c_void_p),
+                                       tokens.ctypes.data_as(C.c_void_p), index.ctypes.data_as(C.c_void_p), C.cast(C.pointer(n_out), C.c_void_p),
+                                       C.cast(C.pointer(e), C.c_void_p)))
+    return tokens, index, n_out.value, st.value, e.value
+
+
+def sample_verify_rows(counts, ids, vals, params, draft, rng_state, err, want_index=True, stream=None):
+    """ifa_sample_verify_rows on torch cuda tensors: counts int32 [rows], ids int32 / vals int16 F16 bits [rows][k], params uint8 bytes
+    of ONE sample_params_array row, draft int32 [rows - 1] (None for one row), rng_state int64 [1] (advances in place), err int32 [1].
+    Returns (tokens int32 [rows], index int32 [rows] or None, n_out int32 [1]); enqueue-only."""
+    import torch
+    rows, k = ids.shape
+    tokens = torch.empty(rows, dtype=torch.int32, device=ids.device)
+    index = torch.empty(rows, dtype=torch.int32, device=ids.device) if want_index else None
+    n_out = torch.empty(1, dtype=torch.int32, device=ids.device)
+    check(lib().ifa_sample_verify_rows(_ptr(counts), _ptr(ids), _ptr(vals), rows, int(k), _ptr(params), _ptr(draft), _ptr(rng_state), _ptr(tokens),
+                                       _ptr(index), _ptr(n_out), _ptr(err), C.c_void_p(stream)))
+    return tokens, index, n_out
+
+
 def logsumexp_rows(logits, n=None, row_idx=None, targets=None, split=True, stream=None):
     """ifa_logsumexp_rows over a torch cuda F16 tensor [rows_avail][stride] (or [n]): the log-sum-exp of the first n entries
     (default: all) of rows row_idx (torch cuda int32; default every row) and, with targets (torch cuda int32, one per row), the
@@ -577,6 +627,19 @@ def logit_adjust_rows(logits, state_slots, state, bias, params, n=None, row_idx=
     out = torch.empty((rows, n), dtype=torch.float16, device=logits.device)
     check(lib().ifa_logit_adjust_rows(_ptr(logits), logits.stride(0), _ptr(row_idx), _ptr(state_slots), rows, n, _ptr(state), _ptr(bias), _ptr(params),
                                       _ptr(out), C.c_void_p(stream)))
+    return out
+
+
+def logit_adjust_draft_rows(logits, state_slot, draft, state, bias, params, n=None, stream=None):
+    """ifa_logit_adjust_draft_rows over a torch cuda F16 tensor [rows][stride] (any storage offset / stride): the rows of ONE slot's
+    draft step, row r adjusted as ifa_logit_adjust_rows would after ifa_logit_state_add of draft[0..r).  state_slot: cuda int32 [1];
+    draft: cuda int32 [rows - 1] (None for one row); state / bias / params as in logit_adjust_rows.  Returns F16 [rows][n]."""
+    import torch
+    n = logits.shape[1] if n is None else int(n)
+    rows = logits.shape[0]
+    out = torch.empty((rows, n), dtype=torch.float16, device=logits.device)
+    check(lib().ifa_logit_adjust_draft_rows(_ptr(logits), logits.stride(0), _ptr(state_slot), rows, n, _ptr(draft), _ptr(state), _ptr(bias), _ptr(params),
+                                            _ptr(out), C.c_void_p(stream)))
     return out
 
 
