@@ -354,6 +354,63 @@ int ifa_logit_state_reset(int slot, const int *prompt_tokens_dev, size_t n_promp
  * result does not depend on the order); pairs outside [0, n_slots) x [0, n) are skipped */
 int ifa_logit_state_add(const int *slots_dev, const int *tokens_dev, size_t n_pairs, size_t n, size_t n_slots, unsigned *state_dev, ifa_stream stream);
 
+/* ---- the feed of a device-fed batched decode step (csrc/ifa_batch_feed.h, csrc/ifa_batch_feed.hip): what stands between two
+ * batched steps of the same n rows when no host is in the loop.  Per row r of step s = *step:
+ *   not live:   ring[s][r] = -1; pair_slot[r] = -1; nothing else of the row changes.
+ *   live:       t = the row's token by its kind -- ARGMAX: argmax[r] (what the step's masked greedy pick wrote); POOL_BEST:
+ *               pool_ids[j][0], entry 0 of the row's candidate pool (-1 for pool_counts[j] <= 0); DRAWN: drawn[j] (what
+ *               ifa_sample_pool_rows wrote).  j = sel: a step pools and draws only the rows that need it, j is the row's place
+ *               among them (as rows_sel of ifa_model_decode_batch_pool); a j outside 0 .. n-1 has no pool: t = -1.
+ *     t < 0:    the row cannot go on (an empty pool, a NaN, a missing array, an unknown kind): live = 0, ring[s][r] = -1,
+ *               pair_slot[r] = -1, and *err = 1 + s * n + r if that word is 0.  Of several such rows the first step's lowest row
+ *               owns the word; later ones never overwrite it.
+ *     else:     ring[s][r] = t; emitted += 1; rng_final = rng[j] for a j inside 0 .. n-1 (the generator as it stands behind this row's draw);
+ *               pair_slot[r] = state_slot, pair_tok[r] = t (the pair ifa_logit_state_add counts; it skips a slot of -1);
+ *               t among stop_ids[0 .. n_stop): live = 0 -- the row is frozen: it stays in the step, so that n and with it every
+ *               other row's arithmetic does not change, and reprocesses the same token at the same position;
+ *               otherwise tok[r] = t, pos[r] += 1 and attn_rows[l][r].n_ctx += 1 for every layer l.
+ *   *step = s + 1.  A step outside 0 .. ring_steps-1 changes nothing and stores -1 into *err if that word is 0.
+ * attn_rows is the batched step's attention table: [layers][n] entries of IFA_BATCH_ATTN_ROW_BYTES bytes (K cache pointer, V cache
+ * pointer, int32 n_ctx at byte 16, int32 pad).  A frozen row's later draws move rng[j] but never rng_final, and nothing is
+ * counted for it. */
+#define IFA_BATCH_STOP_MAX 8
+#define IFA_BATCH_ROWS_MAX 32
+#define IFA_BATCH_STEPS_MAX 256
+#define IFA_BATCH_LAYERS_MAX 1024
+#define IFA_BATCH_ATTN_ROW_BYTES 24
+enum { IFA_BATCH_KIND_ARGMAX = 0, IFA_BATCH_KIND_POOL_BEST = 1, IFA_BATCH_KIND_DRAWN = 2 };
+typedef struct {
+    int live, emitted, kind, n_stop;
+    int stop_ids[IFA_BATCH_STOP_MAX];
+    int state_slot, sel;
+    unsigned long long rng_final;
+} ifa_batch_feed_row;      /* 64 bytes */
+typedef struct {
+    int struct_size;                        /* sizeof(ifa_batch_feed_args) */
+    int n, layers, ring_steps, k_stride, reserved;
+    ifa_batch_feed_row *rows;               /* [n], in/out */
+    int *step;                              /* [1], in/out */
+    const int *argmax;                      /* [n], nullable */
+    const int *pool_counts, *pool_ids;      /* [n], [n][k_stride]; nullable, both or neither */
+    const int *drawn;                       /* [n], nullable */
+    const unsigned long long *rng;          /* [n], nullable: rng_final is then left alone */
+    int *tok, *pos;                         /* [n], in/out: the step's token and position tables */
+    void *attn_rows;                        /* [layers][n], in/out (nullable for layers == 0) */
+    int *ring;                              /* [ring_steps][n], out */
+    int *pair_slot, *pair_tok;              /* [n], out */
+    int *err;                               /* [1], in/out */
+} ifa_batch_feed_args;
+/* every array in device memory; one launch of one workgroup (the row's thread applies the row's rule, the attention entries are
+ * spread over up to 1024 threads), vector stores only, no atomics; enqueue-only, capturable: what a step depends on -- the step
+ * number included -- is read from device memory, never from the launch's arguments. */
+int ifa_batch_feed_rows(const ifa_batch_feed_args *args_of_device_arrays, ifa_stream stream);
+/* host-only (no device needed): the same code compiled for the CPU on host arrays */
+int ifa_batch_feed_host(const ifa_batch_feed_args *args_of_host_arrays);
+/* counts_dev[r] = min(counts_dev[r], pool_len_dev[r]) for `rows` rows: ifa_topk_pool builds every pool of a step with the step's
+ * one k, a row draws from its own pool length; the pool is exact and ordered, so its first pool_len entries ARE the pool_len-pool.
+ * Goes between ifa_topk_pool and ifa_sample_pool_rows.  Enqueue-only, capturable. */
+int ifa_batch_clamp_counts(int *counts_dev, const int *pool_len_dev, size_t rows, ifa_stream stream);
+
 /* ======================================================================== */
 /* Per-device decode worker: counterpart of GpuInferenceWorker                */
 /* (src/transformer/inference_worker.h:23-62, inference_worker.cc:234-340)    */
@@ -578,6 +635,42 @@ int ifa_model_logit_state_reset(ifa_model *m, int kv_slot, const int *prompt_hos
                                 const int *bias_ids_host, const float *bias_vals_host, int n_bias);
 int ifa_model_logit_state_add(ifa_model *m, int n, const int *kv_slots_host, const int *tokens_host);
 int ifa_model_pool_adjust(ifa_model *m, int n_sel, const int *state_slots_host);
+/* ---- device-fed batched steps (csrc/ifa_engine_batch_steps.hip): n_steps (1..256) batched steps of the same n rows with ONE
+ * synchronisation.  The call equals n_steps calls of ifa_model_decode_batch -- or, for a row that is not plainly greedy, of
+ * ifa_model_decode_batch_pool behind ifa_model_pool_adjust -- for the same rows in the same order, each followed by the feed rule
+ * of ifa_batch_feed_rows with ifa_sample_pool_rows as the draw and ifa_logit_state_add of the rule's (slot, token) pairs: tokens,
+ * generator words, logit state and every K / V byte written are identical.  Row r (nullable rows: all greedy, no stop ids, no
+ * processors): p.strategy_id 1 / 2 / 3 / 4 / 7 with its parameters; a row is pooled unless it is greedy with state_slot -1; the
+ * step's one pool length is the largest p.pool_size among the pooled rows and row r draws from its first
+ * min(count, p.pool_size) entries (ifa_batch_clamp_counts); rng_state is the row's 48-bit generator word, on return the word
+ * behind the row's last own draw; state_slot >= 0 passes the row's logits through the processors of that slot and counts every
+ * token the row emits there; a row that emits one of its n_stop (0..IFA_BATCH_STOP_MAX) stop_ids is frozen: it stays in the
+ * later steps of the call, reprocesses its last token at its last position (rewriting the same cache row with the same bytes) and
+ * emits nothing.  out_tokens_host [n_steps][n]: the emitted tokens, -1 where the row was frozen; emitted_host [n].
+ * How: the tables of the first step are uploaded once; every step replays a captured graph of its own per n -- the step of
+ * ifa_model_decode_batch without the table upload and the copy back -- and the processors, pool, clamp, draw, feed and count
+ * launches follow it on the stream; the call's values travel through device memory written by the call.  The graphs of the other
+ * entry points are neither re-captured nor changed.  elapsed_ms (nullable): device time of the steps from HIP events.
+ * IFA_ERR_STATE, nothing touched: the step of n rows is not ONE fused, captured step (ifa_batch_route_plan: n = 1, a chunked n,
+ * an op-by-op model, options exact_order / perf_stat / graph = 0, a partitioned worker; the message says which).  IFA_ERR_ARG:
+ * n_steps outside 1..256, a position with pos + n_steps > max_ctx, a slot used twice or outside the worker's, a token outside
+ * the vocabulary, an unknown strategy, pool_size outside 1..IFA_POOL_MAX, n_stop outside 0..8, a state slot without logit state,
+ * a struct_size that is not this header's.  IFA_ERR_STATE after the steps: a row had no token to draw (an empty pool); the message
+ * names step and row and the results are not valid. */
+typedef struct {
+    int struct_size;                 /* sizeof(ifa_batch_row) */
+    ifa_sample_params p;
+    int state_slot;                  /* -1: no logit processors */
+    unsigned long long rng_state;    /* in/out */
+    int n_stop;
+    int stop_ids[IFA_BATCH_STOP_MAX];
+    int reserved;
+} ifa_batch_row;
+int ifa_model_decode_batch_steps(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host,
+                                 int n_steps, ifa_batch_row *rows, int *out_tokens_host, int *emitted_host, float *elapsed_ms);
+/* the most rows ifa_model_decode_batch_steps takes on this worker with its options as they stand (32 or 16; every n from 2 up to it
+ * is one fused, captured step); 0: the call is refused whatever n.  Plans only, builds nothing. */
+int ifa_model_batch_steps_rows(ifa_model *m);
 /* A scoring prompt: ifa_model_forward(tokens, n_tokens, prefix_len) with the lm_head over ALL rows into the worker's own logits
  * buffer -- bit for bit the rows ifa_model_forward(..., logits_out_dev) delivers, on the same route (one pass, the two passes of a
  * 34..48-token prompt, options exact_order and perf_stat) -- then ifa_logsumexp_rows over them: lse_host[i] and

@@ -116,6 +116,32 @@ int ifa_engine_perf_stat(ifa_engine *e, unsigned *keys, float *ms, int capacity)
  * ocml's (1 ulp), the host's is libm's: see the known gap in DESIGN.md.  The service shell streams through infer / commit and does not
  * use this call. */
 int ifa_engine_generate(ifa_engine *e, int query_id, int n_steps, int *out_tokens, float *gpu_ms);
+/* extension: ifa_engine_generate for a set of queries (DESIGN.md "Batched Generate"; model_info "batch_generate").  Query i wants up to
+ * max_new[i] new tokens and ends early at one of its stop ids stop_ids[stop_offsets[i] .. stop_offsets[i + 1]) (at most 8 each;
+ * stop_offsets nullable: none).  Pending prompts are prefilled one by one as ifa_engine_generate does; that step's token is the
+ * query's first new token.  Then rounds: the live queries, in ascending id order, run
+ *   k = min(batch_generate_round_steps (.ini, default 32, 1..256), every live query's remaining budget and room to max_context_len)
+ * steps in ONE worker call with ONE synchronisation (ifa_model_decode_batch_steps: every row's token is chosen, tested against its
+ * stop ids and fed back on the device); a query's context shift runs between rounds.  With no stop id hit every query receives
+ * exactly the tokens of the ifa_engine_infer / ifa_engine_commit loop in which each query is committed until it has its max_new
+ * tokens and then left alone; generator state, logit state and cache rows are equal as well, and infer / commit, generate or
+ * another generate_batch continue any of the queries.  A query that emits a stop id ends with it (stopped[i] = 1): it stays in its
+ * round as a frozen row, so the other queries' tokens of that round are unchanged, and the following rounds run without it.  A
+ * round of fewer live queries than max(2, dynamic_batching_min_queries) runs each through ifa_engine_generate's single-row path.
+ * out_tokens[out_offsets[i] .. +counts[i]) receives query i's tokens (out_offsets[i + 1] - out_offsets[i] >= max_new[i]);
+ * stats4 (nullable): {rounds, batched steps, steps taken alone, device milliseconds}.  Returns 0, or -1 with nothing touched:
+ * an unknown or repeated id, a query ifa_engine_generate would refuse (greedy always; sample.std / top_k / sample.top_p / min_p and
+ * processed queries with device_sampler = true), more than 8 stop ids, a multi-GPU engine, return_output_tensors = true, more live
+ * queries than one fused batched step of the model takes. */
+int ifa_engine_generate_batch(ifa_engine *e, int n, const int *query_ids, const int *max_new, const int *stop_ids, const int *stop_offsets,
+                              int *out_tokens, const int *out_offsets, int *counts, int *stopped, float *stats4);
+/* host-only: the round rule (host/step_plan.h, PlanGenerateBatch).  facts = {dynamic_batching_min_queries, batch_generate_round_steps,
+ * fused maximum, device sampler active, multi-GPU, return_output_tensors, n queries, then per query {id, remaining, room, shift on,
+ * kind (0 greedy, 1 processed greedy, 2 drawn), has stop ids}}; out (at least 4 + 2 n ints) = {refusal (0 none, 1 duplicate id,
+ * 2 multi-GPU, 3 output tensors, 4 too many live queries, 5 needs the device sampler, 6 no room, 7 bad argument), the id it names,
+ * route (0 done, 1 device-fed batched round, 2 each query alone), m, then m x {id, steps}} in ascending id order.  0, or -1 (bad
+ * arguments). */
+int ifa_generate_batch_plan(const int *facts, int n_facts, int *out, int n_out);
 /* extension: lookup decoding (prompt-lookup decoding / "predicted outputs").  Up to max_new greedy tokens like ifa_engine_generate,
  * but a step carries the query's last token plus up to `lookup_draft_len` (.ini, default 4, 1..7) draft tokens as rows of ONE
  * batched step on the query's KV slot (ifa_model_decode_draft); every leading draft token that equals the step's own greedy choice

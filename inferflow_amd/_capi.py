@@ -109,6 +109,9 @@ SIGNATURES = {
     "ifa_logit_adjust_draft_rows": (_i, [_vp, _sz, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ifa_logit_state_reset": (_i, [_i, _vp, _sz, _f, _f, _f, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
     "ifa_logit_state_add": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp]),
+    "ifa_batch_feed_rows": (_i, [_vp, _vp]),
+    "ifa_batch_feed_host": (_i, [_vp]),
+    "ifa_batch_clamp_counts": (_i, [_vp, _vp, _sz, _vp]),
     "ifa_model_create": (_i, [_vp, C.POINTER(_vp)]),
     "ifa_model_destroy": (_i, [_vp]),
     "ifa_debug_alloc_fail_at": (_i, [C.c_longlong]),
@@ -142,6 +145,8 @@ SIGNATURES = {
     "ifa_model_logit_state_reset": (_i, [_vp, _i, _vp, _i, _f, _f, _f, _vp, _vp, _i]),
     "ifa_model_logit_state_add": (_i, [_vp, _i, _vp, _vp]),
     "ifa_model_pool_adjust": (_i, [_vp, _i, _vp]),
+    "ifa_model_decode_batch_steps": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ifa_model_batch_steps_rows": (_i, [_vp]),
     "ifa_model_forward_score": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "ifa_model_get_buffer": (_i, [_vp, C.c_char_p, _i, C.POINTER(_vp), C.POINTER(_sz)]),
     "ifa_model_stream": (_vp, [_vp]),
@@ -223,6 +228,8 @@ ENGINE_SIGNATURES = {
     "ifa_engine_last_logits": (_i, [_vp, _i, _vp, _sz, _ip, _ip]),
     "ifa_engine_perf_stat": (_i, [_vp, _vp, _vp, _i]),
     "ifa_engine_generate": (_i, [_vp, _i, _i, _ip, C.POINTER(_f)]),
+    "ifa_engine_generate_batch": (_i, [_vp, _i, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(_f)]),
+    "ifa_generate_batch_plan": (_i, [_ip, _i, _ip, _i]),
     "ifa_engine_generate_lookup": (_i, [_vp, _i, _i, _ip, _i, _ip, C.POINTER(_f)]),
     "ifa_lookup_draft": (_i, [_ip, _i, _ip, _i, _i, _i, _i, _ip]),
     "ifa_engine_perplexity": (_i, [_vp, _ip, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
@@ -265,6 +272,18 @@ class QueryOptionsShift(C.Structure):
 class SampleParams(C.Structure):
     """ifa_sample_params (include/inferflow_amd.h)"""
     _fields_ = [("strategy_id", C.c_int), ("temperature", C.c_float), ("top_p", C.c_float), ("max_k", C.c_int), ("min_p", C.c_float), ("pool_size", C.c_int)]
+
+
+class BatchRow(C.Structure):
+    """ifa_batch_row (include/inferflow_amd.h): one row of ifa_model_decode_batch_steps"""
+    _fields_ = [("struct_size", C.c_int), ("p", SampleParams), ("state_slot", C.c_int), ("rng_state", C.c_ulonglong), ("n_stop", C.c_int),
+                ("stop_ids", C.c_int * 8), ("reserved", C.c_int)]
+
+
+class BatchFeedArgs(C.Structure):
+    """ifa_batch_feed_args (include/inferflow_amd.h): the arrays of one feed, all on the device or all on the host"""
+    _fields_ = [(n, C.c_int) for n in ("struct_size", "n", "layers", "ring_steps", "k_stride", "reserved")] + [(n, C.c_void_p) for n in (
+        "rows", "step", "argmax", "pool_counts", "pool_ids", "drawn", "rng", "tok", "pos", "attn_rows", "ring", "pair_slot", "pair_tok", "err")]
 
 
 class ModelConfig(C.Structure):

@@ -123,6 +123,8 @@ void drop_graphs(ifa_model *m)
     m->batch_graphs.clear();
     for (auto &kv : m->draft_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
     m->draft_graphs.clear();
+    for (auto &kv : m->fed_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
+    m->fed_graphs.clear();
     sampled_drop_graphs(m);
 }
 

@@ -564,6 +564,9 @@ static int batch_route_ready(ifa_model *m, int n, bool logits_out, bool entry, B
     return IFA_OK;
 }
 
+// what ifa_model_decode_batch would run for n rows now: the plan only, nothing is built (ifa_model_decode_batch_steps asks before it touches anything)
+int batch_route_of_call(ifa_model *m, int n, BatchRoute &R) { return batch_route_ready(m, n, false, true, R); }
+
 static int batch_fused_layer(ifa_model *m, const BatchRoute &R, int l, int n, const half_t *x, half_t *xnext, const void *rows_l, bool draft)
 {
     const ifa_model_config &c = m->cfg;
@@ -616,7 +619,7 @@ static int batch_fused_layer(ifa_model *m, const BatchRoute &R, int l, int n, co
 }
 
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
-                         void *logits_out, bool draft)
+                         void *logits_out, bool draft, int fed)
 {
     const ifa_model_config &c = m->cfg;
     const int n_slots = m->slots.empty() ? 1 : (int)m->slots.size();
@@ -645,12 +648,13 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     }
     AttnRowH *rows_h = (AttnRowH *)m->batch_tab.pin.get();
     int *pos_pin = (int *)(rows_h + L_ * (size_t)n);
-    for (size_t l = 0; l < L_; l++)
+    // (a later step of a device-fed call: the tables are the device's, and the pinned twin may still be on its way there)
+    for (size_t l = 0; l < L_ && fed != FED_NEXT; l++)
         for (int r = 0; r < n; r++) {
             AttnRowH &a = rows_h[l * (size_t)n + r];
             a.kc = kv_ptr(m, l, slot_host[r], false); a.vc = kv_ptr(m, l, slot_host[r], true); a.n_ctx = pos_host[r] + 1; a.pad = 0;
         }
-    for (int r = 0; r < n; r++) { pos_pin[r] = pos_host[r]; pos_pin[n + r] = tokens_host[r]; }
+    for (int r = 0; r < n && fed != FED_NEXT; r++) { pos_pin[r] = pos_host[r]; pos_pin[n + r] = tokens_host[r]; }
     const AttnRowH *rows_d = (const AttnRowH *)m->batch_tab.dev.get();
     const int *pos_d = (const int *)(rows_d + L_ * (size_t)n);
     const int *tok_d = pos_d + n;
@@ -663,11 +667,15 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     if ((rc = batch_route_ready(m, n, logits_out != nullptr, false, R))) return rc;
     const bool fused = R.kind == BATCH_FUSED, use_graph = R.captured != 0;
     const int attn_ctx = use_graph ? c.max_ctx : max_ctx;     // LDS sizing of the attention kernel must not depend on the step
-    std::map<int, hipGraphExec_t> &graphs = draft ? m->draft_graphs : m->batch_graphs;
+    if (fed && (!fused || !use_graph || draft)) return ifa_fail(IFA_ERR_STATE, "decode_batch_steps: the step of %d rows is not one fused, captured step", n);
+    std::map<int, hipGraphExec_t> &graphs = fed ? m->fed_graphs : draft ? m->draft_graphs : m->batch_graphs;
+    // device-fed call: the first step's tables go up here, once, outside the captured step
+    if (fed == FED_FIRST) IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab.dev, m->batch_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
     if (use_graph) {
         auto it = graphs.find(n);
         if (it != graphs.end()) {
             IFA_HIP_CHECK(hipGraphLaunch(it->second, m->stream));
+            if (fed) return IFA_OK;
             if ((rc = pool_enqueue(m, m->logits, n))) return rc;
             IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
             if ((rc = wait_err_check("batched decode step"))) { drop_graphs(m); return rc; }      // (the captured steps hold K-parts launches: re-captured without them)
@@ -678,7 +686,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
         IFA_HIP_CHECK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
     }
     auto body = [&]() -> int {
-    IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab.dev, m->batch_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
+    if (!fed) IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab.dev, m->batch_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
     if (fused)
         k_dec_batch_gather<<<dim3(4, (unsigned)T), dim3(256), 0, m->stream>>>((const half_t *)m->g[T_EMBD].data, tok_d, pos_d, (int)D, (int)m->g[T_EMBD].rows,
                                                                               m->x, c.rope_order ? m->brope : nullptr, c.head_dim, c.rope_theta,
@@ -739,7 +747,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
         return IFA_OK;
     }
     if ((rc = ifa_argmax_rows(m->logits, V, V, (size_t)n, m->state + 8, m->state + 3, s))) return rc;      // one launch for the n rows
-    IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned + 8, m->state + 8, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
+    if (!fed) IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned + 8, m->state + 8, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
     return IFA_OK;
     };
     rc = body();
@@ -755,6 +763,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
         graphs[n] = ex;
         IFA_HIP_CHECK(hipGraphLaunch(ex, m->stream));
     } else if (rc) return rc;
+    if (fed) return IFA_OK;
     if (!tp && (rc = pool_enqueue(m, m->logits, n))) return rc;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     if ((rc = wait_err_check("batched decode step"))) { drop_graphs(m); return rc; }

@@ -178,6 +178,47 @@ static int pool_arm(ifa_model *m, int k, int n_sel, const int *rows_sel, const c
 // a pool entry point consumes what ifa_model_pool_adjust armed on EVERY way out, the argument checks in front of pool_arm included
 struct AdjConsume { ifa_model *m; ~AdjConsume() { if (m) m->pool_adj_next.clear(); } };
 
+// ---- device-fed batched steps (ifa_engine_batch_steps.hip): the rows and their state slots are the same for every step of the
+// call, so they go to the device once; a step enqueues pool_enqueue's launches for a batched step and copies nothing to the host
+int pool_fed_begin(ifa_model *m, int k, int n_sel, const int *rows_sel, const int *adj_slots, const char *who)
+{
+    AdjConsume consume{m};
+    m->pool_adj_next.assign(adj_slots, adj_slots + n_sel);
+    int rc = pool_arm(m, k, n_sel, rows_sel, who);
+    if (rc) return rc;
+    m->pool.lse = false;               // (no step of the call hands a log-sum-exp to anybody)
+    int *slot_pin = m->pool_idx.pin + pool_idx_rows(m), *slot_dev = m->pool_idx.dev + pool_idx_rows(m);
+    for (int j = 0; j < n_sel; j++) { m->pool_idx.pin[j] = rows_sel[j]; slot_pin[j] = std::max(adj_slots[j], 0); }
+    hipError_t e = hipMemcpyAsync(m->pool_idx.dev, m->pool_idx.pin, sizeof(int) * (size_t)n_sel, hipMemcpyHostToDevice, m->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(slot_dev, slot_pin, sizeof(int) * (size_t)n_sel, hipMemcpyHostToDevice, m->stream);
+    if (e != hipSuccess) { m->pool = ifa_model::PoolReq(); return ifa_fail(IFA_ERR_HIP, "%s: upload of the pooled rows failed: %s", who, hipGetErrorString(e)); }
+    return IFA_OK;
+}
+
+int pool_fed_enqueue(ifa_model *m, const half_t *logits)
+{
+    const ifa_model::PoolReq &R = m->pool;
+    if (R.adj.empty()) return pool_rows_launch(m, logits, m->pool_idx.dev, 0, R.n_sel, false);
+    int rc;
+    for (int ja = 0; ja < R.n_sel;) {      // runs of armed / raw rows, as in pool_enqueue
+        const bool armed = R.adj[(size_t)ja] >= 0;
+        int jb = ja + 1;
+        while (jb < R.n_sel && (R.adj[(size_t)jb] >= 0) == armed) jb++;
+        if ((rc = pool_rows_launch(m, logits, m->pool_idx.dev + ja, ja, jb, armed))) return rc;
+        ja = jb;
+    }
+    return IFA_OK;
+}
+
+void pool_fed_block(ifa_model *m, int **counts, int **ids, void **vals)
+{
+    *counts = (int *)m->pool_blk.dev.get();
+    *ids = *counts + m->pool.n_sel;
+    *vals = *ids + (size_t)m->pool.n_sel * m->pool.k;
+}
+
+void pool_fed_end(ifa_model *m) { m->pool = ifa_model::PoolReq(); }
+
 // after the step: disarms; copies the staged block out if the step succeeded and every wanted row was served
 static int pool_finish(ifa_model *m, int step_rc, int *ids_host, unsigned short *vals_host, int *counts_host, const char *who)
 {

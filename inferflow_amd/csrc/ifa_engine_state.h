@@ -132,6 +132,12 @@ struct ifa_model : Scratch {
     DevPin<void> batch_tab;
     std::map<int, hipGraphExec_t> batch_graphs;      // captured batched step per batch size (dense models)
     std::map<int, hipGraphExec_t> draft_graphs;      // captured draft step (ifa_model_decode_draft: n rows of ONE slot) per row count
+    // Device-fed batched steps (ifa_model_decode_batch_steps, ifa_engine_batch_steps.hip).  fed_graphs: the batched step per row
+    // count WITHOUT the table upload in front and the copy of the greedy ids behind it -- the tables are uploaded once per call and
+    // advanced on the device (csrc/ifa_batch_feed.hip).  bs_blk: the call's per-row feed state, parameters, generator words, token
+    // ring and error word in device memory (+ pinned twin), written by the call like samp_blk.
+    std::map<int, hipGraphExec_t> fed_graphs;
+    DevPin<int> bs_blk;
     // long-context decode attention (keys split over workgroups): workspace, switch and the context it starts at
     DecAttnSplitWs attn_ws = {nullptr, nullptr, nullptr, 8};      // (what the kernels take: filled from the three owners below; nsplits per launch from the route)
     DevBuf<half_t> attn_ws_S; DevBuf<float> attn_ws_lmax, attn_ws_opart;
@@ -443,14 +449,25 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
                 const PromptRoute *planned = nullptr);
 // ifa_decode_draft_kv.hip: RoPE + cache rows of the n rows of a draft step (rows_l: the layer's AttnRowH[n]) in one launch
 int draft_kv_store_launch(ifa_model *m, int n, const half_t *k, const half_t *v, int stride, const void *rows_l);
+// fed (ifa_model_decode_batch_steps; fused + captured routes only): FED_FIRST uploads the tables of the call's first step in front of
+// the replay, FED_NEXT replays on the tables as the device left them; both only enqueue -- no pool, no copy back, no synchronisation
+enum { FED_OFF = 0, FED_FIRST = 1, FED_NEXT = 2 };
+int batch_route_of_call(ifa_model *m, int n, BatchRoute &R);
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
-                         void *logits_out, bool draft = false);      // draft: the rows share a slot (ifa_model_decode_draft)
+                         void *logits_out, bool draft = false, int fed = FED_OFF);      // draft: the rows share a slot (ifa_model_decode_draft)
 // ---- ifa_engine_pool.hip
 // armed (m->pool.k > 0): ifa_topk_pool over the wanted rows of `logits` ([n_rows][vocab], this step's rows) + the copy of the result
 // block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.
 int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
 // device / pinned staging for n_sel rows of k entries (grown on demand, outside any capture)
 int pool_reserve(ifa_model *m, int n_sel, int k);
+// device-fed batched steps: the request armed once for a call of several steps (adj_slots [n_sel]: state slot of pooled row j, -1 raw),
+// row indices and state slots uploaded once; pool_fed_enqueue: one step's launches of pool_enqueue's batched branch on `logits`,
+// nothing copied to the host; pool_fed_block: where those launches leave counts [n_sel], ids and F16 bits [n_sel][k]
+int pool_fed_begin(ifa_model *m, int k, int n_sel, const int *rows_sel, const int *adj_slots, const char *who);
+int pool_fed_enqueue(ifa_model *m, const half_t *logits);
+void pool_fed_block(ifa_model *m, int **counts, int **ids, void **vals);
+void pool_fed_end(ifa_model *m);
 // ifa_engine_draft_sampled.hip: the tail of a sampled draft step on the n rows of `logits` (m->dsv armed), enqueue-only
 int draft_sampled_enqueue(ifa_model *m, const half_t *logits, int n_rows);
 // ---- ifa_engine_score.hip

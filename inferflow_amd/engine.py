@@ -140,6 +140,29 @@ class InferenceEngine:
             raise EngineError("Generate failed: " + self._err())
         return [out[i] for i in range(n)], ms.value
 
+    def generate_batch(self, items):
+        """Generate for a set of queries (InferenceEngine::GenerateBatch): items = [(query_id, max_new_tokens) or (query_id,
+        max_new_tokens, stop_token_ids)].  The live queries run rounds of device-fed batched steps -- one worker call and one
+        synchronisation per round of at most `batch_generate_round_steps` steps -- and receive the tokens of the infer / commit loop;
+        a query ends early at one of its (at most 8) stop ids.  Returns ({query_id: tokens}, {query_id: stopped}, {rounds,
+        batched_steps, single_steps, gpu_ms})."""
+        items = [(int(it[0]), int(it[1]), [int(t) for t in (it[2] if len(it) > 2 and it[2] is not None else ())]) for it in items]
+        n = len(items)
+        ia = lambda v: (C.c_int * max(1, len(v)))(*v)
+        stop_off, out_off = [0], [0]
+        for _, max_new, stops in items:
+            stop_off.append(stop_off[-1] + len(stops))
+            out_off.append(out_off[-1] + max(0, max_new))
+        out = (C.c_int * max(1, out_off[-1]))()
+        counts, stopped, st = (C.c_int * max(1, n))(), (C.c_int * max(1, n))(), (C.c_float * 4)()
+        rc = _capi.lib().ifa_engine_generate_batch(self._h, n, ia([it[0] for it in items]), ia([it[1] for it in items]),
+                                                   ia([t for it in items for t in it[2]]), ia(stop_off), out, ia(out_off), counts, stopped, st)
+        if rc != 0:
+            raise EngineError("GenerateBatch failed: " + self._err())
+        toks = {items[i][0]: [out[out_off[i] + t] for t in range(counts[i])] for i in range(n)}
+        stats = {"rounds": int(st[0]), "batched_steps": int(st[1]), "single_steps": int(st[2]), "gpu_ms": float(st[3])}
+        return toks, {items[i][0]: bool(stopped[i]) for i in range(n)}, stats
+
     def generate_lookup(self, query_id, max_new_tokens, prediction=None):
         """Lookup decoding (InferenceEngine::GenerateLookup): up to max_new_tokens greedy tokens, draft tokens taken from
         `prediction` (token ids the output is expected to repeat; None: none) and from the query's own tokens, verified in one

@@ -263,6 +263,49 @@ int ifa_engine_generate_lookup(ifa_engine *e, int query_id, int max_new, const i
     return (int)toks.size();
 }
 
+int ifa_engine_generate_batch(ifa_engine *e, int n, const int *query_ids, const int *max_new, const int *stop_ids, const int *stop_offsets,
+                              int *out_tokens, const int *out_offsets, int *counts, int *stopped, float *stats4)
+{
+    if (!e || n < 0 || (n > 0 && (!query_ids || !max_new || !out_tokens || !out_offsets || !counts || !stopped))) { EngineSetError("ifa_engine_generate_batch: bad arguments"); return -1; }
+    std::vector<BatchGenerateItem> items((size_t)n);
+    for (int i = 0; i < n; i++) {
+        items[(size_t)i].query_id = query_ids[i]; items[(size_t)i].max_new_tokens = max_new[i];
+        if (max_new[i] > out_offsets[i + 1] - out_offsets[i]) { EngineSetError("ifa_engine_generate_batch: query %d: room for %d of %d tokens", query_ids[i], out_offsets[i + 1] - out_offsets[i], max_new[i]); return -1; }
+        if (stop_offsets) {
+            if (stop_offsets[i + 1] < stop_offsets[i] || (stop_offsets[i + 1] > stop_offsets[i] && !stop_ids)) { EngineSetError("ifa_engine_generate_batch: stop offsets of query %d", query_ids[i]); return -1; }
+            items[(size_t)i].stop_token_ids.assign(stop_ids + stop_offsets[i], stop_ids + stop_offsets[i + 1]);
+        }
+    }
+    BatchGenerateStats st;
+    const bool ok = e->engine.GenerateBatch(items, nullptr, &st);
+    if (stats4) { stats4[0] = (float)st.rounds; stats4[1] = (float)st.batched_steps; stats4[2] = (float)st.single_steps; stats4[3] = st.gpu_ms; }
+    if (!ok) return -1;
+    for (int i = 0; i < n; i++) {
+        const BatchGenerateItem &it = items[(size_t)i];
+        counts[i] = (int)it.new_tokens.size(); stopped[i] = it.stopped ? 1 : 0;
+        for (size_t t = 0; t < it.new_tokens.size(); t++) out_tokens[out_offsets[i] + (int)t] = it.new_tokens[t];
+    }
+    return 0;
+}
+
+// host-only: the rounds of GenerateBatch (host/step_plan.h)
+int ifa_generate_batch_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    if (!facts || !out || n_facts < 7 || facts[6] < 0 || n_facts != 7 + 6 * facts[6] || n_out < 4 + 2 * facts[6]) { EngineSetError("ifa_generate_batch_plan: bad arguments"); return -1; }
+    GenBatchFacts f;
+    f.min_queries = facts[0]; f.round_steps = facts[1]; f.fused_max = facts[2]; f.device_sampler = facts[3] != 0; f.multi_gpu = facts[4] != 0; f.return_output_tensors = facts[5] != 0;
+    std::vector<GenBatchQuery> qs((size_t)facts[6]);
+    for (size_t i = 0; i < qs.size(); i++) {
+        const int *q = facts + 7 + 6 * i;
+        if (q[4] < 0 || q[4] > 2) { EngineSetError("ifa_generate_batch_plan: query %d: kind %d", q[0], q[4]); return -1; }
+        qs[i].id = q[0]; qs[i].remaining = q[1]; qs[i].room = q[2]; qs[i].shift_on = q[3] != 0; qs[i].kind = (GenKind)q[4]; qs[i].has_stops = q[5] != 0;
+    }
+    const GenBatchPlan p = PlanGenerateBatch(f, qs);
+    out[0] = (int)p.refusal; out[1] = p.refused_id; out[2] = (int)p.route; out[3] = (int)p.ids.size();
+    for (size_t i = 0; i < p.ids.size(); i++) { out[4 + 2 * i] = p.ids[i]; out[5 + 2 * i] = p.steps[i]; }
+    return 0;
+}
+
 // host-only: the draft of lookup decoding (host/lookup_draft.h)
 int ifa_lookup_draft(const int *ctx, int n_ctx, const int *pred, int n_pred, int ngram_max, int ngram_min, int k, int *draft_out)
 {
@@ -326,6 +369,9 @@ int ifa_engine_model_info(ifa_engine *e, const char *key)
     if (k == "context_shift_available") return e->engine.SupportsContextShift() ? 1 : 0;
     if (k == "context_shifts") return (int)std::min<long long>(e->engine.context_shifts(), 0x7FFFFFFF);
     if (k == "context_shift_tokens") return (int)std::min<long long>(e->engine.context_shift_tokens(), 0x7FFFFFFF);
+    if (k == "batch_generate") return e->engine.batch_generate_active() ? 1 : 0;
+    if (k == "batch_generate_steps") return (int)std::min<long long>(e->engine.batch_generate_steps(), 0x7FFFFFFF);
+    if (k == "batch_generate_rounds") return (int)std::min<long long>(e->engine.batch_generate_rounds(), 0x7FFFFFFF);
     if (k == "prefix_cache_copies") return (int)std::min<long long>(e->engine.prefix_cache_copies(), 0x7FFFFFFF);
     return -1;
 }

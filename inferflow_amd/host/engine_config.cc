@@ -126,6 +126,10 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "context_shift", config.context_shift);
     cfg.GetItem(section, "context_shift_keep", config.context_shift_keep);
     if (config.context_shift_keep < 0) { EngineSetError("context_shift_keep must be at least 0 (got %d)", config.context_shift_keep); return false; }
+    cfg.GetItem(section, "batch_generate_round_steps", config.batch_generate_round_steps);
+    if (config.batch_generate_round_steps < 1 || config.batch_generate_round_steps > 256) {
+        EngineSetError("batch_generate_round_steps must be 1..256 (got %d)", config.batch_generate_round_steps); return false;
+    }
     cfg.GetItem(section, "lookup_draft_len", config.lookup_draft_len);
     cfg.GetItem(section, "lookup_ngram_max", config.lookup_ngram_max);
     cfg.GetItem(section, "lookup_ngram_min", config.lookup_ngram_min);

@@ -771,9 +771,16 @@ bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_
     if (!DeviceGreedyOk(q, n_steps, false)) return false;
     if (!multi_ && ifa_model_select_kv(model_, q.kv_slot) != IFA_OK) { EngineSetError("select_kv: %s", ifa_last_error()); return false; }
     if (!ShiftIfFull(q)) return false;
-    const bool drawn = DeviceDrawn(q);
-    if (drawn ? !PrefillPendingDrawn(q, new_tokens, n_steps) : !PrefillPending(q, new_tokens, n_steps, nullptr)) return false;
+    if (DeviceDrawn(q) ? !PrefillPendingDrawn(q, new_tokens, n_steps) : !PrefillPending(q, new_tokens, n_steps, nullptr)) return false;
     float ms_total = 0;
+    if (!DecodeSteps(q, n_steps, new_tokens, ms_total)) return false;
+    if (gpu_ms) *gpu_ms = ms_total;
+    return true;
+}
+
+bool InferenceEngine::DecodeSteps(Query &q, int n_steps, std::vector<int> &new_tokens, float &ms_total)
+{
+    const bool drawn = DeviceDrawn(q);
     while (n_steps > 0) {                              // the device token ring holds 1024 steps per call
         // context shift: run to the limit, shift where Infer would (tokens == max_context_len, in front of the step), continue
         if (!ShiftIfFull(q)) return false;
@@ -789,7 +796,6 @@ bool InferenceEngine::Generate(int query_id, int n_steps, std::vector<int> &new_
         q.processed = (int)q.tokens.size() - 1;
         n_steps -= k;
     }
-    if (gpu_ms) *gpu_ms = ms_total;
     return true;
 }
 

@@ -138,6 +138,10 @@ struct InferenceConfig {
     // "context_shift" = 0).  QueryOptions::context_shift / context_keep override both per query.
     bool context_shift = false;
     int context_shift_keep = 4;
+    // extension: GenerateBatch.  A round of device-fed batched steps is at most this many steps long (1..256): it bounds the steps
+    // a stopped query idles in its round and the wait before the call returns; 32 steps amortise the round's one synchronisation
+    // to well under 0.1 % of the round (a design choice, not a measurement).
+    int batch_generate_round_steps = 32;
     DebugOptions debug;
 };
 
@@ -185,6 +189,12 @@ struct QueryNextToken { int id = 0; bool is_end = false; };
 // what a GenerateLookup call did: worker steps in all, how many of them were draft steps (ifa_model_decode_draft), draft tokens
 // offered and draft tokens that equalled the step's own greedy choice, milliseconds spent inside the worker's step calls
 struct LookupStats { int steps = 0, draft_steps = 0, drafted = 0, accepted = 0; float gpu_ms = 0.0f; };
+
+// GenerateBatch: one query of the call (in: query_id, max_new_tokens, at most 8 stop_token_ids; out: new_tokens, stopped -- the
+// last new token is one of the stop ids) and what the call did: rounds of device-fed batched steps (one synchronisation each), the
+// steps in them, the steps queries took alone under the batching threshold, device milliseconds inside the worker's calls
+struct BatchGenerateItem { int query_id = 0, max_new_tokens = 0; std::vector<int> stop_token_ids; std::vector<int> new_tokens; bool stopped = false; };
+struct BatchGenerateStats { int rounds = 0, batched_steps = 0, single_steps = 0; float gpu_ms = 0.0f; };
 
 struct InferencePerfStat { std::map<uint32_t, float> time_map; };   // key 0: the step end to end (ms); study mode: the reference's per-phase keys, (layer + 1) * 10000 + phase
 
@@ -272,6 +282,21 @@ public:
     // n x {Infer, CommitInferenceResult(the step's token)}: greedy queries always; with InferenceConfig::device_sampler also sampled
     // (sample.std, top_k, sample.top_p, min_p) and processed queries, whose tokens are drawn on the device from the query's generator.
     bool Generate(int query_id, int n_steps, std::vector<int> &new_tokens, float *gpu_ms = nullptr);
+
+    // Extension: Generate for a set of queries (DESIGN.md "Batched Generate").  Pending prompts are prefilled one by one as Generate
+    // does (that step's token is the query's first new token); then rounds: the live queries in ascending id order run
+    // k = min(batch_generate_round_steps, every query's remaining budget and room) steps in ONE worker call with one synchronisation
+    // (ifa_model_decode_batch_steps: tokens chosen, tested against the stop ids and fed back on the device).  With no stop id hit every
+    // query receives exactly the tokens of the Infer / CommitInferenceResult loop in which each query is committed until it has its
+    // max_new_tokens; generator state, logit state and cache rows are equal as well.  A query that emits one of its stop ids ends
+    // there (stopped = true); the others' tokens of that round are unchanged, the next rounds run without it.  Fewer live queries
+    // than max(2, dynamic_batching_min_queries) run each through Generate's single-row path.  Everything is validated before
+    // anything is touched: each query as Generate asks, plus no duplicate or unknown id, no more than 8 stop ids each, a
+    // single-device engine, return_output_tensors = false, no more live queries than one fused batched step takes.
+    bool GenerateBatch(std::vector<BatchGenerateItem> &items, float *gpu_ms = nullptr, BatchGenerateStats *stats = nullptr);
+    bool batch_generate_active() const { return model_ && !multi_ && !config_.return_output_tensors; }
+    long long batch_generate_steps() const { return batch_generate_steps_; }
+    long long batch_generate_rounds() const { return batch_generate_rounds_; }
 
     // Extension: lookup decoding (prompt-lookup / "predicted outputs").  Up to max_new_tokens greedy tokens like Generate, but a step
     // carries the query's last token PLUS draft tokens -- the continuation of the context's last n-gram in `prediction` (nullable),
@@ -377,6 +402,9 @@ private:
     bool CountQuery(Query &q);                  // CountCommitted for one query
     bool PrefillPendingDrawn(Query &q, std::vector<int> &new_tokens, int &left);       // the first token from the pool step, like Infer
     bool DecodeDrawn(Query &q, int k, int *out, float *gpu_ms);
+    // n_steps of Generate's single-row path behind the prefill (the loop of Generate; GenerateBatch under the batching threshold)
+    bool DecodeSteps(Query &q, int n_steps, std::vector<int> &new_tokens, float &ms_total);
+    long long batch_generate_steps_ = 0, batch_generate_rounds_ = 0;
     // ---- multi-GPU partitions (devices = 0&1 | 0;1 | 0&1;2&3): one worker and one host thread per GPU, like the
     // reference's Infer_TensorParallelism / Infer_Std over GpuInferenceWorker threads (inference_engine.cc:1161-1296).
     // MultiGpu and everything that looks inside it: inference_engine_multi.cc

@@ -51,4 +51,44 @@ BatchStepPlan PlanBatchStep(bool return_output_tensors, const std::vector<BatchR
     return p;
 }
 
+GenBatchPlan PlanGenerateBatch(const GenBatchFacts &f, const std::vector<GenBatchQuery> &queries)
+{
+    GenBatchPlan p;
+    auto refuse = [&](GenRefusal why, int id) { p = GenBatchPlan(); p.refusal = why; p.refused_id = id; return p; };
+    if (f.multi_gpu) return refuse(GenRefusal::MultiGpu, 0);
+    if (f.return_output_tensors) return refuse(GenRefusal::OutputTensors, 0);
+    if (f.round_steps < 1 || f.round_steps > 256) return refuse(GenRefusal::BadArgument, 0);
+    std::vector<const GenBatchQuery *> live;
+    for (size_t i = 0; i < queries.size(); i++) {
+        const GenBatchQuery &q = queries[i];
+        if (q.remaining < 0 || q.room < 0) return refuse(GenRefusal::BadArgument, q.id);
+        for (size_t j = 0; j < i; j++) if (queries[j].id == q.id) return refuse(GenRefusal::Duplicate, q.id);
+    }
+    for (const GenBatchQuery &q : queries) {
+        if (q.kind != GenKind::Greedy && !f.device_sampler) return refuse(GenRefusal::NeedsSampler, q.id);
+        if (!q.shift_on && q.remaining > q.room) return refuse(GenRefusal::NoRoom, q.id);
+        if (q.remaining > 0) live.push_back(&q);
+    }
+    const bool batched = (int)live.size() >= std::max(2, f.min_queries);
+    if (batched && (int)live.size() > f.fused_max) return refuse(GenRefusal::TooMany, 0);
+    if (live.empty()) return p;
+    std::sort(live.begin(), live.end(), [](const GenBatchQuery *a, const GenBatchQuery *b) { return a->id < b->id; });
+    if (batched) {
+        int k = f.round_steps;
+        for (const GenBatchQuery *q : live) k = std::min(k, std::min(q->remaining, q->room));
+        if (k < 1) return refuse(GenRefusal::NoRoom, live[0]->id);      // (a shift-on query at the limit with nothing to drop)
+        p.route = GenRoute::Fed;
+        for (const GenBatchQuery *q : live) { p.ids.push_back(q->id); p.steps.push_back(k); }
+        return p;
+    }
+    p.route = GenRoute::Single;
+    for (const GenBatchQuery *q : live) {
+        int k = q->remaining;
+        if (q->has_stops) k = q->kind == GenKind::Greedy ? std::min(std::min(q->remaining, q->room), f.round_steps) : 1;
+        if (k < 1) return refuse(GenRefusal::NoRoom, q->id);
+        p.ids.push_back(q->id); p.steps.push_back(k);
+    }
+    return p;
+}
+
 } // namespace inferflow_amd

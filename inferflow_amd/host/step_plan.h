@@ -47,4 +47,39 @@ struct BatchStepPlan {
 //  4. want_logits = return_output_tensors || a host-sampled row is left.
 BatchStepPlan PlanBatchStep(bool return_output_tensors, const std::vector<BatchRow> &rows);
 
+// ---- InferenceEngine::GenerateBatch (DESIGN.md "Batched Generate"): the next round of a set of queries, or why the call is refused.
+enum class GenKind { Greedy = 0, ProcessedGreedy = 1, Drawn = 2 };
+struct GenBatchQuery {
+    int id = 0;
+    int remaining = 0;                      // new tokens the query still wants (0: it takes no part any more)
+    int room = 0;                           // tokens it can take before max_context_len (after the shift in front of the round)
+    bool shift_on = false;                  // context shift: the query goes on behind the limit, a round does not cross it
+    GenKind kind = GenKind::Greedy;
+    bool has_stops = false;
+};
+struct GenBatchFacts {
+    int min_queries = 2;                    // dynamic_batching_min_queries
+    int round_steps = 32;                   // batch_generate_round_steps
+    int fused_max = 32;                     // rows one fused batched step takes
+    bool device_sampler = false, multi_gpu = false, return_output_tensors = false;
+};
+enum class GenRefusal { None = 0, Duplicate = 1, MultiGpu = 2, OutputTensors = 3, TooMany = 4, NeedsSampler = 5, NoRoom = 6, BadArgument = 7 };
+enum class GenRoute { Done = 0, Fed = 1, Single = 2 };
+struct GenBatchPlan {
+    GenRefusal refusal = GenRefusal::None;
+    int refused_id = 0;                     // the query the refusal names (0: the call as a whole)
+    GenRoute route = GenRoute::Done;
+    std::vector<int> ids;                   // the round's queries, ascending ids (Infer's batch order)
+    std::vector<int> steps;                 // per query of ids; Fed: the same number for all
+};
+// Refusals, in this order, nothing planned with one: a multi-GPU engine; return_output_tensors; round_steps outside 1..256 or a
+// negative budget (BadArgument); an id given twice; a drawn or processed query without the device sampler; a query without the
+// context shift whose budget exceeds its room; a batched round (below) of more live queries (remaining > 0) than fused_max.
+// Live queries in ascending id order.  None: Done.  At least max(2, min_queries): Fed, steps = min(round_steps, min over the live
+// queries of remaining and room) -- a query runs out of budget only at a round boundary, where the Infer / Commit loop loses it too.
+// Fewer: Single, each live query through Generate's single-row path on its own: the whole budget without stop ids; with stop ids a
+// greedy query min(remaining, room, round_steps) steps, trimmed at the stop id on the host, a processed or drawn one 1 step, so that
+// generator and counts stay exact.
+GenBatchPlan PlanGenerateBatch(const GenBatchFacts &facts, const std::vector<GenBatchQuery> &queries);
+
 } // namespace inferflow_amd

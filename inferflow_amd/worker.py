@@ -119,6 +119,41 @@ class DecodeWorker:
                                            C.c_void_p(logits_out.data_ptr()) if logits_out is not None else None))
         return out
 
+    def decode_batch_steps(self, tokens, positions, slots, n_steps, rows=None, timed=False):
+        """n_steps device-fed batched steps of the same rows with one synchronisation (ifa_model_decode_batch_steps).  rows: None (all
+        greedy, no stop ids) or one dict per row with any of strategy (SampleParams-style tuple (strategy_id, temperature, top_p, max_k,
+        min_p), default greedy), pool_size (default 1), rng_state, state_slot (default -1), stop_ids (at most 8).
+        Returns (tokens int32 [n_steps][n] with -1 where a row was frozen, emitted int32 [n], generator states [n], gpu_ms)."""
+        from ._capi import BatchRow
+        toks = np.ascontiguousarray(tokens, np.int32)
+        pos = np.ascontiguousarray(positions, np.int32)
+        sl = np.ascontiguousarray(slots, np.int32)
+        n = toks.size
+        arr = None
+        if rows is not None:
+            assert len(rows) == n
+            arr = (BatchRow * n)()
+            for r, d in enumerate(rows):
+                b = arr[r]
+                b.struct_size = C.sizeof(BatchRow)
+                sid, temp, top_p, max_k, min_p = d.get("strategy", (2, 1.0, 1.0, 1, 0.0))
+                b.p.strategy_id, b.p.temperature, b.p.top_p, b.p.max_k, b.p.min_p = int(sid), float(temp), float(top_p), int(max_k), float(min_p)
+                b.p.pool_size = int(d.get("pool_size", 1))
+                b.state_slot = int(d.get("state_slot", -1))
+                b.rng_state = int(d.get("rng_state", 0))
+                stops = list(d.get("stop_ids", ()))
+                b.n_stop = len(stops)
+                for i, t in enumerate(stops[:8]):
+                    b.stop_ids[i] = int(t)
+        out = np.full((int(n_steps), n), -2, np.int32)
+        emitted = np.full(n, -2, np.int32)
+        ms = C.c_float(-1.0)
+        check(lib().ifa_model_decode_batch_steps(self._h, n, toks.ctypes.data_as(C.c_void_p), pos.ctypes.data_as(C.c_void_p), sl.ctypes.data_as(C.c_void_p),
+                                                 int(n_steps), arr, out.ctypes.data_as(C.c_void_p), emitted.ctypes.data_as(C.c_void_p),
+                                                 C.byref(ms) if timed else None))
+        states = [int(arr[r].rng_state) for r in range(n)] if arr is not None else [0] * n
+        return out, emitted, states, ms.value
+
     def decode_draft(self, tokens, pos0, logits_out=None):
         """The draft step on the selected KV slot: row i is tokens[i] at position pos0 + i behind rows [0, pos0 + i) -- tokens[0] the
         last committed token, the rest draft tokens (2..8 rows).  Returns the greedy next token of every row."""
@@ -657,6 +692,55 @@ def logit_state_add(slots, tokens, state, stream=None):
     """ifa_logit_state_add: state[slots[i]][tokens[i]] += 1 for every pair (torch cuda int32) in one launch; enqueue-only"""
     assert slots.numel() == tokens.numel()
     check(lib().ifa_logit_state_add(_ptr(slots), _ptr(tokens), slots.numel(), state.shape[1], state.shape[0], _ptr(state), C.c_void_p(stream)))
+
+
+# ifa_batch_feed_row / one entry of the batched step's attention table (include/inferflow_amd.h)
+BATCH_FEED_ROW = np.dtype([("live", np.int32), ("emitted", np.int32), ("kind", np.int32), ("n_stop", np.int32), ("stop_ids", np.int32, (8,)),
+                           ("state_slot", np.int32), ("sel", np.int32), ("rng_final", np.uint64)])
+BATCH_ATTN_ROW = np.dtype([("kc", np.uint64), ("vc", np.uint64), ("n_ctx", np.int32), ("pad", np.int32)])
+BATCH_KIND_ARGMAX, BATCH_KIND_POOL_BEST, BATCH_KIND_DRAWN = 0, 1, 2
+_BATCH_FEED_ARRAYS = ("rows", "step", "argmax", "pool_counts", "pool_ids", "drawn", "rng", "tok", "pos", "attn_rows", "ring", "pair_slot", "pair_tok", "err")
+
+
+def _batch_feed_args(n, layers, arrays, addr):
+    from ._capi import BatchFeedArgs
+    unknown = set(arrays) - set(_BATCH_FEED_ARRAYS)
+    assert not unknown, "batch feed: unknown arrays %s" % sorted(unknown)
+    a = BatchFeedArgs()
+    a.struct_size, a.n, a.layers = C.sizeof(BatchFeedArgs), int(n), int(layers)
+    ring, ids = arrays["ring"], arrays.get("pool_ids")
+    a.ring_steps = int(ring.shape[0])
+    a.k_stride = int(ids.shape[1]) if ids is not None else 0
+    for name in _BATCH_FEED_ARRAYS:
+        v = arrays.get(name)
+        setattr(a, name, addr(v) if v is not None else None)
+    return a
+
+
+def batch_feed_host(n, layers, arrays):
+    """ifa_batch_feed_host (no device): one feed on numpy arrays, updated in place.  arrays: a dict by the pointer names of
+    ifa_batch_feed_args -- rows BATCH_FEED_ROW [n], attn_rows BATCH_ATTN_ROW [layers][n] (None for no layers), ring int32
+    [ring_steps][n], pool_ids int32 [n][k], rng uint64 [n], the others int32; argmax / pool_counts + pool_ids / drawn / rng may be
+    absent.  Every array must be C-contiguous."""
+    for k, v in arrays.items():
+        assert v is None or (isinstance(v, np.ndarray) and v.flags.c_contiguous), k
+    a = _batch_feed_args(n, layers, arrays, lambda v: v.ctypes.data)
+    check(lib().ifa_batch_feed_host(C.byref(a)))
+
+
+def batch_feed_rows(n, layers, arrays, stream=None):
+    """ifa_batch_feed_rows: the same on torch cuda tensors (rows: the bytes of a BATCH_FEED_ROW array, attn_rows: those of a
+    BATCH_ATTN_ROW array, rng int64 bits); enqueue-only."""
+    for k, v in arrays.items():
+        assert v is None or (v.is_cuda and v.is_contiguous()), k
+    a = _batch_feed_args(n, layers, arrays, lambda v: v.data_ptr())
+    check(lib().ifa_batch_feed_rows(C.byref(a), C.c_void_p(stream)))
+
+
+def batch_clamp_counts(counts, pool_len, stream=None):
+    """ifa_batch_clamp_counts: counts[r] = min(counts[r], pool_len[r]) in place (torch cuda int32 [rows]); enqueue-only"""
+    assert counts.numel() == pool_len.numel()
+    check(lib().ifa_batch_clamp_counts(_ptr(counts), _ptr(pool_len), counts.numel(), C.c_void_p(stream)))
 
 
 class TpTopology(C.Structure):
