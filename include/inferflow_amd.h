@@ -906,6 +906,14 @@ int ifa_moe_plan(const int *facts, int n_facts, int *out, int n_out);
  * IFA_ERR_ARG for a layer without experts.  Plans only: launches and allocates nothing. */
 int ifa_model_moe_plan(ifa_model *m, int layer, int T, int caller_norm, int *out, int n_out);
 
+/* The pooled rows ONE step of a pool call serves (csrc/ifa_pool_rows_plan.h, DESIGN.md "Step tails").  Host-only, no GPU needed.
+ * rows_sel[n_sel]: the call's pooled rows, strictly ascending indices into its rows; adj[n_sel] or NULL: state slot of pooled row j, < 0
+ * raw (ifa_model_pool_adjust); cursor: pooled rows the call's earlier steps have served; the step runs the call's rows
+ * [chunk0, chunk0 + n_rows).  runs_out[cap_runs][3] takes (ja, jb, armed) per run of pooled rows [ja, jb): maximal within the step, all
+ * armed or all raw, in order; *n_runs their number; *cursor_out the cursor behind the step. */
+int ifa_pool_rows_plan(const int *rows_sel, const int *adj, int n_sel, int cursor, int chunk0, int n_rows, int *runs_out, int cap_runs,
+                       int *n_runs, int *cursor_out);
+
 #ifdef __cplusplus
 }
 #endif

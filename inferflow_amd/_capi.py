@@ -162,6 +162,7 @@ SIGNATURES = {
     "ifa_gemm_big_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_rows_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_moe_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_pool_rows_plan": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ifa_model_moe_plan": (_i, [_vp, _i, _i, _i, _vp, _i]),
     "ifa_gemm_rows_launches": (_i, [_vp, _i]),
     "ifa_debug_gemm_rows_record": (_i, [_vp, _i, _i]),

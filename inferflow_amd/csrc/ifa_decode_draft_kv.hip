@@ -110,5 +110,6 @@ extern "C" int ifa_model_decode_draft(ifa_model *m, int n, const int *tokens_hos
     IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
     int pos[8], slot[8];
     for (int i = 0; i < n; i++) { pos[i] = pos0 + i; slot[i] = m->cur_slot; }
-    return forward_batch(m, n, tokens_host, pos, slot, next_tokens_host, logits_out_dev, true);
+    StepTail none; TailCursor cur;
+    return forward_batch(m, n, tokens_host, pos, slot, next_tokens_host, logits_out_dev, none, cur, true);
 }

@@ -642,14 +642,14 @@ int launch_lm(ifa_model *m, const half_t *x, half_t *logits_out)
     return launch_lmhead(lm_params(m, x, logits_out), m->g[T_OUT_NORM].present() ? 1 : 0, m->opt_rpw_lm, m->stream);
 }
 
-int enqueue_fused_step(ifa_model *m, int tail)
+int enqueue_fused_step(ifa_model *m, const StepTail &t)
 {
     const ifa_model_config &c = m->cfg;
     hipStream_t s = m->stream;
     int rc;
     // st_on: the previous step's last launch (or ifa_model_decode, for a call's first step) has gathered this step's input; a
     // sampled step always gathers its own (its token is drawn by the step's last launch but one)
-    if ((!m->st_on || tail == STEP_TAIL_SAMPLED) && (rc = launch_gather(m))) return rc;
+    if ((!m->st_on || t.kind == TAIL_SAMPLED) && (rc = launch_gather(m))) return rc;
     half_t *x = m->x, *xnext = m->x2;
     const int l_first = std::min(std::max(m->opt_debug_layer0, 0), c.layers - 1);
     const int n_layers = (m->opt_debug_layers > 0 && l_first + m->opt_debug_layers < c.layers) ? l_first + m->opt_debug_layers : c.layers;
@@ -685,7 +685,7 @@ int enqueue_fused_step(ifa_model *m, int tail)
         }
         std::swap(x, xnext);
     }
-    if (tail == STEP_TAIL_SAMPLED) return sampled_tail_enqueue(m, x);
+    if (t.kind == TAIL_SAMPLED) return sampled_tail_enqueue(m, t, x);
     if (m->st_on) return launch_lm_tail(m, x);
     if ((rc = launch_lm(m, x))) return rc;
     k_dec_argmax_advance<<<dim3(1), dim3(1024), 0, s>>>(m->logits, (int)m->g[T_LM_HEAD].rows, m->state, ifa_model::RING);
@@ -768,7 +768,8 @@ int ifa_model_gemv_plan(ifa_model *m, int layer, int role, int *out, int n_out)
 
 int ifa_model_decode(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms)
 {
-    return decode_impl(m, first_token, start_pos, n_steps, out_tokens_host, elapsed_ms, false);
+    StepTail none; TailCursor cur;
+    return decode_impl(m, first_token, start_pos, n_steps, out_tokens_host, elapsed_ms, false, none, cur);
 }
 
 // Everything a decode call of n_steps from start_pos sets up before its first launch -- the attention variant of the contexts it
@@ -777,7 +778,8 @@ int ifa_model_decode(ifa_model *m, int first_token, int start_pos, int n_steps, 
 // touched (the token / position words are rewritten by every call anyway).
 int ifa_model_decode_prepare(ifa_model *m, int start_pos, int n_steps)
 {
-    return decode_impl(m, 0, start_pos, n_steps, nullptr, nullptr, true);
+    StepTail none; TailCursor cur;
+    return decode_impl(m, 0, start_pos, n_steps, nullptr, nullptr, true, none, cur);
 }
 
 } // extern "C"
@@ -802,24 +804,18 @@ static int qa_err_check(ifa_model *m, int qerr)
 // n greedy steps in a row as one captured, instantiated graph (replaces *graph)
 static int capture_steps(ifa_model *m, int n, hipGraph_t *graph, hipGraphExec_t *exec)
 {
-    int rc = IFA_OK;
-    IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-    IFA_HIP_CHECK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < n && !rc; i++) rc = enqueue_fused_step(m);
-    hipGraph_t gph = nullptr;
-    hipError_t e = hipStreamEndCapture(m->stream, &gph);
-    if (rc) { if (gph) (void)hipGraphDestroy(gph); return rc; }
-    if (e != hipSuccess) return ifa_fail(IFA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-    if (*graph) (void)hipGraphDestroy(*graph);
-    *graph = gph;
-    IFA_HIP_CHECK(hipGraphInstantiate(exec, gph, nullptr, nullptr, 0));
-    return IFA_OK;
+    const StepTail greedy;
+    return capture_graph(m, "decode step", exec, graph, [&] {
+        int rc = IFA_OK;
+        for (int i = 0; i < n && !rc; i++) rc = enqueue_fused_step(m, greedy);
+        return rc;
+    });
 }
 
-// sc: the call draws its tokens on the device (ifa_model_decode_sampled, which has checked that the fused graph route is open)
 int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms, bool prepare_only,
-                const SampledCall *sc)
+                const StepTail &t, TailCursor &cur)
 {
+    const SampledCall *sc = t.kind == TAIL_SAMPLED ? t.sampled : nullptr;      // the call draws its tokens on the device
     IFA_REQUIRE(m && m->finalized, "ifa_model_decode: model not finalized");
     IFA_REQUIRE(n_steps > 0 && n_steps <= ifa_model::RING, "ifa_model_decode: n_steps %d (max %d per call)", n_steps, ifa_model::RING);
     IFA_REQUIRE(start_pos >= 0 && start_pos + n_steps <= m->cfg.max_ctx, "ifa_model_decode: positions [%d,%d) exceed max_ctx %d",
@@ -835,7 +831,7 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
         int tok = first_token;
         for (int i = 0; i < n_steps; i++) {
             int nt = 0;
-            int rc = exact ? forward_exact(m, tok, start_pos + i, nullptr, &nt) : forward_ops(m, &tok, 1, start_pos + i, nullptr, &nt);
+            int rc = exact ? forward_exact(m, tok, start_pos + i, nullptr, &nt, t, cur) : forward_ops(m, &tok, 1, start_pos + i, nullptr, &nt, t, cur);
             if (rc) return rc;
             if (out_tokens_host) out_tokens_host[i] = nt;
             tok = nt;
@@ -865,8 +861,8 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     }
     hipGraphExec_t samp_exec = nullptr;
     if (sc) {
-        if ((rc = sampled_prepare(m, *sc))) return rc;
-        if (m->opt_graph && (rc = sampled_graph(m, &samp_exec))) return rc;
+        if ((rc = sampled_prepare(m, t))) return rc;
+        if (m->opt_graph && (rc = sampled_graph(m, t, &samp_exec))) return rc;
         if ((rc = sampled_begin(m, *sc))) return rc;
     }
     if (!sc && m->opt_graph && !m->graph_exec && (rc = capture_steps(m, 1, &m->graph, &m->graph_exec))) return rc;
@@ -886,18 +882,18 @@ int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *
     for (int i = 0; i < n_steps;) {
         if (sc) {
             if (samp_exec) IFA_HIP_CHECK(hipGraphLaunch(samp_exec, s));
-            else if ((rc = enqueue_fused_step(m, STEP_TAIL_SAMPLED))) return rc;
+            else if ((rc = enqueue_fused_step(m, t))) return rc;
             i++;
             continue;
         }
         if (m->opt_graph && m->graph_exec_n && m->graph_n_steps == S && S > 1 && n_steps - i >= S) { IFA_HIP_CHECK(hipGraphLaunch(m->graph_exec_n, s)); i += S; continue; }
         if (m->opt_graph) IFA_HIP_CHECK(hipGraphLaunch(m->graph_exec, s));
-        else if ((rc = enqueue_fused_step(m))) return rc;
+        else if ((rc = enqueue_fused_step(m, t))) return rc;
         i++;
     }
     th("steps enqueued");
     if (elapsed_ms) IFA_HIP_CHECK(hipEventRecord(e1, s));
-    if (!sc && (rc = pool_enqueue(m, m->logits, 1))) return rc;      // (armed by ifa_model_decode_pool only: the last step's row)
+    if ((rc = tail_enqueue(m, t, cur, m->logits, 1))) return rc;      // (a pool: ifa_model_decode_pool only, the last step's row; the draw is inside the step)
     if (sc && (rc = sampled_copy_back(m))) return rc;
     IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned + 8, m->state + 8, sizeof(int) * (size_t)n_steps, hipMemcpyDeviceToHost, s));
     int *qerr = m->host_pinned + 8 + ifa_model::RING;

@@ -60,7 +60,7 @@ static int exact_matmul(ifa_model *m, const half_t *x, const Tensor &W, const Te
     return exact_gemv_f16x(W.dtype, W.data, W.rows, W.cols, x, b, y, m->stream);
 }
 
-int forward_exact(ifa_model *m, int token, int pos, void *logits_out, int *next_token)
+int forward_exact(ifa_model *m, int token, int pos, void *logits_out, int *next_token, const StepTail &t, TailCursor &cur)
 {
     const ifa_model_config &c = m->cfg;
     std::string why;
@@ -165,8 +165,7 @@ int forward_exact(ifa_model *m, int token, int pos, void *logits_out, int *next_
     if (logits_out) IFA_HIP_CHECK(hipMemcpyAsync(logits_out, m->logits, lm.rows * 2, hipMemcpyDeviceToDevice, m->stream));
     if ((rc = ifa_argmax_masked(m->logits, lm.rows, m->state + 3, m->state, s))) return rc;
     IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned, m->state, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    if ((rc = pool_enqueue(m, m->logits, 1))) return rc;
-    if ((rc = score_enqueue(m, m->logits, 1))) return rc;
+    if ((rc = tail_enqueue(m, t, cur, m->logits, 1))) return rc;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
     if (next_token) *next_token = m->host_pinned[0];
     return IFA_OK;

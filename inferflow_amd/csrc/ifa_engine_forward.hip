@@ -349,7 +349,8 @@ static int rope_store_rows(ifa_model *m, Layer &L, int T, int prefix_len)
 
 // no_head: a chunk of a longer prompt that is not its last one -- the layers only (KV cache rows written), no lm_head / argmax / sync
 // planned: the route ifa_model_forward planned for this very pass (prompt_route_ready); without it the pass plans itself
-int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, bool no_head, const PromptRoute *planned)
+int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, const StepTail &t, TailCursor &cur,
+                bool no_head, const PromptRoute *planned)
 {
     const ifa_model_config &c = m->cfg;
     int rc;
@@ -463,7 +464,7 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
         if (next_token) *next_token = m->host_pinned[0];
         return IFA_OK;
     }
-    const bool all_rows = logits_out || m->score.n > 0;      // the lm_head over every row: for the caller's buffer, or for a scoring prompt
+    const bool all_rows = logits_out || t.kind == TAIL_SCORE;      // the lm_head over every row: for the caller's buffer, or for a scoring prompt
     if (no_head && !all_rows) return IFA_OK;
     PerfSpan sp_out(m, 1000009);         // (ProcessPostLayer: output norm + lm_head, inference_worker.cc:326-336, 673-675)
     if (scale_on(c.out_scale) && (rc = ifa_scale(x, c.out_scale, (size_t)T * D, x, s))) return rc;
@@ -495,8 +496,8 @@ int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, voi
     } else {
         if ((rc = ifa_argmax_masked(m->logits + (size_t)(T - 1) * V, V, m->state + 3, m->state, s))) return rc;
         IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned, m->state, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        if ((rc = pool_enqueue(m, m->logits + (size_t)(T - 1) * V, 1))) return rc;
-        if ((rc = score_enqueue(m, m->logits, T))) return rc;
+        // (all_rows: the T rows; otherwise only the last row is there, and a single-query pool reads that one)
+        if ((rc = tail_enqueue(m, t, cur, all_rows ? m->logits : m->logits + (size_t)(T - 1) * V, all_rows ? T : 1))) return rc;
     }
     const auto host_t1 = std::chrono::steady_clock::now();
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -619,8 +620,9 @@ static int batch_fused_layer(ifa_model *m, const BatchRoute &R, int l, int n, co
 }
 
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
-                         void *logits_out, bool draft, int fed)
+                  void *logits_out, const StepTail &t, TailCursor &cur, bool draft)
 {
+    const bool fed = t.kind == TAIL_FED, fed_next = fed && !t.fed_first;
     const ifa_model_config &c = m->cfg;
     const int n_slots = m->slots.empty() ? 1 : (int)m->slots.size();
     int max_ctx = 0;
@@ -649,12 +651,12 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     AttnRowH *rows_h = (AttnRowH *)m->batch_tab.pin.get();
     int *pos_pin = (int *)(rows_h + L_ * (size_t)n);
     // (a later step of a device-fed call: the tables are the device's, and the pinned twin may still be on its way there)
-    for (size_t l = 0; l < L_ && fed != FED_NEXT; l++)
+    for (size_t l = 0; l < L_ && !fed_next; l++)
         for (int r = 0; r < n; r++) {
             AttnRowH &a = rows_h[l * (size_t)n + r];
             a.kc = kv_ptr(m, l, slot_host[r], false); a.vc = kv_ptr(m, l, slot_host[r], true); a.n_ctx = pos_host[r] + 1; a.pad = 0;
         }
-    for (int r = 0; r < n && fed != FED_NEXT; r++) { pos_pin[r] = pos_host[r]; pos_pin[n + r] = tokens_host[r]; }
+    for (int r = 0; r < n && !fed_next; r++) { pos_pin[r] = pos_host[r]; pos_pin[n + r] = tokens_host[r]; }
     const AttnRowH *rows_d = (const AttnRowH *)m->batch_tab.dev.get();
     const int *pos_d = (const int *)(rows_d + L_ * (size_t)n);
     const int *tok_d = pos_d + n;
@@ -670,21 +672,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     if (fed && (!fused || !use_graph || draft)) return ifa_fail(IFA_ERR_STATE, "decode_batch_steps: the step of %d rows is not one fused, captured step", n);
     std::map<int, hipGraphExec_t> &graphs = fed ? m->fed_graphs : draft ? m->draft_graphs : m->batch_graphs;
     // device-fed call: the first step's tables go up here, once, outside the captured step
-    if (fed == FED_FIRST) IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab.dev, m->batch_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
-    if (use_graph) {
-        auto it = graphs.find(n);
-        if (it != graphs.end()) {
-            IFA_HIP_CHECK(hipGraphLaunch(it->second, m->stream));
-            if (fed) return IFA_OK;
-            if ((rc = pool_enqueue(m, m->logits, n))) return rc;
-            IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-            if ((rc = wait_err_check("batched decode step"))) { drop_graphs(m); return rc; }      // (the captured steps hold K-parts launches: re-captured without them)
-            if (next_tokens) for (int r = 0; r < n; r++) next_tokens[r] = m->host_pinned[8 + r];
-            return IFA_OK;
-        }
-        IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-        IFA_HIP_CHECK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
-    }
+    if (fed && t.fed_first) IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab.dev, m->batch_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
     auto body = [&]() -> int {
     if (!fed) IFA_HIP_CHECK(hipMemcpyAsync(m->batch_tab.dev, m->batch_tab.pin, tab_bytes, hipMemcpyHostToDevice, m->stream));
     if (fused)
@@ -750,33 +738,26 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     if (!fed) IFA_HIP_CHECK(hipMemcpyAsync(m->host_pinned + 8, m->state + 8, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, m->stream));
     return IFA_OK;
     };
-    rc = body();
     if (use_graph) {
-        // forward ops swap m->x / m->f per layer: an odd layer count would leave them exchanged between replays
-        hipGraph_t gph = nullptr;
-        hipError_t e = hipStreamEndCapture(m->stream, &gph);
-        if (rc) { if (gph) (void)hipGraphDestroy(gph); return rc; }
-        if (e != hipSuccess) return ifa_fail(IFA_ERR_HIP, "hipStreamEndCapture (batched step): %s", hipGetErrorString(e));
-        hipGraphExec_t ex = nullptr;
-        IFA_HIP_CHECK(hipGraphInstantiate(&ex, gph, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(gph);
-        graphs[n] = ex;
-        IFA_HIP_CHECK(hipGraphLaunch(ex, m->stream));
-    } else if (rc) return rc;
+        // (forward ops swap m->x / m->f per layer: an odd layer count would leave them exchanged between replays)
+        auto it = graphs.find(n);
+        if (it == graphs.end()) {
+            hipGraphExec_t ex = nullptr;
+            if ((rc = capture_graph(m, "batched step", &ex, nullptr, body))) return rc;
+            it = graphs.emplace(n, ex).first;
+        }
+        IFA_HIP_CHECK(hipGraphLaunch(it->second, m->stream));
+    } else if ((rc = body())) return rc;
     if (fed) return IFA_OK;
-    if (!tp && (rc = pool_enqueue(m, m->logits, n))) return rc;
+    if (!tp && (rc = tail_enqueue(m, t, cur, m->logits, n))) return rc;
     IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-    if ((rc = wait_err_check("batched decode step"))) { drop_graphs(m); return rc; }
+    if ((rc = wait_err_check("batched decode step"))) { drop_graphs(m); return rc; }      // (the captured steps hold K-parts launches: re-captured without them)
     if (next_tokens) for (int r = 0; r < n; r++) next_tokens[r] = m->host_pinned[8 + r];
     return IFA_OK;
 }
 
-} // namespace ifae
-
-extern "C" {
-
-int ifa_model_forward(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, void *logits_out_dev,
-                      int *next_token_host)
+int forward_impl(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, void *logits_out_dev, int *next_token_host,
+                 const StepTail &t, TailCursor &cur)
 {
     IFA_REQUIRE(m && m->finalized, "ifa_model_forward: model not finalized");
     IFA_REQUIRE(tokens_host, "ifa_model_forward: null tokens");
@@ -786,28 +767,28 @@ int ifa_model_forward(ifa_model *m, const int *tokens_host, int n_tokens, int pr
     if (rc) return rc;
     const size_t V = m->g[T_LM_HEAD].present() ? m->g[T_LM_HEAD].rows : 0;
     if (R.kind == PROMPT_EXACT) {      // order-exact: the tokens one by one through the single-row step (the reference's T = 1 branch for every row)
-        for (int t = 0; t < n_tokens; t++) {
-            rc = forward_exact(m, tokens_host[t], prefix_len + t, logits_out_dev ? (char *)logits_out_dev + (size_t)t * V * 2 : nullptr,
-                               t == n_tokens - 1 ? next_token_host : nullptr);
+        for (int i = 0; i < n_tokens; i++) {
+            rc = forward_exact(m, tokens_host[i], prefix_len + i, logits_out_dev ? (char *)logits_out_dev + (size_t)i * V * 2 : nullptr,
+                               i == n_tokens - 1 ? next_token_host : nullptr, t, cur);
             if (rc) return rc;
         }
         return IFA_OK;
     }
-    if (!R.first_pass) return forward_ops(m, tokens_host, n_tokens, prefix_len, logits_out_dev, next_token_host, false, &R);
+    if (!R.first_pass) return forward_ops(m, tokens_host, n_tokens, prefix_len, logits_out_dev, next_token_host, t, cur, false, &R);
     // Two passes (round 5: 32 tokens, then 2..16 through the rows GEMM, whose weights stream into registers five groups deep, instead of
     // one pass of the op-by-op layer: 40 tokens 7.08 -> 6.35 ms, 48 tokens 7.26 -> 6.67, profiles/r05_prompt_lengths.log; two passes of 17..32
     // rows each -- 49..64 tokens -- measured no faster than the tile kernels).  The second pass reads the first one's K / V rows from the
     // cache like any continued prompt; every row goes through the kernels of a prompt of <= 32 tokens.  Never a one-token pass: a single
     // row takes the int8 GEMV (the reference's rule for ONE row), which is not how a prompt's rows are computed.  Each pass plans itself.
     const int t1 = R.first_pass;
-    if ((rc = forward_ops(m, tokens_host, t1, prefix_len, logits_out_dev, nullptr, true))) return rc;
-    rc = forward_ops(m, tokens_host + t1, n_tokens - t1, prefix_len + t1, logits_out_dev ? (char *)logits_out_dev + (size_t)t1 * V * 2 : nullptr, next_token_host);
+    if ((rc = forward_ops(m, tokens_host, t1, prefix_len, logits_out_dev, nullptr, t, cur, true))) return rc;
+    rc = forward_ops(m, tokens_host + t1, n_tokens - t1, prefix_len + t1, logits_out_dev ? (char *)logits_out_dev + (size_t)t1 * V * 2 : nullptr, next_token_host, t, cur);
     m->prompt_route = R;
     return rc;
 }
 
-int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host,
-                           int *next_tokens_host, void *logits_out_dev)
+int decode_batch_impl(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host, int *next_tokens_host,
+                      void *logits_out_dev, const StepTail &t, TailCursor &cur)
 {
     IFA_REQUIRE(m && m->finalized, "ifa_model_decode_batch: model not finalized");
     IFA_REQUIRE(n >= 1 && n <= ifa_model::RING && tokens_host && positions_host && kv_slots_host, "ifa_model_decode_batch: bad arguments");
@@ -822,7 +803,7 @@ int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const in
         for (int i = 0; i < n && rc == IFA_OK; i++) {
             if ((rc = ifa_model_select_kv(m, kv_slots_host[i]))) break;
             int nt = 0;
-            rc = forward_exact(m, tokens_host[i], positions_host[i], logits_out_dev ? (char *)logits_out_dev + (size_t)i * V * 2 : nullptr, &nt);
+            rc = forward_exact(m, tokens_host[i], positions_host[i], logits_out_dev ? (char *)logits_out_dev + (size_t)i * V * 2 : nullptr, &nt, t, cur);
             if (next_tokens_host) next_tokens_host[i] = nt;
         }
         const int rb = ifa_model_select_kv(m, back);
@@ -838,14 +819,32 @@ int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const in
         const int per = R.chunk;
         for (int c0 = 0; c0 < n; c0 += per) {
             const int nc = std::min(per, n - c0);
-            m->pool.chunk0 = c0; m->pool.last_chunk = c0 + nc >= n;
+            cur.chunk0 = c0; cur.last_chunk = c0 + nc >= n;
             int rc = forward_batch(m, nc, tokens_host + c0, positions_host + c0, kv_slots_host + c0, next_tokens_host ? next_tokens_host + c0 : nullptr,
-                                   logits_out_dev ? (char *)logits_out_dev + (size_t)c0 * m->g[T_LM_HEAD].rows * 2 : nullptr);
+                                   logits_out_dev ? (char *)logits_out_dev + (size_t)c0 * m->g[T_LM_HEAD].rows * 2 : nullptr, t, cur);
             if (rc) return rc;
         }
         return IFA_OK;
     }
-    return forward_batch(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, logits_out_dev);
+    return forward_batch(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, logits_out_dev, t, cur);
+}
+
+} // namespace ifae
+
+extern "C" {
+
+int ifa_model_forward(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, void *logits_out_dev,
+                      int *next_token_host)
+{
+    StepTail none; TailCursor cur;
+    return forward_impl(m, tokens_host, n_tokens, prefix_len, logits_out_dev, next_token_host, none, cur);
+}
+
+int ifa_model_decode_batch(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host,
+                           int *next_tokens_host, void *logits_out_dev)
+{
+    StepTail none; TailCursor cur;
+    return decode_batch_impl(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, logits_out_dev, none, cur);
 }
 
 } // extern "C"

@@ -1,10 +1,11 @@
-// ifa_engine_pool.hip -- worker steps that end in a candidate pool (ifa_model_decode_pool / _decode_batch_pool / _forward_pool):
-// the entry point arms m->pool, runs the ordinary step -- whatever route ifa_model_decode / _decode_batch / _forward takes for
-// this model -- and that step calls pool_enqueue() on its logits in front of its one stream synchronisation: one more launch
-// (csrc/ifa_topk_pool.hip) and one copy of (counts, ids, values) into pinned staging.  Nothing is captured: the pool launch
-// follows the graph replay on the stream.
-// Logit processors (ifa_logit_adjust.hip) hook in here: rows armed by ifa_model_pool_adjust pass through ifa_logit_adjust_rows into
-// m->la_adj first and the pool / log-sum-exp launches read those rows; with nothing armed the launches are the ones above.
+// ifa_engine_pool.hip -- the tails of the worker's steps (StepTail, ifa_engine_state.h; DESIGN.md "Step tails") and the entry points
+// that end in a candidate pool (ifa_model_decode_pool / _decode_batch_pool / _forward_pool).  An entry point builds its tail, runs the
+// ordinary step -- whatever route decode_impl / decode_batch_impl / forward_impl takes for this model -- and that step calls
+// tail_enqueue() on its logits in front of its one stream synchronisation.  A pool tail is one more launch (csrc/ifa_topk_pool.hip)
+// and one copy of (counts, ids, values) into pinned staging; nothing is captured: the launches follow the graph replay on the stream.
+// Logit processors (ifa_logit_adjust.hip): rows armed by ifa_model_pool_adjust pass through ifa_logit_adjust_rows into m->la_adj first
+// and the pool / log-sum-exp launches read those rows.  pool_rows_launch is the one place that enqueues this sequence: the sampled,
+// draft-verify and device-fed tails call it too and differ in what follows it.
 #include <algorithm>
 #include <cmath>
 #include "ifa_engine_state.h"
@@ -19,9 +20,6 @@ int logit_adjust_rows(const void *logits, size_t row_stride, const int *row_idx_
 }
 
 namespace ifae {
-
-// counts [n_sel] | (with_lse: lse [n_sel] |) ids [n_sel][k] | F16 bits [n_sel][k]
-static size_t pool_block_bytes(int n_sel, int k, bool with_lse) { return (size_t)n_sel * (with_lse ? 8 : 4) + (size_t)n_sel * (size_t)k * 6; }
 
 // state / bias / params for every KV slot the worker has now (first use, or more slots since: the old rows are kept)
 static int logit_state_reserve(ifa_model *m)
@@ -49,20 +47,25 @@ static int logit_state_reserve(ifa_model *m)
     return IFA_OK;
 }
 
-static int logit_partitioned(const ifa_model *m, const char *who)
+const char *device_tail_refusal(const ifa_model *m, bool needs_embd, bool fused_only)
 {
-    if (m->cfg.tp_size > 1 || m->topo) return ifa_fail(IFA_ERR_STATE, "%s: the vocabulary of a partitioned worker is sharded; logit processors run on a single-device worker", who);
-    if (!m->g[T_LM_HEAD].present()) return ifa_fail(IFA_ERR_STATE, "%s: lm_head missing (pipeline stage worker)", who);
-    return IFA_OK;
+    if (m->cfg.tp_size > 1 || m->topo) return "the vocabulary of a partitioned worker is sharded";
+    if (!m->g[T_LM_HEAD].present() || (needs_embd && !m->g[T_EMBD].present())) return needs_embd ? "embeddings / lm_head missing (pipeline stage worker)" : "lm_head missing (pipeline stage worker)";
+    if (fused_only && m->opt_exact_order) return "option exact_order steps row by row on the host";
+    if (fused_only && m->opt_perf_stat) return "option perf_stat times the op-by-op step";
+    return nullptr;
 }
 
-// rows the index block serves: its second half holds the state slots of the armed rows
-static size_t pool_idx_rows(const ifa_model *m) { return m->pool_idx.cap() / 2; }
+int device_tail_refusals(const ifa_model *m, const char *who, bool needs_embd, bool fused_only, const char *hint)
+{
+    const char *why = device_tail_refusal(m, needs_embd, fused_only);
+    return why ? ifa_fail(IFA_ERR_STATE, "%s: %s; %s", who, why, hint) : IFA_OK;
+}
 
 // staging for n_sel rows of k entries (grown on demand, outside any capture; one allocation serves every later step)
 int pool_reserve(ifa_model *m, int n_sel, int k)
 {
-    const size_t bytes = pool_block_bytes(std::max(n_sel, 8), IFA_POOL_MAX >= k ? IFA_POOL_MAX : k, true);
+    const size_t bytes = pool_block(nullptr, std::max(n_sel, 8), IFA_POOL_MAX >= k ? IFA_POOL_MAX : k, true).bytes;
     int rc;
     if (bytes > m->pool_blk.cap()) {
         IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -76,162 +79,121 @@ int pool_reserve(ifa_model *m, int n_sel, int k)
     return IFA_OK;
 }
 
-// pool (+ lse) of pooled rows [ja, jb): armed rows first pass through the logit processors into la_adj rows [ja, jb) and are read
-// from there; idx (null: the step's one row) indexes `logits`
-static int pool_rows_launch(ifa_model *m, const half_t *logits, const int *idx, int ja, int jb, bool armed)
+int la_adj_reserve(ifa_model *m, size_t rows, const char *who)
 {
-    ifa_model::PoolReq &R = m->pool;
+    const size_t V = m->g[T_LM_HEAD].rows, want = std::max<size_t>(rows, 8);
+    if (want * V <= m->la_adj.cap()) return IFA_OK;
+    IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
+    if (m->la_adj.alloc(want * V)) return ifa_fail(IFA_ERR_NOMEM, "%s: no memory for %zu adjusted rows", who, want);
+    return IFA_OK;
+}
+
+int pool_rows_launch(ifa_model *m, const PoolBlock &B, int k, const half_t *logits, const int *idx, const int *slots, int ja, int jb)
+{
     const size_t V = m->g[T_LM_HEAD].rows, rows = (size_t)(jb - ja);
-    const int k = R.k, n_sel = R.n_sel;
-    int *counts = (int *)m->pool_blk.dev.get();
-    float *lse = R.lse ? (float *)(counts + n_sel) : nullptr;
-    int *ids = counts + (R.lse ? 2 : 1) * n_sel;
-    uint16_t *vals = (uint16_t *)(ids + (size_t)n_sel * k);
     int rc = IFA_OK;
     const void *src = logits;
-    if (armed) {
+    if (slots) {
         half_t *adj = m->la_adj + (size_t)ja * V;
-        if ((rc = logit_adjust_rows(logits, V, idx, m->pool_idx.dev + pool_idx_rows(m) + ja, rows, V, m->la_state, m->la_bias, m->la_params, adj, m->stream))) return rc;
+        if ((rc = logit_adjust_rows(logits, V, idx, slots, rows, V, m->la_state, m->la_bias, m->la_params, adj, m->stream))) return rc;
         src = adj; idx = nullptr;
     }
-    if ((rc = topk_pool_rows(src, V, idx, rows, V, k, m->pool_excl, ids + (size_t)ja * k, vals + (size_t)ja * k, counts + ja, m->stream))) return rc;
-    if (lse && (rc = lse_rows(src, V, idx, rows, V, nullptr, lse + ja, nullptr, m->lse_part, m->stream))) return rc;
+    if ((rc = topk_pool_rows(src, V, idx, rows, V, k, m->pool_excl, B.ids + (size_t)ja * k, B.vals + (size_t)ja * k, B.counts + ja, m->stream))) return rc;
+    if (B.lse && (rc = lse_rows(src, V, idx, rows, V, nullptr, B.lse + ja, nullptr, m->lse_part, m->stream))) return rc;
     return IFA_OK;
 }
 
-int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows)
+// TAIL_POOL: the pooled rows this step serves, then -- behind the call's last step -- the copy of the block
+static int pool_enqueue(ifa_model *m, const StepTail &t, TailCursor &cur, const half_t *logits, int n_rows)
 {
-    if (m->dsv.k > 0) return draft_sampled_enqueue(m, logits, n_rows);      // (ifa_model_decode_draft_sampled: its own tail, no pool copy)
-    ifa_model::PoolReq &R = m->pool;
-    if (R.k <= 0) return IFA_OK;
-    const int k = R.k, n_sel = R.n_sel;
-    const bool adj = !R.adj.empty();
+    const size_t V = m->g[T_LM_HEAD].rows;
+    const int n_sel = t.n;
+    const bool adj = t.adj != nullptr;
+    const PoolBlock B = pool_block(m->pool_blk.dev.get(), n_sel, t.k, t.lse);
     int *slot_pin = m->pool_idx.pin + pool_idx_rows(m), *slot_dev = m->pool_idx.dev + pool_idx_rows(m);
     int rc = IFA_OK;
-    if (!R.rows_sel) {                 // a single-query step: its one row
+    if (!t.rows_sel) {                 // a single-query step: its last row
         if (adj) {
-            slot_pin[0] = R.adj[0];
+            slot_pin[0] = t.adj[0];
             IFA_HIP_CHECK(hipMemcpyAsync(slot_dev, slot_pin, sizeof(int), hipMemcpyHostToDevice, m->stream));
         }
-        if ((rc = pool_rows_launch(m, logits, nullptr, 0, 1, adj))) return rc;
-        R.done = 1;
+        if ((rc = pool_rows_launch(m, B, t.k, logits + (size_t)(n_rows - 1) * V, nullptr, adj ? slot_dev : nullptr, 0, 1))) return rc;
+        cur.done = 1;
     } else {                           // a batched step (or one chunk of it): the wanted rows among [chunk0, chunk0 + n_rows)
-        int j0 = R.done, j1 = j0;
-        while (j1 < n_sel && R.rows_sel[j1] < R.chunk0 + n_rows) j1++;
+        std::vector<PoolRun> runs;
+        const int j0 = cur.done, j1 = pool_rows_plan(t.rows_sel, t.adj, n_sel, j0, cur.chunk0, n_rows, runs);
         if (j1 > j0) {
-            for (int j = j0; j < j1; j++) m->pool_idx.pin[j] = R.rows_sel[j] - R.chunk0;
+            for (int j = j0; j < j1; j++) m->pool_idx.pin[j] = t.rows_sel[j] - cur.chunk0;
             IFA_HIP_CHECK(hipMemcpyAsync(m->pool_idx.dev + j0, m->pool_idx.pin + j0, sizeof(int) * (size_t)(j1 - j0), hipMemcpyHostToDevice, m->stream));
-            if (!adj) {
-                if ((rc = pool_rows_launch(m, logits, m->pool_idx.dev + j0, j0, j1, false))) return rc;
-            } else {                   // runs of armed / raw rows, each run its own launches (all armed, the usual case: one run)
-                for (int j = j0; j < j1; j++) slot_pin[j] = std::max(R.adj[(size_t)j], 0);
+            if (adj) {
+                for (int j = j0; j < j1; j++) slot_pin[j] = std::max(t.adj[j], 0);
                 IFA_HIP_CHECK(hipMemcpyAsync(slot_dev + j0, slot_pin + j0, sizeof(int) * (size_t)(j1 - j0), hipMemcpyHostToDevice, m->stream));
-                for (int ja = j0; ja < j1;) {
-                    const bool armed = R.adj[(size_t)ja] >= 0;
-                    int jb = ja + 1;
-                    while (jb < j1 && (R.adj[(size_t)jb] >= 0) == armed) jb++;
-                    if ((rc = pool_rows_launch(m, logits, m->pool_idx.dev + ja, ja, jb, armed))) return rc;
-                    ja = jb;
-                }
             }
+            for (const PoolRun &r : runs)      // each run its own launches (nothing or everything armed, the usual case: one run)
+                if ((rc = pool_rows_launch(m, B, t.k, logits, m->pool_idx.dev + r.ja, r.armed ? slot_dev + r.ja : nullptr, r.ja, r.jb))) return rc;
         }
-        R.done = j1;
-        if (!R.last_chunk) return IFA_OK;
+        cur.done = j1;
+        if (!cur.last_chunk) return IFA_OK;
     }
-    IFA_HIP_CHECK(hipMemcpyAsync(m->pool_blk.pin, m->pool_blk.dev, pool_block_bytes(n_sel, k, R.lse), hipMemcpyDeviceToHost, m->stream));
+    IFA_HIP_CHECK(hipMemcpyAsync(m->pool_blk.pin, m->pool_blk.dev, B.bytes, hipMemcpyDeviceToHost, m->stream));
     return IFA_OK;
 }
 
-// arms the request; an error code + message if this worker cannot serve it
-static int pool_arm(ifa_model *m, int k, int n_sel, const int *rows_sel, const char *who)
+int tail_enqueue(ifa_model *m, const StepTail &t, TailCursor &cur, const half_t *logits, int n_rows)
 {
-    // what ifa_model_pool_adjust armed belongs to THIS step, whether it gets as far as a launch or not
-    std::vector<int> adj;
-    adj.swap(m->pool_adj_next);
-    if (std::all_of(adj.begin(), adj.end(), [](int s) { return s < 0; })) adj.clear();
+    switch (t.kind) {
+    case TAIL_POOL: return pool_enqueue(m, t, cur, logits, n_rows);
+    case TAIL_SCORE: return score_enqueue(m, t, cur, logits, n_rows);
+    case TAIL_DRAFT_VERIFY: return draft_sampled_enqueue(m, t, logits, n_rows);
+    case TAIL_NONE: case TAIL_SAMPLED: case TAIL_FED: break;      // (the draw is inside the step; a fed step's caller enqueues what follows)
+    }
+    return IFA_OK;
+}
+
+int pool_ready(ifa_model *m, int k, int n_sel, std::vector<int> &adj, const char *who)
+{
+    if (std::all_of(adj.begin(), adj.end(), [](int slot) { return slot < 0; })) adj.clear();
     IFA_REQUIRE(adj.empty() || (int)adj.size() == n_sel, "%s: ifa_model_pool_adjust armed %zu rows, the step pools %d", who, adj.size(), n_sel);
     IFA_REQUIRE(k >= 1 && k <= IFA_POOL_MAX, "%s: k %d outside 1..%d", who, k, IFA_POOL_MAX);
-    if (m->cfg.tp_size > 1 || m->topo) return ifa_fail(IFA_ERR_STATE, "%s: the vocabulary of a partitioned worker is sharded; the pool is built on the host there", who);
-    if (!m->g[T_LM_HEAD].present()) return ifa_fail(IFA_ERR_STATE, "%s: lm_head missing (pipeline stage worker)", who);
-    IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
-    int rc = pool_reserve(m, n_sel, k);
+    int rc = device_tail_refusals(m, who, false, false, "the pool is built on the host there");
     if (rc) return rc;
+    IFA_HIP_CHECK(hipSetDevice(m->cfg.device));
+    if ((rc = pool_reserve(m, n_sel, k))) return rc;
     if (m->opt_pool_lse && (rc = lse_part_reserve(m))) return rc;
     m->pool_lse_last.clear();
-    m->pool = ifa_model::PoolReq();
-    m->pool.lse = m->opt_pool_lse != 0;
-    m->pool.k = k; m->pool.n_sel = n_sel; m->pool.rows_sel = rows_sel;
-    if (!adj.empty()) {
-        const size_t V = m->g[T_LM_HEAD].rows;
-        for (int s : adj)
-            if (s >= 0 && (size_t)s >= m->la_slots) { m->pool = ifa_model::PoolReq(); return ifa_fail(IFA_ERR_STATE, "%s: state slot %d has no logit state (ifa_model_logit_state_reset first)", who, s); }
-        if ((size_t)n_sel * V > m->la_adj.cap()) {
-            IFA_HIP_CHECK(hipStreamSynchronize(m->stream));
-            const size_t rows = (size_t)std::max(n_sel, 8);
-            if (m->la_adj.alloc(rows * V)) { m->pool = ifa_model::PoolReq(); return ifa_fail(IFA_ERR_NOMEM, "%s: no memory for %zu adjusted rows", who, rows); }
-        }
-        m->pool.adj.swap(adj);
+    for (int slot : adj)
+        if (slot >= 0 && (size_t)slot >= m->la_slots) return ifa_fail(IFA_ERR_STATE, "%s: state slot %d has no logit state (ifa_model_logit_state_reset first)", who, slot);
+    if (!adj.empty() && (rc = la_adj_reserve(m, (size_t)n_sel, who))) return rc;
+    return IFA_OK;
+}
+
+// A pool entry point: what ifa_model_pool_adjust armed belongs to THIS call -- moved out at entry, whether the call gets as far as a
+// launch or not, the argument checks in front of ready() included.  The tail points into the call's own array.
+struct PoolCall {
+    StepTail t; TailCursor cur; std::vector<int> adj;
+    explicit PoolCall(ifa_model *m) { if (m) adj.swap(m->pool_adj_next); }
+    int ready(ifa_model *m, int k, int n_sel, const int *rows_sel, const char *who)
+    {
+        const int rc = pool_ready(m, k, n_sel, adj, who);
+        if (rc) return rc;
+        t.kind = TAIL_POOL; t.k = k; t.n = n_sel; t.rows_sel = rows_sel;
+        t.lse = m->opt_pool_lse != 0;
+        t.adj = adj.empty() ? nullptr : adj.data();
+        return IFA_OK;
     }
-    return IFA_OK;
-}
+};
 
-// a pool entry point consumes what ifa_model_pool_adjust armed on EVERY way out, the argument checks in front of pool_arm included
-struct AdjConsume { ifa_model *m; ~AdjConsume() { if (m) m->pool_adj_next.clear(); } };
-
-// ---- device-fed batched steps (ifa_engine_batch_steps.hip): the rows and their state slots are the same for every step of the
-// call, so they go to the device once; a step enqueues pool_enqueue's launches for a batched step and copies nothing to the host
-int pool_fed_begin(ifa_model *m, int k, int n_sel, const int *rows_sel, const int *adj_slots, const char *who)
+// after the step: copies the staged block out if the step succeeded and every wanted row was served
+static int pool_finish(ifa_model *m, const PoolCall &c, int step_rc, int *ids_host, unsigned short *vals_host, int *counts_host, const char *who)
 {
-    AdjConsume consume{m};
-    m->pool_adj_next.assign(adj_slots, adj_slots + n_sel);
-    int rc = pool_arm(m, k, n_sel, rows_sel, who);
-    if (rc) return rc;
-    m->pool.lse = false;               // (no step of the call hands a log-sum-exp to anybody)
-    int *slot_pin = m->pool_idx.pin + pool_idx_rows(m), *slot_dev = m->pool_idx.dev + pool_idx_rows(m);
-    for (int j = 0; j < n_sel; j++) { m->pool_idx.pin[j] = rows_sel[j]; slot_pin[j] = std::max(adj_slots[j], 0); }
-    hipError_t e = hipMemcpyAsync(m->pool_idx.dev, m->pool_idx.pin, sizeof(int) * (size_t)n_sel, hipMemcpyHostToDevice, m->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(slot_dev, slot_pin, sizeof(int) * (size_t)n_sel, hipMemcpyHostToDevice, m->stream);
-    if (e != hipSuccess) { m->pool = ifa_model::PoolReq(); return ifa_fail(IFA_ERR_HIP, "%s: upload of the pooled rows failed: %s", who, hipGetErrorString(e)); }
-    return IFA_OK;
-}
-
-int pool_fed_enqueue(ifa_model *m, const half_t *logits)
-{
-    const ifa_model::PoolReq &R = m->pool;
-    if (R.adj.empty()) return pool_rows_launch(m, logits, m->pool_idx.dev, 0, R.n_sel, false);
-    int rc;
-    for (int ja = 0; ja < R.n_sel;) {      // runs of armed / raw rows, as in pool_enqueue
-        const bool armed = R.adj[(size_t)ja] >= 0;
-        int jb = ja + 1;
-        while (jb < R.n_sel && (R.adj[(size_t)jb] >= 0) == armed) jb++;
-        if ((rc = pool_rows_launch(m, logits, m->pool_idx.dev + ja, ja, jb, armed))) return rc;
-        ja = jb;
-    }
-    return IFA_OK;
-}
-
-void pool_fed_block(ifa_model *m, int **counts, int **ids, void **vals)
-{
-    *counts = (int *)m->pool_blk.dev.get();
-    *ids = *counts + m->pool.n_sel;
-    *vals = *ids + (size_t)m->pool.n_sel * m->pool.k;
-}
-
-void pool_fed_end(ifa_model *m) { m->pool = ifa_model::PoolReq(); }
-
-// after the step: disarms; copies the staged block out if the step succeeded and every wanted row was served
-static int pool_finish(ifa_model *m, int step_rc, int *ids_host, unsigned short *vals_host, int *counts_host, const char *who)
-{
-    const ifa_model::PoolReq R = m->pool;
-    m->pool = ifa_model::PoolReq();
+    const StepTail &t = c.t;
     if (step_rc) return step_rc;
-    if (R.done != R.n_sel) return ifa_fail(IFA_ERR_STATE, "%s: the step served %d of %d pools", who, R.done, R.n_sel);
-    const int *counts = (const int *)m->pool_blk.pin.get(), *ids = counts + (R.lse ? 2 : 1) * R.n_sel;
-    if (R.lse) m->pool_lse_last.assign((const float *)(counts + R.n_sel), (const float *)(counts + R.n_sel) + R.n_sel);
-    const uint16_t *vals = (const uint16_t *)(ids + (size_t)R.n_sel * R.k);
-    memcpy(counts_host, counts, sizeof(int) * (size_t)R.n_sel);
-    memcpy(ids_host, ids, sizeof(int) * (size_t)R.n_sel * R.k);
-    memcpy(vals_host, vals, sizeof(uint16_t) * (size_t)R.n_sel * R.k);
+    if (c.cur.done != t.n) return ifa_fail(IFA_ERR_STATE, "%s: the step served %d of %d pools", who, c.cur.done, t.n);
+    const PoolBlock B = pool_block(m->pool_blk.pin.get(), t.n, t.k, t.lse);
+    if (B.lse) m->pool_lse_last.assign(B.lse, B.lse + t.n);
+    memcpy(counts_host, B.counts, sizeof(int) * (size_t)t.n);
+    memcpy(ids_host, B.ids, sizeof(int) * (size_t)t.n * t.k);
+    memcpy(vals_host, B.vals, sizeof(uint16_t) * (size_t)t.n * t.k);
     return IFA_OK;
 }
 
@@ -261,7 +223,7 @@ int ifa_model_logit_state_reset(ifa_model *m, int kv_slot, const int *prompt_hos
 {
     const char *who = "ifa_model_logit_state_reset";
     IFA_REQUIRE(m && m->finalized, "%s: model not finalized", who);
-    int rc = logit_partitioned(m, who);
+    int rc = device_tail_refusals(m, who, false, false, "logit processors run on a single-device worker");
     if (rc) return rc;
     const size_t V = m->g[T_LM_HEAD].rows;
     IFA_REQUIRE(kv_slot >= 0 && (size_t)kv_slot < std::max<size_t>(m->slots.size(), 1), "%s: KV slot %d (the worker has %zu)", who, kv_slot, std::max<size_t>(m->slots.size(), 1));
@@ -305,7 +267,7 @@ int ifa_model_logit_state_add(ifa_model *m, int n, const int *kv_slots_host, con
 {
     const char *who = "ifa_model_logit_state_add";
     IFA_REQUIRE(m && m->finalized, "%s: model not finalized", who);
-    int rc = logit_partitioned(m, who);
+    int rc = device_tail_refusals(m, who, false, false, "logit processors run on a single-device worker");
     if (rc) return rc;
     IFA_REQUIRE(n >= 0 && n <= ifa_model::RING && (n == 0 || (kv_slots_host && tokens_host)), "%s: %d pairs (at most %d)", who, n, ifa_model::RING);
     if (n == 0) return IFA_OK;
@@ -335,7 +297,7 @@ int ifa_model_pool_adjust(ifa_model *m, int n_sel, const int *state_slots_host)
     const char *who = "ifa_model_pool_adjust";
     IFA_REQUIRE(m && m->finalized, "%s: model not finalized", who);
     m->pool_adj_next.clear();
-    int rc = logit_partitioned(m, who);
+    int rc = device_tail_refusals(m, who, false, false, "logit processors run on a single-device worker");
     if (rc) return rc;
     IFA_REQUIRE(n_sel >= 0 && n_sel <= ifa_model::RING && (n_sel == 0 || state_slots_host), "%s: n_sel %d", who, n_sel);
     for (int j = 0; j < n_sel; j++)
@@ -358,14 +320,15 @@ int ifa_model_pool_lse(ifa_model *m, float *lse_host, int cap, int *n_out)
 int ifa_model_decode_pool(ifa_model *m, int token, int pos, int k, int *next_token_host,
                           int *pool_ids_host, unsigned short *pool_vals_host, int *pool_count_host)
 {
-    AdjConsume consume{m};
-    IFA_REQUIRE(m && m->finalized, "ifa_model_decode_pool: model not finalized");
-    IFA_REQUIRE(pool_ids_host && pool_vals_host && pool_count_host, "ifa_model_decode_pool: null pointer");
-    int rc = pool_arm(m, k, 1, nullptr, "ifa_model_decode_pool");
+    const char *who = "ifa_model_decode_pool";
+    PoolCall c(m);
+    IFA_REQUIRE(m && m->finalized, "%s: model not finalized", who);
+    IFA_REQUIRE(pool_ids_host && pool_vals_host && pool_count_host, "%s: null pointer", who);
+    int rc = c.ready(m, k, 1, nullptr, who);
     if (rc) return rc;
     int next = -1;
-    rc = ifa_model_decode(m, token, pos, 1, &next, nullptr);
-    rc = pool_finish(m, rc, pool_ids_host, pool_vals_host, pool_count_host, "ifa_model_decode_pool");
+    rc = decode_impl(m, token, pos, 1, &next, nullptr, false, c.t, c.cur);
+    rc = pool_finish(m, c, rc, pool_ids_host, pool_vals_host, pool_count_host, who);
     if (!rc && next_token_host) *next_token_host = next;
     return rc;
 }
@@ -373,15 +336,16 @@ int ifa_model_decode_pool(ifa_model *m, int token, int pos, int k, int *next_tok
 int ifa_model_forward_pool(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, void *logits_out_dev, int k,
                            int *next_token_host, int *pool_ids_host, unsigned short *pool_vals_host, int *pool_count_host)
 {
-    AdjConsume consume{m};
-    IFA_REQUIRE(m && m->finalized, "ifa_model_forward_pool: model not finalized");
-    IFA_REQUIRE(tokens_host && n_tokens >= 1 && pool_ids_host && pool_vals_host && pool_count_host, "ifa_model_forward_pool: bad arguments");
-    int rc = pool_arm(m, k, 1, nullptr, "ifa_model_forward_pool");
+    const char *who = "ifa_model_forward_pool";
+    PoolCall c(m);
+    IFA_REQUIRE(m && m->finalized, "%s: model not finalized", who);
+    IFA_REQUIRE(tokens_host && n_tokens >= 1 && pool_ids_host && pool_vals_host && pool_count_host, "%s: bad arguments", who);
+    int rc = c.ready(m, k, 1, nullptr, who);
     if (rc) return rc;
     int next = -1;
-    rc = ifa_model_forward(m, tokens_host, n_tokens, prefix_len, logits_out_dev, &next);
+    rc = forward_impl(m, tokens_host, n_tokens, prefix_len, logits_out_dev, &next, c.t, c.cur);
     // (option exact_order feeds a prompt row by row: every row's step stages its pool, the last one's is what remains)
-    rc = pool_finish(m, rc, pool_ids_host, pool_vals_host, pool_count_host, "ifa_model_forward_pool");
+    rc = pool_finish(m, c, rc, pool_ids_host, pool_vals_host, pool_count_host, who);
     if (!rc && next_token_host) *next_token_host = next;
     return rc;
 }
@@ -390,19 +354,20 @@ int ifa_model_decode_batch_pool(ifa_model *m, int n, const int *tokens_host, con
                                 int *next_tokens_host, int k, const int *rows_sel_host, int n_sel,
                                 int *pool_ids_host, unsigned short *pool_vals_host, int *pool_counts_host)
 {
-    AdjConsume consume{m};
-    IFA_REQUIRE(m && m->finalized, "ifa_model_decode_batch_pool: model not finalized");
-    IFA_REQUIRE(n >= 1 && n_sel >= 0 && n_sel <= n, "ifa_model_decode_batch_pool: n %d n_sel %d", n, n_sel);
-    if (n_sel == 0) { m->pool_adj_next.clear(); return ifa_model_decode_batch(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, nullptr); }
-    IFA_REQUIRE(rows_sel_host && pool_ids_host && pool_vals_host && pool_counts_host, "ifa_model_decode_batch_pool: null pointer");
+    const char *who = "ifa_model_decode_batch_pool";
+    PoolCall c(m);
+    IFA_REQUIRE(m && m->finalized, "%s: model not finalized", who);
+    IFA_REQUIRE(n >= 1 && n_sel >= 0 && n_sel <= n, "%s: n %d n_sel %d", who, n, n_sel);
+    if (n_sel == 0) return ifa_model_decode_batch(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, nullptr);
+    IFA_REQUIRE(rows_sel_host && pool_ids_host && pool_vals_host && pool_counts_host, "%s: null pointer", who);
     for (int j = 0; j < n_sel; j++)
         IFA_REQUIRE(rows_sel_host[j] >= 0 && rows_sel_host[j] < n && (j == 0 || rows_sel_host[j] > rows_sel_host[j - 1]),
-                    "ifa_model_decode_batch_pool: rows_sel must be strictly ascending indices below n = %d", n);
-    if (m->opt_exact_order) return ifa_fail(IFA_ERR_STATE, "ifa_model_decode_batch_pool: option exact_order steps the rows one by one; take ifa_model_decode_pool per query");
-    int rc = pool_arm(m, k, n_sel, rows_sel_host, "ifa_model_decode_batch_pool");
+                    "%s: rows_sel must be strictly ascending indices below n = %d", who, n);
+    if (m->opt_exact_order) return ifa_fail(IFA_ERR_STATE, "%s: option exact_order steps the rows one by one; take ifa_model_decode_pool per query", who);
+    int rc = c.ready(m, k, n_sel, rows_sel_host, who);
     if (rc) return rc;
-    rc = ifa_model_decode_batch(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, nullptr);
-    return pool_finish(m, rc, pool_ids_host, pool_vals_host, pool_counts_host, "ifa_model_decode_batch_pool");
+    rc = decode_batch_impl(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, nullptr, c.t, c.cur);
+    return pool_finish(m, c, rc, pool_ids_host, pool_vals_host, pool_counts_host, who);
 }
 
 } // extern "C"

@@ -18,6 +18,7 @@
 // size over freed memory.  Captured steps hold buffer addresses: whoever moves a buffer calls drop_graphs().
 #pragma once
 #include <chrono>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -38,6 +39,7 @@
 #include "ifa_decode_chain.h"
 #include "ifa_prompt_route.h"
 #include "ifa_moe_plan.h"
+#include "ifa_pool_rows_plan.h"
 
 using namespace ifa;
 
@@ -95,6 +97,69 @@ struct Scratch {
 };
 
 
+// ---- Step tails: what a step does behind its logits and in front of its one synchronisation ("Step tails").  The entry
+// point builds a StepTail on its stack and hands it down through decode_impl / forward_ops / forward_exact / forward_batch /
+// enqueue_fused_step; each of them calls tail_enqueue() at one place.  Nothing of a tail lives in the model: what a call of several
+// steps has served so far is the entry point's TailCursor.
+struct SampledCall { const ifa_sample_params *p = nullptr; unsigned long long *rng = nullptr; int state_slot = -1; };
+enum TailKind {
+    TAIL_NONE = 0,         // the greedy id only
+    TAIL_POOL,             // candidate pools of the wanted rows (+ their log-sum-exp), one copy of the block into pinned staging
+    TAIL_SCORE,            // log-sum-exp + target logit of every row of a prompt; behind the last row one copy into pinned staging
+    TAIL_DRAFT_VERIFY,     // the n rows of a draft step: [processors ->] pools -> the chained draws (k_sample_verify) -> one copy
+    TAIL_SAMPLED,          // INSIDE the fused step, captured with it: lm_head -> [processors ->] pool -> draw + state advance
+    TAIL_FED               // a batched step of a device-fed call: only enqueues -- no copy back, no synchronisation; its caller feeds
+};
+struct StepTail {
+    TailKind kind = TAIL_NONE;
+    int k = 0;                             // POOL / DRAFT_VERIFY / SAMPLED: pool length
+    int n = 0;                             // POOL: pooled rows (1 for a single-query step); SCORE: rows of the prompt (targets on the device)
+    const int *rows_sel = nullptr;         // POOL, batched step: ascending row indices (host); null: the step's last row
+    bool lse = false;                      // POOL: the rows' log-sum-exp ride in the block (option pool_lse)
+    const int *adj = nullptr;              // POOL: logit processors, [n] state slot of pooled row j, -1 raw (the entry point's array); null: none
+    bool armed = false;                    // DRAFT_VERIFY / SAMPLED: the logit processors of the call's state slot run first
+    const SampledCall *sampled = nullptr;  // SAMPLED: what the call writes into samp_blk
+    bool fed_first = false;                // FED: the call's first step (its tables go up in front of the replay)
+};
+struct TailCursor {
+    int done = 0;                          // POOL: pooled rows whose launches are enqueued; SCORE: rows
+    int chunk0 = 0; bool last_chunk = true;      // a batched step taken as several steps: first row of this one / it is the last
+};
+
+// the result block of the pool steps: counts [n_sel] | (with_lse: lse [n_sel] |) ids [n_sel][k] | F16 bits [n_sel][k]
+struct PoolBlock { int *counts; float *lse; int *ids; uint16_t *vals; size_t bytes; };
+static inline PoolBlock pool_block(void *base, int n_sel, int k, bool with_lse)
+{
+    PoolBlock B;
+    B.counts = (int *)base;
+    B.lse = with_lse ? (float *)(B.counts + n_sel) : nullptr;
+    B.ids = B.counts + (with_lse ? 2 : 1) * n_sel;
+    B.vals = (uint16_t *)(B.ids + (size_t)n_sel * k);
+    B.bytes = (size_t)n_sel * (with_lse ? 8 : 4) + (size_t)n_sel * (size_t)k * 6;
+    return B;
+}
+
+// The call blocks in device memory (+ pinned twin): what differs from call to call and is no kernel argument of a captured launch.
+// Sampled decode: all of it goes up in front of the first step, [rng, end) comes back behind the last.
+struct SampBlk { ifa_sample_params p; unsigned long long rng; int slot, err, token, index, pad[4]; };
+static_assert(offsetof(SampBlk, rng) % 8 == 0 && offsetof(SampBlk, slot) == offsetof(SampBlk, rng) + 8, "SampBlk: the generator word is aligned, what comes back is contiguous");
+// Sampled draft step: all of it goes up, [rng, back_end) comes back.
+struct DraftBlk { ifa_sample_params p; int slot, pad0, draft[8]; unsigned long long rng; int n_out, err, tokens[8], back_end[4]; };
+static_assert(offsetof(DraftBlk, rng) % 8 == 0 && offsetof(DraftBlk, n_out) == offsetof(DraftBlk, rng) + 8 && offsetof(DraftBlk, back_end) == offsetof(DraftBlk, tokens) + 32,
+              "DraftBlk: the generator word is aligned, what comes back is contiguous");
+// Device-fed batched steps: [rows, ring) and [params, end) go up (the ring is written by the device); [rows, ring + n_steps * n) comes back.
+struct BatchStepsBlk {
+    ifa_batch_feed_row rows[IFA_BATCH_ROWS_MAX];
+    int step, err, draw_err, pad;
+    int ring[IFA_BATCH_STEPS_MAX * IFA_BATCH_ROWS_MAX];
+    ifa_sample_params params[IFA_BATCH_ROWS_MAX];
+    unsigned long long rng[IFA_BATCH_ROWS_MAX];
+    int pool_len[IFA_BATCH_ROWS_MAX], drawn[IFA_BATCH_ROWS_MAX], index[IFA_BATCH_ROWS_MAX], pair_slot[IFA_BATCH_ROWS_MAX], pair_tok[IFA_BATCH_ROWS_MAX];
+};
+static_assert(offsetof(BatchStepsBlk, rng) % 8 == 0 && offsetof(BatchStepsBlk, ring) == offsetof(BatchStepsBlk, step) + 16 && sizeof(ifa_batch_feed_row) % 8 == 0
+              && offsetof(BatchStepsBlk, params) == offsetof(BatchStepsBlk, ring) + sizeof(int) * IFA_BATCH_STEPS_MAX * IFA_BATCH_ROWS_MAX,
+              "BatchStepsBlk: the 8-byte words are aligned, what comes back is contiguous");
+
 } // namespace ifae
 using namespace ifae;
 
@@ -137,7 +202,7 @@ struct ifa_model : Scratch {
     // advanced on the device (csrc/ifa_batch_feed.hip).  bs_blk: the call's per-row feed state, parameters, generator words, token
     // ring and error word in device memory (+ pinned twin), written by the call like samp_blk.
     std::map<int, hipGraphExec_t> fed_graphs;
-    DevPin<int> bs_blk;
+    DevPin<BatchStepsBlk> bs_blk;
     // long-context decode attention (keys split over workgroups): workspace, switch and the context it starts at
     DecAttnSplitWs attn_ws = {nullptr, nullptr, nullptr, 8};      // (what the kernels take: filled from the three owners below; nsplits per launch from the route)
     DevBuf<half_t> attn_ws_S; DevBuf<float> attn_ws_lmax, attn_ws_opart;
@@ -218,25 +283,15 @@ struct ifa_model : Scratch {
     int opt_prefill_res_mid = 2048;   // prefill_mid_max + 1 .. this many tokens: wo / w2 still through k_gemm_mid, the other products through the large tiles (0: never)
     int opt_rows_kparts = 1, opt_gemm_splitk = 1;   // 0: never the launches whose workgroups wait for partner workgroups (K parts of the 9..32-row GEMM, split-K halves of the large-tile GEMM)
     int opt_debug_mo_alloc_fail = 0;           // tests: ensure_mo_build fails like an exhausted allocator after its first copy
-    // Steps that end in a candidate pool (ifa_model_decode_pool / _decode_batch_pool / _forward_pool, ifa_engine_pool.hip): the entry
-    // point arms `pool`, the step calls pool_enqueue() on its logits in front of its one synchronisation (never under capture), the
-    // entry point reads the pinned block afterwards.  Result block: counts [n_sel] | ids [n_sel][k] | F16 bits [n_sel][k].
-    struct PoolReq {
-        int k = 0;                             // > 0: armed
-        int n_sel = 0;                         // rows wanted (1 for a single-query step)
-        const int *rows_sel = nullptr;         // batched step: ascending row indices (host); null: the step's one row
-        int chunk0 = 0; bool last_chunk = true;      // batched step taken as several steps: first row / last step of this one
-        int done = 0;                          // rows whose pool has been enqueued
-        bool lse = false;                      // option pool_lse at arming: the rows' log-sum-exp ride in the block
-        std::vector<int> adj;                  // logit processors (ifa_model_pool_adjust): [n_sel] state slot of pooled row j, -1 raw; empty: none
-    } pool;
+    // Memory of the step tails (StepTail above; the tails themselves live on the entry points' stacks).
+    // Candidate pools (ifa_engine_pool.hip): the result block (PoolBlock), device / pinned.
     DevBuf<unsigned> pool_excl;                // device bitmask of ids the pool never offers (null: none)
     DevPin<void> pool_blk;                     // result block, device / pinned
     DevPin<int> pool_idx;                      // row indices [cap / 2] | state slots of armed rows [cap / 2] (logit processors)
     // Logit processors (ifa_logit_adjust.hip): per KV slot the u32 state row, the f32 bias row and {rep, freq, pres}, allocated for
     // la_slots slots on the first ifa_model_logit_state_reset (regrown, contents kept, when ifa_model_kv_slots has added slots).
-    // pool_adj_next: what ifa_model_pool_adjust armed for the next pool step (moved into pool.adj by pool_arm).  la_adj: the adjusted
-    // rows of the last armed step, [rows][vocab].  la_ring: LA_RING staging blocks of 2 * RING ints (slots | tokens)
+    // pool_adj_next: what ifa_model_pool_adjust armed for the next pool call (moved into that call's StepTail at entry, consumed on every
+    // way out).  la_adj: the adjusted rows of the last armed step, [rows][vocab] (la_adj_reserve).  la_ring: LA_RING staging blocks of 2 * RING ints (slots | tokens)
     // for ifa_model_logit_state_add, block i guarded by la_ev[i]; reset's prompt / bias staging is la_reset.
     static constexpr int LA_RING = 8;
     DevBuf<unsigned> la_state; DevBuf<float> la_bias, la_params; size_t la_slots = 0;
@@ -249,12 +304,7 @@ struct ifa_model : Scratch {
     int opt_pool_lse = 0;
     std::vector<float> pool_lse_last;
     DevBuf<float> lse_part;                    // device: (max, sum) pairs of the rows a launch splits over workgroups (LSE_PART_FLOATS)
-    // Scoring prompt (ifa_model_forward_score, ifa_engine_score.hip): armed like `pool`; the prompt runs its lm_head over all rows
-    // and every route calls score_enqueue() on the rows it has just written, in front of its synchronisation.
-    struct ScoreReq {
-        int n = 0;                             // > 0: armed, rows wanted in all
-        int done = 0;                          // rows whose launch has been enqueued
-    } score;
+    // Scoring prompt (ifa_model_forward_score, ifa_engine_score.hip): the targets and the results of its rows
     DevPin<int> score_tgt;                     // [cap] target ids
     DevPin<float> score_out;                   // lse [cap] | target logit [cap]
     // Slot-to-slot copy of cache rows (ifa_model_kv_copy, ifa_kv_copy.hip): the K and V buffers of EVERY slot as one device table
@@ -267,18 +317,15 @@ struct ifa_model : Scratch {
     std::vector<DevPin<void *>> kvc_retired;   // replaced tables
     DevBuf<float> kvs_rot;                     // context shift (ifa_model_kv_shift, ifa_kv_shift.hip): [head_dim / 2] (cos, sin) of the last call's rotation
     // Sampled decode (ifa_model_decode_sampled, ifa_engine_sampled.hip).  samp_blk: the call's parameters, generator state, state
-    // slot and error word in device memory (+ pinned twin).  samp_k / samp_armed: pool length and "logit processors armed" of the
-    // current call, baked into the launches of the step it captures.  samp_graphs: the captured sampled step per
-    // (KV slot << 10 | k << 1 | armed) with the buffer addresses it names; the greedy step's graphs are not among them.
+    // slot and error word in device memory (+ pinned twin).  samp_graphs: the captured sampled step per
+    // (KV slot << 10 | k << 1 | armed) -- what the tail bakes into its launches -- with the buffer addresses it names; the greedy
+    // step's graphs are not among them.
     struct SampGraph { hipGraphExec_t exec = nullptr; const void *ptrs[8] = {}; };
     std::map<int, SampGraph> samp_graphs;
-    DevPin<int> samp_blk;
-    int samp_k = 0; bool samp_armed = false;
-    // Sampled draft step (ifa_model_decode_draft_sampled, ifa_engine_draft_sampled.hip).  dsv.k > 0: armed -- the draft step in flight
-    // ends in draft_sampled_enqueue() in place of pool_enqueue()'s pool, in front of its one synchronisation.  dsv_blk: the call's
-    // parameters, state slot, draft tokens, generator state and results in device memory (+ pinned twin).
-    struct DraftSampReq { int k = 0; bool armed = false; } dsv;
-    DevPin<int> dsv_blk;
+    DevPin<SampBlk> samp_blk;
+    // Sampled draft step (ifa_model_decode_draft_sampled, ifa_engine_draft_sampled.hip): the call's parameters, state slot, draft
+    // tokens, generator state and results in device memory (+ pinned twin).
+    DevPin<DraftBlk> draft_blk;
     static constexpr int RING = 1024;
 };
 
@@ -380,6 +427,35 @@ static int attn_dispatch(int head_dim, bool q8, F &&f)
 
 // ---- ifa_engine.hip
 void drop_graphs(ifa_model *m);
+// One body of launches as an instantiated graph: synchronise, begin capture, run body, end capture, instantiate.  The hipGraph_t is
+// destroyed on every failing path -- and on success too unless `keep` is given, whose old graph it then replaces.
+template <class F>
+static int capture_graph(ifa_model *m, const char *what, hipGraphExec_t *exec, hipGraph_t *keep, F &&body)
+{
+    hipStream_t s = m->stream;
+    IFA_HIP_CHECK(hipStreamSynchronize(s));
+    IFA_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = body();
+    hipGraph_t gph = nullptr;
+    const hipError_t e = hipStreamEndCapture(s, &gph);
+    if (rc || e != hipSuccess) {
+        if (gph) (void)hipGraphDestroy(gph);
+        return rc ? rc : ifa_fail(IFA_ERR_HIP, "hipStreamEndCapture (%s): %s", what, hipGetErrorString(e));
+    }
+    hipGraphExec_t ex = nullptr;
+    const hipError_t ei = hipGraphInstantiate(&ex, gph, nullptr, nullptr, 0);
+    if (ei != hipSuccess || !keep) (void)hipGraphDestroy(gph);
+    if (ei != hipSuccess) return ifa_fail(IFA_ERR_HIP, "hipGraphInstantiate (%s): %s", what, hipGetErrorString(ei));
+    if (keep) { if (*keep) (void)hipGraphDestroy(*keep); *keep = gph; }
+    *exec = ex;
+    return IFA_OK;
+}
+// what every entry point with a tail on the device refuses: a partitioned worker (its vocabulary is sharded), a pipeline stage
+// without lm_head (needs_embd: or embeddings) and -- fused_only: the tail hangs on the fused, captured step -- options exact_order / perf_stat.
+// device_tail_refusal: the reason or null, nothing recorded; device_tail_refusals: IFA_ERR_STATE with "who: reason; hint" (hint: what
+// the caller can do instead)
+const char *device_tail_refusal(const ifa_model *m, bool needs_embd, bool fused_only);
+int device_tail_refusals(const ifa_model *m, const char *who, bool needs_embd, bool fused_only, const char *hint);
 // perf_stat spans (ifa_engine.hip): no-ops unless the option is on.  PerfSpan brackets a phase on the model's stream.
 int perf_begin(ifa_model *m, int key);
 void perf_end(ifa_model *m, int idx);
@@ -423,16 +499,16 @@ int step_tail_ready(ifa_model *m);
 int launch_lm_tail(ifa_model *m, const half_t *x);
 int launch_gather(ifa_model *m);
 int launch_lm(ifa_model *m, const half_t *x, half_t *logits_out = nullptr);
-// how a fused step ends: the greedy argmax (k_dec_lmhead_tail, or lm_head + k_dec_argmax_advance), or the draw (sampled_tail_enqueue)
-enum { STEP_TAIL_GREEDY = 0, STEP_TAIL_SAMPLED = 1 };
-struct SampledCall { const ifa_sample_params *p = nullptr; unsigned long long *rng = nullptr; int state_slot = -1; };
-int enqueue_fused_step(ifa_model *m, int tail = STEP_TAIL_GREEDY);
+// a fused step ends in the greedy argmax (k_dec_lmhead_tail, or lm_head + k_dec_argmax_advance) unless its tail is TAIL_SAMPLED: then in
+// the draw (sampled_tail_enqueue)
+int enqueue_fused_step(ifa_model *m, const StepTail &t);
+// (a TAIL_SAMPLED call comes from ifa_model_decode_sampled, which has checked that the fused graph route is open)
 int decode_impl(ifa_model *m, int first_token, int start_pos, int n_steps, int *out_tokens_host, float *elapsed_ms, bool prepare_only,
-                const SampledCall *sc = nullptr);
+                const StepTail &t, TailCursor &cur);
 // ---- ifa_engine_sampled.hip
-int sampled_prepare(ifa_model *m, const SampledCall &sc);
-int sampled_tail_enqueue(ifa_model *m, const half_t *x);
-int sampled_graph(ifa_model *m, hipGraphExec_t *exec_out);
+int sampled_prepare(ifa_model *m, const StepTail &t);
+int sampled_tail_enqueue(ifa_model *m, const StepTail &t, const half_t *x);
+int sampled_graph(ifa_model *m, const StepTail &t, hipGraphExec_t *exec_out);
 void sampled_drop_graphs(ifa_model *m);
 int sampled_begin(ifa_model *m, const SampledCall &sc);
 int sampled_copy_back(ifa_model *m);
@@ -445,37 +521,46 @@ int ffn_dense(ifa_model *m, const half_t *x, int T, const Tensor &w1, const Tens
                      const Tensor &w2, const Tensor &b2, half_t *out, int perf_base = 0);
 int layer_tail_ops(ifa_model *m, int l, int T, half_t *&x, const half_t *attn_in, bool &xn_ready);
 int prompt_route_ready(ifa_model *m, int T, int prefix_len, bool entry, PromptRoute &R);
-int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, bool no_head = false,
-                const PromptRoute *planned = nullptr);
+int forward_ops(ifa_model *m, const int *tokens_host, int T, int prefix_len, void *logits_out, int *next_token, const StepTail &t, TailCursor &cur,
+                bool no_head = false, const PromptRoute *planned = nullptr);
+// ifa_model_forward behind its argument checks: one pass, the two passes of a 34..48-token prompt, or exact_order's row-by-row steps
+int forward_impl(ifa_model *m, const int *tokens_host, int n_tokens, int prefix_len, void *logits_out_dev, int *next_token_host,
+                 const StepTail &t, TailCursor &cur);
 // ifa_decode_draft_kv.hip: RoPE + cache rows of the n rows of a draft step (rows_l: the layer's AttnRowH[n]) in one launch
 int draft_kv_store_launch(ifa_model *m, int n, const half_t *k, const half_t *v, int stride, const void *rows_l);
-// fed (ifa_model_decode_batch_steps; fused + captured routes only): FED_FIRST uploads the tables of the call's first step in front of
-// the replay, FED_NEXT replays on the tables as the device left them; both only enqueue -- no pool, no copy back, no synchronisation
-enum { FED_OFF = 0, FED_FIRST = 1, FED_NEXT = 2 };
 int batch_route_of_call(ifa_model *m, int n, BatchRoute &R);
+// TAIL_FED (ifa_model_decode_batch_steps; fused + captured routes only): the call's first step uploads its tables in front of the replay,
+// a later one replays on the tables as the device left them; both only enqueue.  draft: the rows share a slot (ifa_model_decode_draft)
 int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_host, const int *slot_host, int *next_tokens,
-                         void *logits_out, bool draft = false, int fed = FED_OFF);      // draft: the rows share a slot (ifa_model_decode_draft)
+                  void *logits_out, const StepTail &t, TailCursor &cur, bool draft = false);
+// ifa_model_decode_batch behind its argument checks: one step, balanced chunks, or exact_order's rows one by one
+int decode_batch_impl(ifa_model *m, int n, const int *tokens_host, const int *positions_host, const int *kv_slots_host, int *next_tokens_host,
+                      void *logits_out_dev, const StepTail &t, TailCursor &cur);
 // ---- ifa_engine_pool.hip
-// armed (m->pool.k > 0): ifa_topk_pool over the wanted rows of `logits` ([n_rows][vocab], this step's rows) + the copy of the result
-// block, on the model's stream; a no-op otherwise.  Called by every step in front of its synchronisation.
-int pool_enqueue(ifa_model *m, const half_t *logits, int n_rows);
+// What the step's tail enqueues behind `logits` ([n_rows][vocab], this step's rows) on the model's stream: called by every step at
+// one place, in front of its synchronisation, never under capture.  TAIL_NONE / _SAMPLED / _FED: nothing.
+int tail_enqueue(ifa_model *m, const StepTail &t, TailCursor &cur, const half_t *logits, int n_rows);
+// "[logit processors ->] pool [-> log-sum-exp]" of the pooled rows [ja, jb) of block B (k entries a row).  idx: device row indices
+// into `logits` for row ja on, null: rows [0, jb - ja).  slots: device state slots for row ja on -- the rows pass through
+// ifa_logit_adjust_rows into la_adj rows [ja, jb) and are pooled from there -- null: raw.  The one place the pool launches.
+int pool_rows_launch(ifa_model *m, const PoolBlock &B, int k, const half_t *logits, const int *idx, const int *slots, int ja, int jb);
 // device / pinned staging for n_sel rows of k entries (grown on demand, outside any capture)
 int pool_reserve(ifa_model *m, int n_sel, int k);
-// device-fed batched steps: the request armed once for a call of several steps (adj_slots [n_sel]: state slot of pooled row j, -1 raw),
-// row indices and state slots uploaded once; pool_fed_enqueue: one step's launches of pool_enqueue's batched branch on `logits`,
-// nothing copied to the host; pool_fed_block: where those launches leave counts [n_sel], ids and F16 bits [n_sel][k]
-int pool_fed_begin(ifa_model *m, int k, int n_sel, const int *rows_sel, const int *adj_slots, const char *who);
-int pool_fed_enqueue(ifa_model *m, const half_t *logits);
-void pool_fed_block(ifa_model *m, int **counts, int **ids, void **vals);
-void pool_fed_end(ifa_model *m);
-// ifa_engine_draft_sampled.hip: the tail of a sampled draft step on the n rows of `logits` (m->dsv armed), enqueue-only
-int draft_sampled_enqueue(ifa_model *m, const half_t *logits, int n_rows);
+// la_adj for `rows` adjusted rows (at least 8; never shrinks; synchronises before it reallocates)
+int la_adj_reserve(ifa_model *m, size_t rows, const char *who);
+// checks and reservations of a call that pools n_sel rows with k entries; adj: what ifa_model_pool_adjust armed for it (emptied when
+// no row is armed)
+int pool_ready(ifa_model *m, int k, int n_sel, std::vector<int> &adj, const char *who);
+// where the block's second half starts: row indices [cap / 2] | state slots of armed rows [cap / 2]
+static inline size_t pool_idx_rows(const ifa_model *m) { return m->pool_idx.cap() / 2; }
+// ifa_engine_draft_sampled.hip: TAIL_DRAFT_VERIFY on the n rows of `logits`, enqueue-only
+int draft_sampled_enqueue(ifa_model *m, const StepTail &t, const half_t *logits, int n_rows);
 // ---- ifa_engine_score.hip
 static constexpr size_t LSE_PART_FLOATS = 256;      // rows * splits <= 128 pairs whatever the row count (ifa_logprob.hip, lse_splits)
 int lse_part_reserve(ifa_model *m);
-// armed (m->score.n > 0): the row log-sum-exp + target gather over `logits` ([n_rows][vocab], the next n_rows rows of the prompt); after
-// the last row the copy of the 2 * n floats into pinned staging.  A no-op otherwise.
-int score_enqueue(ifa_model *m, const half_t *logits, int n_rows);
+// TAIL_SCORE: the row log-sum-exp + target gather over `logits` ([n_rows][vocab], the next n_rows rows of the prompt); after the last
+// row the copy of the 2 * n floats into pinned staging
+int score_enqueue(ifa_model *m, const StepTail &t, TailCursor &cur, const half_t *logits, int n_rows);
 // ---- ifa_engine_moe.hip
 int launch_moe_router(ifa_model *m, int l);
 // Mixture of experts (ProcessGpuLayer_Moe, inference_worker.cc:1924-2146): router GEMV -> softmax -> D2H ->
@@ -490,7 +575,7 @@ int moe_layer(ifa_model *m, Layer &L, const MoePlan &P, const half_t *ff_n, int 
 int ensure_side_stream(ifa_model *m);
 // ---- ifa_engine_exact.hip
 bool exact_supported(const ifa_model *m, std::string *why);
-int forward_exact(ifa_model *m, int token, int pos, void *logits_out, int *next_token);
+int forward_exact(ifa_model *m, int token, int pos, void *logits_out, int *next_token, const StepTail &t, TailCursor &cur);
 // ---- ifa_engine_tp.hip
 int tp_argmax_scratch(ifa_model *m, size_t n_rows);
 int tp_pick_rows(ifa_model *m, const ifa_tp_topology &t, const half_t *shard, size_t row_stride, int shard_rows, int n_rows);

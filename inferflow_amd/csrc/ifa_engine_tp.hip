@@ -408,7 +408,8 @@ int ifa_model_tp_prefill(ifa_model *m, const ifa_tp_topology *topo, const int *t
         // wo and w2, [T][dim] hand-over between layer groups) -- the reference's MatrixMultiplication branch for T > 1
         // (inference_worker.cc:2364-2432) with its merge of token_num x dim values (:2148-2195)
         m->topo = topo;
-        rc = forward_ops(m, tokens_host, n_tokens, start_pos, logits_shard_out_dev, next_token_host);
+        StepTail none; TailCursor cur;      // (the group's own tail: the distributed argmax)
+        rc = forward_ops(m, tokens_host, n_tokens, start_pos, logits_shard_out_dev, next_token_host, none, cur);
         m->topo = nullptr;
         if (rc == IFA_OK) { (void)hipStreamSynchronize(m->stream); rc = tp_oneshot_status(m, *topo, "ifa_model_tp_prefill"); }
         return rc;
@@ -436,7 +437,8 @@ int ifa_model_tp_decode_batch(ifa_model *m, const ifa_tp_topology *topo, int n, 
     int rc = tp_check(m, topo, "ifa_model_tp_decode_batch");
     if (rc) return rc;
     m->topo = topo;
-    rc = forward_batch(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, logits_shard_out_dev);
+    StepTail none; TailCursor cur;
+    rc = forward_batch(m, n, tokens_host, positions_host, kv_slots_host, next_tokens_host, logits_shard_out_dev, none, cur);
     m->topo = nullptr;
     if (rc == IFA_OK) { (void)hipStreamSynchronize(m->stream); rc = tp_oneshot_status(m, *topo, "ifa_model_tp_decode_batch"); }
     return rc;
