@@ -205,6 +205,17 @@ SIGNATURES = {
 }
 
 
+# engine-internal launches of csrc/ifa_ops.hip (declared in csrc/ifa_engine_state.h, exported but not part of the header):
+# bound here so that the op-level tests call them with checked argument types
+INTERNAL_SIGNATURES = {
+    "ifa_rope_qk_store": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _sz, _vp]),
+    "ifa_rope_rows": (_i, [_vp, _i, _i, _i, _vp, _f, _i, _f, _vp]),
+    "ifa_add_layernorm": (_i, [_i, _vp, _vp, _sz, _sz, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+    "ifa_activation_mul": (_i, [_i, _vp, _vp, _sz, _vp, _vp]),
+    "ifa_argmax_rows": (_i, [_vp, _sz, _sz, _sz, _vp, _vp, _vp]),
+}
+
+
 # include/inferflow_engine.h (the C++ InferenceEngine facade)
 _ip = C.POINTER(C.c_int)
 ENGINE_SIGNATURES = {
@@ -301,7 +312,7 @@ class ModelConfig(C.Structure):
 
 def _declare(L):
     missing = []
-    for name, (res, args) in list(SIGNATURES.items()) + list(ENGINE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()) + list(ENGINE_SIGNATURES.items()):
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -27,11 +27,15 @@ __global__ void __launch_bounds__(128) k_layernorm(const half_t *__restrict__ x,
     const half_t *src = x + (size_t)blockIdx.x * cols;
     half_t *dst = y + (size_t)blockIdx.x * cols;
     bool staged = false;
+    // the 16-byte paths need whole chunks AND 16-byte-aligned bases (row r starts cols * 2 bytes further: aligned with its base);
+    // anything else takes the element-wise paths, which round the same expressions
+    const bool vec = (cols & 7) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w) |
+                                          reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(add) | reinterpret_cast<uintptr_t>(sum_out)) & 15) == 0;
     if (add) {      // TensorOpr::Add in front of the norm, same launch: the half-rounded sum goes to sum_out and to LDS
         half_t *row = reinterpret_cast<half_t *>(smem_row);
         const half_t *ad = add + (size_t)blockIdx.x * cols;
         half_t *so = sum_out + (size_t)blockIdx.x * cols;
-        if ((cols & 7) == 0) {
+        if (vec) {
             typedef _Float16 h8 __attribute__((ext_vector_type(8)));
             for (int c = tid; c < cols / 8; c += 128) {
                 const h8 a8 = reinterpret_cast<const h8 *>(src)[c], b8 = reinterpret_cast<const h8 *>(ad)[c];
@@ -71,7 +75,7 @@ __global__ void __launch_bounds__(128) k_layernorm(const half_t *__restrict__ x,
         }
         __syncthreads();
         const float scale = rms_scale_of(rms_total(part, ngroups), cols, eps);
-        if ((cols & 7) == 0) {       // element-wise: 16-byte accesses, chunks interleaved over the threads
+        if (vec) {       // element-wise: 16-byte accesses, chunks interleaved over the threads
             typedef _Float16 h8 __attribute__((ext_vector_type(8)));
             for (int c = tid; c < cols / 8; c += 128) {
                 const h8 xv = reinterpret_cast<const h8 *>(src)[c];
@@ -101,7 +105,7 @@ __global__ void __launch_bounds__(128) k_layernorm(const half_t *__restrict__ x,
         // would otherwise walk global memory one 2-byte load at a time on a latency chain
         half_t *row = reinterpret_cast<half_t *>(smem_row);
         if (!staged) {
-            if ((cols & 7) == 0) {
+            if (vec) {
                 typedef uint32_t u4 __attribute__((ext_vector_type(4)));
                 for (int c = tid; c < cols / 8; c += 128) reinterpret_cast<u4 *>(row)[c] = reinterpret_cast<const u4 *>(src)[c];
             } else {
@@ -149,7 +153,7 @@ __global__ void __launch_bounds__(128) k_layernorm(const half_t *__restrict__ x,
         }
         __syncthreads();
         const float mean = stat[0], scale = stat[1];
-        if ((cols & 7) == 0) {       // element-wise: 8 contiguous elements per thread and step, 16-byte accesses
+        if (vec) {       // element-wise: 8 contiguous elements per thread and step, 16-byte accesses
             typedef _Float16 h8 __attribute__((ext_vector_type(8)));
             for (int c = tid; c < cols / 8; c += 128) {
                 const h8 xv = reinterpret_cast<const h8 *>(src)[c];
@@ -478,7 +482,7 @@ int ifa_add_layernorm(int kind, const void *a, const void *addend, size_t rows, 
     IFA_REQUIRE(b == nullptr || w != nullptr, "ifa_add_layernorm: bias without weight");
     if (rows == 0 || cols == 0) return IFA_OK;
     const size_t smem = (cols * 2 + 15) & ~(size_t)15;
-    IFA_REQUIRE(smem <= 64 * 1024, "ifa_add_layernorm: %zu columns", cols);
+    IFA_REQUIRE(smem <= 64 * 1024, "ifa_add_layernorm: %zu columns (the row is staged in LDS: limit 32768)", cols);
     if (kind == 0)
         k_layernorm<0><<<dim3((unsigned)rows), dim3(128), smem, ifa_s(stream)>>>((const half_t *)a, (int)cols, (const half_t *)w, (const half_t *)b, multi_base, eps,
                                                                                  (half_t *)y, (const half_t *)addend, (half_t *)sum_out);
@@ -497,6 +501,8 @@ int ifa_layernorm(int kind, const void *x, size_t rows, size_t cols, const void 
     IFA_REQUIRE(b == nullptr || w != nullptr, "ifa_layernorm: bias without weight");
     if (rows == 0 || cols == 0) return IFA_OK;
     IFA_REQUIRE(cols <= 65536, "ifa_layernorm: %zu columns (limit 65536)", cols);
+    // the std norm stages its row in LDS: 2 * cols bytes, 64 KiB at the most (ifa_add_layernorm's limit)
+    IFA_REQUIRE(kind == 0 || ((cols * 2 + 15) & ~(size_t)15) <= 64 * 1024, "ifa_layernorm: %zu columns (std norm stages the row in LDS: limit 32768)", cols);
     if (kind == 0)
         k_layernorm<0><<<dim3((unsigned)rows), dim3(128), 0, ifa_s(stream)>>>((const half_t *)x, (int)cols, (const half_t *)w, (const half_t *)b, multi_base, eps, (half_t *)y);
     else
@@ -542,7 +548,7 @@ int ifa_rope_qk_store(void *q, void *k, const void *v, int head_dim, int heads, 
     if (partial_rotary_factor <= 0) partial_rotary_factor = 1.0f;
     const int rope_cols = (int)(head_dim * partial_rotary_factor + 0.5f);
     const size_t smem = (size_t)head_dim * 4 + (size_t)kv_dim * 2;
-    if (smem > 64 * 1024 || (((uintptr_t)k | (uintptr_t)kcache_rows | (uintptr_t)vcache_rows | (uintptr_t)v) & 15) || (cache_row_elems % 8)) return IFA_ERR_STATE;
+    if (smem > 64 * 1024 || (((uintptr_t)q | (uintptr_t)k | (uintptr_t)kcache_rows | (uintptr_t)vcache_rows | (uintptr_t)v) & 15) || (cache_row_elems % 8)) return IFA_ERR_STATE;
     k_rope_qk_store<<<dim3((unsigned)tokens), dim3(256), smem, ifa_s(stream)>>>((half_t *)q, (half_t *)k, (const half_t *)v, head_dim, heads, kv_heads, pos0,
                                                                                theta, order, rope_cols, rope_cols, (half_t *)kcache_rows,
                                                                                (half_t *)vcache_rows, cache_row_elems);

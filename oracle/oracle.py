@@ -274,6 +274,14 @@ def rope(x, pos0, theta=10000.0, order=2, partial_rotary=1.0):
     return x16.view(np.float16)
 
 
+def alibi(scores, base_head=0, total_heads=None):
+    """scores: [heads][q_tokens][ctx] float16; returns the biased copy (orc_alibi)."""
+    s16 = _f16(scores).copy()
+    heads, qt, ctx = s16.shape
+    lib().orc_alibi(_p(s16), ctx, qt, heads, base_head, total_heads or heads)
+    return s16.view(np.float16)
+
+
 def softmax(s, prefix_len=-1, scale=1.0):
     """s: [cz][cy][cx] float16."""
     s16 = _f16(s).copy()
