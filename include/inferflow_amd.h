@@ -212,6 +212,18 @@ int ifa_attention_rows(const void *q_f16, const void *rows_dev, int kv_dtype, in
  * with 64 queries per workgroup, 4 two-pass with 128), queries per workgroup, grid x, grid y, dynamic LDS bytes, sg_nkp (row stride
  * of the workspace tiles, halfs), xcd_remap, then the workspace bytes as two ints (low half first). */
 int ifa_attention_plan(const int *facts, int n_facts, int *out, int n_out);
+/* head_dim 48 / 80 / 96 on the matrix cores: with on = 1 (default 0; < 0 only queries; returns the previous value) a call of
+ * ifa_attention with one of these head sizes and at least 4 queries runs k_attention_heads16 (csrc/ifa_attn_heads.hip) instead of the
+ * scalar kernel; every other call is unchanged, and so is ifa_attention_rows.  One workgroup per (64 queries, head), a wave per 16
+ * queries on 16 x 16 MFMA tiles; the wave's query block stays in registers, 32-key K / V blocks go through LDS in two buffers (Q8_B32T2
+ * dequantised while staged, the block scale taken by the absolute column of the cache row); two passes over the keys, no score tile,
+ * no workspace, enqueue-only.  Rounding points as the two-pass kernels above: scores half(alpha * q.k) (+ ALiBi), maximum and sum
+ * fp32, probabilities half(half(exp) / sum), fp32 accumulation, F16 output.
+ * ifa_attention_heads16_plan: what that call launches (csrc/ifa_attn_heads_plan.h).  Host-only, no GPU needed, no state -- it does not
+ * read the switch.  facts[10] as ifa_attention_plan; out[6]: error (0 ok; 1 .. 5 as ifa_attention_plan; 6 head_dim not 48 / 80 / 96,
+ * 7 fewer than 4 queries, 8 rows mode), queries per workgroup (64), grid x (query tiles), grid y (heads), dynamic LDS bytes, xcd_remap. */
+int ifa_attention_mfma_heads(int on);
+int ifa_attention_heads16_plan(const int *facts, int n_facts, int *out, int n_out);
 
 /* ---- greedy argmax over F16 logits (SampleTokens top-1) ------------------ */
 /* MoE routing of `tokens` softmaxed router rows [tokens][experts] on the device -- the per-row part of

@@ -18,6 +18,7 @@
 #include "ifa_device.h"
 #include "ifa_math.h"
 #include "ifa_attn_plan.h"
+#include "ifa_attn_heads_plan.h"
 
 namespace ifa {
 
@@ -891,6 +892,21 @@ extern "C" int ifa_attention_two_pass_min_keys(int min_keys)
     return prev;
 }
 
+// head_dim 48 / 80 / 96 on the matrix cores (k_attention_heads16, ifa_attn_heads.hip) instead of k_attention; opt-in
+static int g_attn_mfma_heads = 0;
+namespace ifa {
+int launch_attention_heads16(const AttnHeads16Plan &pl, const void *q, const void *kcache, const void *vcache, int kv_dtype, int n_ctx,
+                             int q_tokens, int prefix_len, int heads, int kv_heads, int head_dim, float kq_scale, int alibi,
+                             int alibi_base, int alibi_total, void *out, hipStream_t s);
+}
+
+extern "C" int ifa_attention_mfma_heads(int on)
+{
+    const int prev = g_attn_mfma_heads;
+    if (on >= 0) g_attn_mfma_heads = on ? 1 : 0;
+    return prev;
+}
+
 extern "C" int ifa_debug_attn_trace(unsigned long long *out8)
 {
     IFA_HIP_CHECK(hipMemcpyFromSymbol(out8, HIP_SYMBOL(ifa::g_attn_trace), 64));
@@ -958,6 +974,9 @@ extern "C" int ifa_attention(const void *q, const void *kcache, const void *vcac
     IFA_REQUIRE(kq_scale > 0, "ifa_attention: kq_scale must be > 0");
     const int total_heads = alibi_total_heads > 0 ? alibi_total_heads : heads;
     hipStream_t hs = ifa_s(stream);
+    if (g_attn_mfma_heads && attn_heads16_head(head_dim) && q_tokens >= H16_MIN_QUERIES)
+        return launch_attention_heads16(plan_attention_heads16(attn_facts(kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, 0)), q, kcache, vcache,
+                                        kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, kq_scale, alibi, alibi_base_head, total_heads, out, hs);
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
     const size_t smem = (size_t)pl.lds;
     switch (pl.kind) {

@@ -135,6 +135,7 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "lookup_ngram_min", config.lookup_ngram_min);
     if (!LookupConfigOk(config)) return false;
     cfg.GetItem(section, "lookup_sampled", config.lookup_sampled);
+    cfg.GetItem(section, "attention_mfma_heads", config.attention_mfma_heads);
     cfg.GetItem(section, "is_study_mode", config.debug.is_study_mode);
     cfg.GetItem(section, "show_tensors", config.debug.show_tensors);
     return true;

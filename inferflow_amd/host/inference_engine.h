@@ -130,6 +130,10 @@ struct InferenceConfig {
     // where device_sampler and lookup decoding both are (model_info "lookup_sampled"); off by default: GenerateLookup then refuses
     // such queries as before.
     bool lookup_sampled = false;
+    // extension: prompt attention on the matrix cores for models with 48-, 80- or 96-wide heads (Phi-2 / StableLM / Phi-3-mini geometries):
+    // Init sets ifa_attention_mfma_heads(1), and every prompt chunk of at least 4 tokens runs k_attention_heads16 instead of the scalar
+    // kernel.  The switch is process-wide; other head sizes are not affected.  Off by default.
+    bool attention_mfma_heads = false;
     // extension: context shift (host/context_shift.h; DESIGN.md "Context shift").  A query whose tokens reach max_context_len does not
     // end: the engine keeps its first context_shift_keep cache rows, drops the older half of the rows behind them and moves the rest
     // down on the device (ifa_model_kv_shift: K rows re-rotated to their new positions), then goes on.  An approximation by design
