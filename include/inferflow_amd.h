@@ -221,9 +221,16 @@ int ifa_attention_plan(const int *facts, int n_facts, int *out, int n_out);
  * fp32, probabilities half(half(exp) / sum), fp32 accumulation, F16 output.
  * ifa_attention_heads16_plan: what that call launches (csrc/ifa_attn_heads_plan.h).  Host-only, no GPU needed, no state -- it does not
  * read the switch.  facts[10] as ifa_attention_plan; out[6]: error (0 ok; 1 .. 5 as ifa_attention_plan; 6 head_dim not 48 / 80 / 96,
- * 7 fewer than 4 queries, 8 rows mode), queries per workgroup (64), grid x (query tiles), grid y (heads), dynamic LDS bytes, xcd_remap. */
+ * 7 fewer than 4 queries, 8 rows mode), queries per workgroup (64), grid x (query tiles), grid y (heads), dynamic LDS bytes, xcd_remap.
+ * The same switch covers head_dim 256 (Gemma): with on = 1 a call of ifa_attention with head_dim 256 and at least 4 queries runs the
+ * same kernel instantiated at 256 (8 x32 steps per score tile, 16 output tiles, 74 752 bytes of LDS), behind a plan of its own; passes
+ * and rounding points as above.  Decode at 256 is not affected (it runs op by op).
+ * ifa_attention_heads256_plan: what that call launches (csrc/ifa_attn_heads256_plan.h); host-only as the one above, the same facts[10]
+ * and out[6]: error (0 ok; 1 .. 5 as ifa_attention_plan; 6 head_dim not 256, 7 fewer than 4 queries, 8 rows mode), queries per
+ * workgroup (64), grid x (query tiles), grid y (heads), dynamic LDS bytes, xcd_remap. */
 int ifa_attention_mfma_heads(int on);
 int ifa_attention_heads16_plan(const int *facts, int n_facts, int *out, int n_out);
+int ifa_attention_heads256_plan(const int *facts, int n_facts, int *out, int n_out);
 
 /* ---- greedy argmax over F16 logits (SampleTokens top-1) ------------------ */
 /* MoE routing of `tokens` softmaxed router rows [tokens][experts] on the device -- the per-row part of

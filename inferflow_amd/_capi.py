@@ -72,6 +72,7 @@ SIGNATURES = {
     "ifa_attention_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_attention_mfma_heads": (_i, [_i]),
     "ifa_attention_heads16_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_attention_heads256_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_big_tiles": (_i, [_i]),
     "ifa_wait_grid_decision": (_i, [_i, _i, C.c_longlong]),
     "ifa_visible_cus_from_mask": (_i, [C.c_char_p, _i, _i]),

@@ -19,6 +19,7 @@
 #include "ifa_math.h"
 #include "ifa_attn_plan.h"
 #include "ifa_attn_heads_plan.h"
+#include "ifa_attn_heads256_plan.h"
 
 namespace ifa {
 
@@ -892,12 +893,16 @@ extern "C" int ifa_attention_two_pass_min_keys(int min_keys)
     return prev;
 }
 
-// head_dim 48 / 80 / 96 on the matrix cores (k_attention_heads16, ifa_attn_heads.hip) instead of k_attention; opt-in
+// head_dim 48 / 80 / 96, and 256 behind ifa_attn_heads256_plan.h, on the matrix cores (k_attention_heads16, ifa_attn_heads.hip) instead
+// of k_attention; opt-in
 static int g_attn_mfma_heads = 0;
 namespace ifa {
 int launch_attention_heads16(const AttnHeads16Plan &pl, const void *q, const void *kcache, const void *vcache, int kv_dtype, int n_ctx,
                              int q_tokens, int prefix_len, int heads, int kv_heads, int head_dim, float kq_scale, int alibi,
                              int alibi_base, int alibi_total, void *out, hipStream_t s);
+int launch_attention_heads256(const AttnHeads256Plan &pl, const void *q, const void *kcache, const void *vcache, int kv_dtype, int n_ctx,
+                              int q_tokens, int prefix_len, int heads, int kv_heads, float kq_scale, int alibi, int alibi_base,
+                              int alibi_total, void *out, hipStream_t s);
 }
 
 extern "C" int ifa_attention_mfma_heads(int on)
@@ -929,6 +934,17 @@ extern "C" int ifa_attention_plan(const int *facts, int n_facts, int *out, int n
     AttnFacts f;
     memcpy(&f, facts, sizeof(f));
     const AttnPlan r = plan_attention(f);
+    memcpy(out, &r, sizeof(r));
+    return IFA_OK;
+}
+
+// the launch plan of prompt attention at head_dim 256 (ifa_attn_heads256_plan.h) behind the C ABI, for tests: the pure function, no device is touched
+extern "C" int ifa_attention_heads256_plan(const int *facts, int n_facts, int *out, int n_out)
+{
+    IFA_REQUIRE(facts && out && n_facts == ATTN_N_FACTS && n_out >= ATTN256_N_OUT, "ifa_attention_heads256_plan: %d facts, %d outputs expected", ATTN_N_FACTS, ATTN256_N_OUT);
+    AttnFacts f;
+    memcpy(&f, facts, sizeof(f));
+    const AttnHeads256Plan r = plan_attention_heads256(f);
     memcpy(out, &r, sizeof(r));
     return IFA_OK;
 }
@@ -977,6 +993,12 @@ extern "C" int ifa_attention(const void *q, const void *kcache, const void *vcac
     if (g_attn_mfma_heads && attn_heads16_head(head_dim) && q_tokens >= H16_MIN_QUERIES)
         return launch_attention_heads16(plan_attention_heads16(attn_facts(kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, 0)), q, kcache, vcache,
                                         kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, kq_scale, alibi, alibi_base_head, total_heads, out, hs);
+    if (g_attn_mfma_heads && head_dim == H256_HD) {
+        const AttnHeads256Plan p256 = plan_attention_heads256(attn_facts(kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, head_dim, 0));
+        if (p256.error == ATTN_OK)      // (refused -- fewer than 4 queries: k_attention below, as with the switch off)
+            return launch_attention_heads256(p256, q, kcache, vcache, kv_dtype, n_ctx, q_tokens, prefix_len, heads, kv_heads, kq_scale, alibi,
+                                             alibi_base_head, total_heads, out, hs);
+    }
     const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
     const size_t smem = (size_t)pl.lds;
     switch (pl.kind) {

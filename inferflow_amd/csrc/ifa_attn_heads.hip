@@ -1,4 +1,5 @@
-// ifa_attn_heads.hip -- prompt attention on the matrix cores for head_dim 48 / 80 / 96 (Phi-2 / StableLM, Phi-3-mini geometries).
+// ifa_attn_heads.hip -- prompt attention on the matrix cores for head_dim 48 / 80 / 96 (Phi-2 / StableLM, Phi-3-mini geometries), and for
+// 256 (Gemma) behind a plan of its own (launch_attention_heads256 at the end of the file).
 //
 // The 32 x 32 tile kernels of ifa_attn.hip need head_dim in multiples of 32 (the P.V output width) and have LDS swizzles written for 64
 // and 128; these head sizes therefore ran k_attention: one workgroup per (head, query), scalar dots, the whole prefix re-read per query.
@@ -32,6 +33,7 @@
 #include "ifa_device.h"
 #include "ifa_math.h"
 #include "ifa_attn_heads_plan.h"
+#include "ifa_attn_heads256_plan.h"
 
 namespace ifa {
 
@@ -71,7 +73,7 @@ __global__ void __launch_bounds__(256, 2) k_attention_heads16(const half_t *__re
                                                               int prefix_len, int heads, int kv_heads, float kq_scale,
                                                               int alibi, int alibi_base, int alibi_total, half_t *__restrict__ out)
 {
-    static_assert(attn_heads16_head(HD), "16-wide tiles: head_dim 48 / 80 / 96");
+    static_assert(attn_heads16_head(HD) || HD == H256_HD, "16-wide tiles: head_dim 48 / 80 / 96, and 256 behind its own plan");
     constexpr int KS32 = HD / 32;                    // x32 reduction steps of a score tile
     constexpr bool TAIL = HD % 32 != 0;              // ... and one x16 step over the last 16 dims
     constexpr int NT = HD / 16;                      // 16-wide output tiles
@@ -293,6 +295,31 @@ int launch_attention_heads16(const AttnHeads16Plan &pl, const void *q, const voi
     default: if (q8) IFA_H16(96, true); else IFA_H16(96, false); break;
     }
 #undef IFA_H16
+    IFA_LAUNCH_CHECK();
+    return IFA_OK;
+}
+
+// head_dim 256 (Gemma: 8 heads over 1 kv head, 16 over 16) behind plan_attention_heads256 (ifa_attn_heads256_plan.h): the same template.
+// At 256 it is 8 x32 steps per score tile and no x16 tail, 16 output tiles (64 accumulator registers), 64 halfs of Q per lane (32
+// registers), four staged chunks of K and of V per thread and block, a 32-value Q8 block inside one head; 182 (F16) / 222 (Q8)
+// VGPRs, no scratch, two workgroups per CU.  Its 74 752 bytes of LDS are past what a kernel gets unasked, hence the attribute.
+// A kernel written for this head size alone -- 128 queries per workgroup, a wave per 32 queries on v_mfma_f32_32x32x16_f16, Q (64
+// registers) and eight 32 x 32 output tiles (128) in registers, one wave per SIMD, half the LDS operand bytes per flop -- was measured
+// against this instantiation and lost at every size from 64 to 8192 queries (2048 queries, 16 heads, F16: 217 against 174 us): with one
+// wave per SIMD nothing overlaps its LDS reads, its dependent 16-step MFMA chain and its softmax, and at 8 or 16 heads a prompt of 2048
+// tokens gives 128-query tiles no more than one workgroup per CU.  docs/prompt_attention_heads256.md has the table.
+int launch_attention_heads256(const AttnHeads256Plan &pl, const void *q, const void *kcache, const void *vcache, int kv_dtype, int n_ctx,
+                              int q_tokens, int prefix_len, int heads, int kv_heads, float kq_scale, int alibi, int alibi_base,
+                              int alibi_total, void *out, hipStream_t s)
+{
+    IFA_REQUIRE(pl.error == ATTN_OK && pl.lds == H256_LDS && pl.q_per_wg == H16_QT, "ifa_attention: no plan for 256-wide heads (error %d)", pl.error);
+    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
+#define IFA_H256(Q8V) { auto kern = k_attention_heads16<H256_HD, Q8V>; \
+        IFA_HIP_CHECK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds)); \
+        kern<<<grid, dim3(256), (size_t)pl.lds, s>>>((const half_t *)q, (const uint8_t *)kcache, (const uint8_t *)vcache, n_ctx, q_tokens, \
+                                                     prefix_len, heads, kv_heads, kq_scale, alibi, alibi_base, alibi_total, (half_t *)out); }
+    if (kv_dtype == Q8_B32T2) IFA_H256(true) else IFA_H256(false)
+#undef IFA_H256
     IFA_LAUNCH_CHECK();
     return IFA_OK;
 }
