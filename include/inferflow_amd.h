@@ -224,7 +224,9 @@ int ifa_attention_plan(const int *facts, int n_facts, int *out, int n_out);
  * 7 fewer than 4 queries, 8 rows mode), queries per workgroup (64), grid x (query tiles), grid y (heads), dynamic LDS bytes, xcd_remap.
  * The same switch covers head_dim 256 (Gemma): with on = 1 a call of ifa_attention with head_dim 256 and at least 4 queries runs the
  * same kernel instantiated at 256 (8 x32 steps per score tile, 16 output tiles, 74 752 bytes of LDS), behind a plan of its own; passes
- * and rounding points as above.  Decode at 256 is not affected (it runs op by op).
+ * and rounding points as above.  The switch also opens the fused decode step to head_dim 256: with on = 1 ifa_model_fused_supported
+ * accepts the head size and single-token steps run k_dec_attn256 / k_dec_attn256_scores (csrc/ifa_decode_attn256.h: a key row split
+ * over a quad of lanes) in the captured step; with on = 0 such a model decodes op by op as before.  The answer is taken per call.
  * ifa_attention_heads256_plan: what that call launches (csrc/ifa_attn_heads256_plan.h); host-only as the one above, the same facts[10]
  * and out[6]: error (0 ok; 1 .. 5 as ifa_attention_plan; 6 head_dim not 256, 7 fewer than 4 queries, 8 rows mode), queries per
  * workgroup (64), grid x (query tiles), grid y (heads), dynamic LDS bytes, xcd_remap. */
@@ -542,7 +544,8 @@ int ifa_model_set_excluded_tokens(ifa_model *m, const int *ids_host, int n);
  * this call drains the stream, copies up to cap (key, ms) pairs in ascending key order, stores the number of keys there are in *n_out and
  * clears the map if clear != 0. */
 int ifa_model_perf_stat(ifa_model *m, int *keys_out, float *ms_out, int cap, int *n_out, int clear);
-/* 1 if the fused batch-1 decode kernels cover this model, else 0 (+ reason) */
+/* 1 if the fused batch-1 decode kernels cover this model, else 0 (+ reason).  head_dim 32 / 48 / 64 / 80 / 96 / 128 always, 256 only
+ * while ifa_attention_mfma_heads is on: asked on every call, so the next decode call follows a flipped switch. */
 int ifa_model_fused_supported(ifa_model *m, char *why, size_t why_len);
 /* One Infer() step for one query: n_tokens new tokens at positions
  * [prefix_len, prefix_len+n_tokens); op-by-op; synchronous.  logits_out_dev (F16

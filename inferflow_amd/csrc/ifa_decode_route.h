@@ -15,8 +15,9 @@ constexpr int DEC_PV_STAGE = 4096;           // keys of the score row k_dec_attn
 
 // dynamic LDS bytes.  k_dec_attn_scores: staging of 256 F16 key rows (a Q8 cache is read straight into registers); k_dec_attn_pv: partial
 // sums, the staged piece of the score row, this split's probabilities; k_dec_attn / the tail of k_dec_qkv_attn: q | k | v of the step,
-// partial sums, the K tile (ktile_rows > 0), the score row [max_ctx]
-constexpr size_t dec_attn_scores_smem(int head_dim, bool q8) { return q8 ? 16 : (size_t)256 * (head_dim * 2 + 16); }
+// partial sums, the K tile (ktile_rows > 0), the score row [max_ctx].  head_dim 256 (k_dec_attn256 / k_dec_attn256_scores,
+// ifa_decode_attn256.h): the same layouts; its scores kernel reads F16 rows straight into a quad's registers and stages nothing
+constexpr size_t dec_attn_scores_smem(int head_dim, bool q8) { return (q8 || head_dim == 256) ? 16 : (size_t)256 * (head_dim * 2 + 16); }
 constexpr size_t dec_attn_pv_smem(int head_dim, int max_ctx, int nsplits = 8)
 {
     const size_t nsplit = 256 / (head_dim / 8);

@@ -88,8 +88,11 @@ bool fused_supported(const ifa_model *m, std::string *why)
         return fail("output scales (attn_out_scale / ffn_out_scale / out_scale) on a partitioned model use the op-by-op path");
     if (c.experts > 0 && (c.norm_kind != 0 || c.parallel_attn || c.share_input)) return fail("MoE layers need the sequential RMS-norm wiring");
     if (!c.full_quant_gemv) return fail("full_quant_gemv disabled");
-    if (c.head_dim != 32 && c.head_dim != 48 && c.head_dim != 64 && c.head_dim != 80 && c.head_dim != 96 && c.head_dim != 128)
-        return fail("fused attention supports head_dim 32/48/64/80/96/128");
+    // head_dim 256 (Gemma): k_dec_attn256 / k_dec_attn256_scores, only while ifa_attention_mfma_heads is on (asked per call; off: the
+    // reason and every path are what they were before those kernels existed)
+    if (c.head_dim == 256) { if (!ifa_attention_mfma_heads(-1)) return fail("fused attention supports head_dim 32/48/64/80/96/128"); }
+    else if (c.head_dim != 32 && c.head_dim != 48 && c.head_dim != 64 && c.head_dim != 80 && c.head_dim != 96 && c.head_dim != 128)
+        return fail("fused attention supports head_dim 32/48/64/80/96/128 (256 behind attention_mfma_heads)");
     if (c.kv_dtype == Q8_B32T2 && c.head_dim % 32 != 0) return fail("Q8 KV needs head_dim % 32 == 0");
     if (dec_attn_pv_smem(c.head_dim, c.max_ctx, DEC_ATTN_MAX_SPLITS) > IFA_LDS_LIMIT) return fail("max_context_len too large for the fused attention kernels' LDS (decode falls back to the op-by-op path)");
     if (c.dim % 32 != 0 || c.ffn % 32 != 0) return fail("dim/ffn must be multiples of 32");
@@ -202,6 +205,10 @@ int decode_route_ready(ifa_model *m, int reach, bool own_launches)
     const DecRoute route = plan_decode_route(route_facts(m, reach, own_launches));
     m->route_reach = reach;
     if (!(route == m->route)) { m->route = route; drop_graphs(m); }
+    if (c.head_dim == 256) {      // the fused step of this head size hangs on the switch: steps captured under another value go
+        const int sw = ifa_attention_mfma_heads(-1);
+        if (sw != m->route_mfma_heads) { m->route_mfma_heads = sw; drop_graphs(m); }
+    }
     if (route.kind == DEC_ROUTE_FUSED_TAIL && !m->qa_gran) {
         const size_t n = (size_t)c.layers * (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim;
         DevBuf<unsigned long long> gran; DevBuf<unsigned> call, err;      // installed together, zeroed
@@ -375,6 +382,8 @@ int launch_attn(ifa_model *m, int l)
     const DecRoute R = unplanned ? plan_decode_route(route_facts(m, m->route_reach, true)) : m->route;
     hipStream_t s = m->stream;
     DecAttnParams A; attn_params(m, l, A);
+    // head_dim 256: kernels of its own (attn_dispatch also serves the batched and draft steps, which have none at this size)
+    if (c.head_dim == 256 && !(R.kind == DEC_ROUTE_SPLIT && R.error)) return launch_attn256(m, R, A);
     if (R.kind == DEC_ROUTE_SPLIT) {
         if (R.error) return ifa_fail(IFA_ERR_ARG, "fused attention: max_context_len %d needs %d bytes of LDS per workgroup", c.max_ctx, R.lds_pv);
         DecAttnSplitWs ws = m->attn_ws; ws.nsplits = R.nsplits;

@@ -132,8 +132,9 @@ struct InferenceConfig {
     bool lookup_sampled = false;
     // extension: prompt attention on the matrix cores for models with 48-, 80- or 96-wide heads (Phi-2 / StableLM / Phi-3-mini geometries):
     // Init sets ifa_attention_mfma_heads(1), and every prompt chunk of at least 4 tokens runs k_attention_heads16 instead of the scalar
-    // kernel.  The same key covers 256-wide heads (Gemma): their prompt chunks of at least 4 tokens run the same kernel at 256; their
-    // decode steps stay op by op.  The switch is process-wide; other head sizes are not affected.  Off by default.
+    // kernel.  The same key covers 256-wide heads (Gemma): their prompt chunks of at least 4 tokens run the same kernel at 256, and their
+    // single-token steps take the fused, captured decode step (k_dec_attn256) instead of running op by op -- which also opens
+    // device_sampler, sampled Generate and the device pool to them.  The switch is process-wide; other head sizes are not affected.  Off by default.
     bool attention_mfma_heads = false;
     // extension: context shift (host/context_shift.h; DESIGN.md "Context shift").  A query whose tokens reach max_context_len does not
     // end: the engine keeps its first context_shift_keep cache rows, drops the older half of the rows behind them and moves the rest
