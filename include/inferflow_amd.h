@@ -227,6 +227,12 @@ int ifa_attention_plan(const int *facts, int n_facts, int *out, int n_out);
  * and rounding points as above.  The switch also opens the fused decode step to head_dim 256: with on = 1 ifa_model_fused_supported
  * accepts the head size and single-token steps run k_dec_attn256 / k_dec_attn256_scores (csrc/ifa_decode_attn256.h: a key row split
  * over a quad of lanes) in the captured step; with on = 0 such a model decodes op by op as before.  The answer is taken per call.
+ * The value is a level: 0 / 1 / 2 are stored as given (larger values as 2) and returned as the previous value; everything above takes
+ * non-zero as on.  Level 2 adds the batched steps of a head_dim 256 model: ifa_model_decode_batch runs the fused, captured step on the
+ * rows GEMM with k_dec_attn256_batch (one workgroup per (head, row)) instead of op by op, ifa_model_decode_batch_steps accepts the
+ * model, ifa_model_decode_draft is fused (k_draft_kv_store at 256), and prompts of 2 .. 32 tokens take the rows GEMM; the captured
+ * steps of such a model are dropped when the level changes.  At levels 0 and 1 those paths are what they were
+ * (docs/decode_batch_heads256.md).
  * ifa_attention_heads256_plan: what that call launches (csrc/ifa_attn_heads256_plan.h); host-only as the one above, the same facts[10]
  * and out[6]: error (0 ok; 1 .. 5 as ifa_attention_plan; 6 head_dim not 256, 7 fewer than 4 queries, 8 rows mode), queries per
  * workgroup (64), grid x (query tiles), grid y (heads), dynamic LDS bytes, xcd_remap. */

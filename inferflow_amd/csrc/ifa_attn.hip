@@ -894,7 +894,8 @@ extern "C" int ifa_attention_two_pass_min_keys(int min_keys)
 }
 
 // head_dim 48 / 80 / 96, and 256 behind ifa_attn_heads256_plan.h, on the matrix cores (k_attention_heads16, ifa_attn_heads.hip) instead
-// of k_attention; opt-in
+// of k_attention; opt-in.  A level: every reader here takes non-zero as on; the engine reads 2 as "and the batched / draft steps of a
+// 256-wide model on the rows GEMM with k_dec_attn256_batch" (route_model_facts, ifa_engine_forward.hip)
 static int g_attn_mfma_heads = 0;
 namespace ifa {
 int launch_attention_heads16(const AttnHeads16Plan &pl, const void *q, const void *kcache, const void *vcache, int kv_dtype, int n_ctx,
@@ -908,7 +909,7 @@ int launch_attention_heads256(const AttnHeads256Plan &pl, const void *q, const v
 extern "C" int ifa_attention_mfma_heads(int on)
 {
     const int prev = g_attn_mfma_heads;
-    if (on >= 0) g_attn_mfma_heads = on ? 1 : 0;
+    if (on >= 0) g_attn_mfma_heads = on > 2 ? 2 : on;      // levels: 0 off, 1 on, 2 also the batched / draft steps of 256-wide heads
     return prev;
 }
 

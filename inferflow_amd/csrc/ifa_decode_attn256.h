@@ -1,5 +1,6 @@
-// ifa_decode_attn256.h -- the batch-1 decode attention for 256-wide heads (Gemma): k_dec_attn256 (one workgroup per head) and
-// k_dec_attn256_scores (keys split over workgroups; k_dec_attn_pv<256> / k_dec_attn_combine<256> finish that step).
+// ifa_decode_attn256.h -- the decode attention for 256-wide heads (Gemma): batch-1 k_dec_attn256 (one workgroup per head) and
+// k_dec_attn256_scores (keys split over workgroups; k_dec_attn_pv<256> / k_dec_attn_combine<256> finish that step), and
+// k_dec_attn256_batch (the batched and the draft step: one workgroup per (head, row)).
 //
 // dec_attn_body gives every lane a whole key row in registers: at 256 that is 128 VGPRs of key per lane (and as many of q in
 // k_dec_attn_scores).  Here a key row is split over a QUAD of lanes:
@@ -139,6 +140,91 @@ __device__ __forceinline__ void dec256_stage_new(half_t *qs, half_t *kn, half_t 
     }
 }
 
+// What follows the scores of a whole row in LDS (S [n_ctx], every thread's lmax): softmax and P.V with dec_attn_body's rounding points;
+// returns output element `tid` of the head in fp32.  Row n_ctx - 1 is the step's own: its value comes from vn (LDS), and no request
+// goes past the last cached row n_ctx - 2.
+template <bool Q8>
+__device__ __forceinline__ float dec256_softmax_pv(half_t *S, float *red, float *opart, const half_t *vn, const uint8_t *pvc, size_t row_bytes,
+                                                   size_t head_off, int n_ctx, float lmax, float kq_scale)
+{
+    constexpr int HD = D256, DG = HD / 8, NSPLIT = 256 / DG;       // 32 threads per V row, 8 key residues
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int pos = n_ctx - 1, jlast = max(pos - 1, 0);
+    // ---- softmax over S (probabilities from the F16 scores, fp32 sum, F16 e and P)
+    lmax = wave_max(lmax);
+    if (lane == 0) red[wave] = lmax;
+    __syncthreads();
+    const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float lsum = 0.0f;
+    for (int j = tid; j < n_ctx; j += 256) {
+        const float e = expf(kq_scale * h2f(S[j]) - mx);
+        lsum += e;
+        S[j] = f2h(e);
+    }
+    lsum = wave_sum(lsum);
+    if (lane == 0) red[4 + wave] = lsum;
+    __syncthreads();
+    const float inv = 1.0f / (((red[4] + red[5]) + red[6]) + red[7]);
+    for (int j = tid; j < n_ctx; j += 256) S[j] = f2h(h2f(S[j]) * inv);
+    __syncthreads();
+
+    // ---- O = P.V: thread (sp, dg) accumulates keys sp, sp + 8, ... for its 8 dims, groups of TB keys, the next group requested
+    // before the current one is multiplied (clamped rows)
+    const int dg = tid % DG, sp = tid / DG;
+    constexpr int TB = 8;
+    u32x4 vcur[Q8 ? 1 : TB], vnxt[Q8 ? 1 : TB];
+    uint32_t sc_c[Q8 ? TB : 1], cw_c[Q8 ? TB : 1][2], sc_n[Q8 ? TB : 1], cw_n[Q8 ? TB : 1][2];      // Q8: block scale (half bits), the thread's 8 codes
+    const size_t vq_off = head_off + (size_t)(dg / 4) * 34;
+    auto vload = [&](u32x4 (&dst)[Q8 ? 1 : TB], uint32_t (&ds)[Q8 ? TB : 1], uint32_t (&dc)[Q8 ? TB : 1][2], int j0) {
+#pragma unroll
+        for (int u = 0; u < TB; u++) {
+            const int jr = min(j0 + u * NSPLIT, jlast);
+            if constexpr (!Q8) dst[u] = IFA_GP(u32x4, pvc + (size_t)jr * row_bytes + head_off)[dg];
+            else {
+                const auto *blk = IFA_GP(uint16_t, pvc + (size_t)jr * row_bytes + vq_off);
+                typedef uint32_t u32x2_a2 __attribute__((ext_vector_type(2), aligned(2)));
+                ds[u] = blk[0];
+                const u32x2_a2 cw = *IFA_GP(u32x2_a2, blk + 1 + (dg % 4) * 4);
+                dc[u][0] = cw[0]; dc[u][1] = cw[1];
+            }
+        }
+    };
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) o[e] = 0.0f;
+    vload(vcur, sc_c, cw_c, sp);
+    for (int j = sp; j < n_ctx; j += TB * NSPLIT) {
+        vload(vnxt, sc_n, cw_n, j + TB * NSPLIT);
+#pragma unroll
+        for (int u = 0; u < TB; u++) {
+            const int jj = j + u * NSPLIT;
+            if (jj >= n_ctx) break;
+            const float pj = h2f(S[jj]);
+            half8_t v8;
+            if (jj == pos) v8 = *reinterpret_cast<const half8_t *>(vn + dg * 8);
+            else if constexpr (!Q8) v8 = __builtin_bit_cast(half8_t, vcur[u]);
+            else {
+                const float sc = hbits2f((uint16_t)sc_c[u]);
+#pragma unroll
+                for (int e = 0; e < 8; e++) v8[e] = f2h((float)(int)(int8_t)((cw_c[u][e >> 2] >> (8 * (e & 3))) & 0xFFu) * sc);
+            }
+#pragma unroll
+            for (int e = 0; e < 8; e++) o[e] = __builtin_fmaf(pj, (float)v8[e], o[e]);
+        }
+#pragma unroll
+        for (int u = 0; u < TB; u++) {
+            if constexpr (Q8) { sc_c[u] = sc_n[u]; cw_c[u][0] = cw_n[u][0]; cw_c[u][1] = cw_n[u][1]; }
+            else vcur[u] = vnxt[u];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) opart[sp * HD + dg * 8 + e] = o[e];
+    __syncthreads();
+    float acc = opart[tid];
+    for (int s2 = 1; s2 < NSPLIT; s2++) acc = acc + opart[s2 * HD + tid];      // residue order
+    return acc;
+}
+
 // One workgroup (256 threads) per query head: k_dec_attn<HD, Q8, false, 256, false>'s job at HD = 256.  Dynamic LDS:
 // dec_attn_smem(256, max_ctx, 0) -- q | k | v, red[16], opart[8][256], the score row.  The leading scalar arguments are k_dec_attn's
 // (preloaded into SGPRs): the first pass's rows (keys 0 .. 63: the cache holds at least DEC_ATTN_MIN_ROWS rows) are requested before
@@ -154,7 +240,7 @@ __global__ void __launch_bounds__(256) k_dec_attn256(const half_t *pq, const uin
     float *red = reinterpret_cast<float *>(vn + HD);               // [16]
     float *opart = red + 16;                                       // [NSPLIT][HD]
     half_t *S = reinterpret_cast<half_t *>(opart + NSPLIT * HD);   // [n_ctx]
-    const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = blockIdx.x, tid = threadIdx.x;
     const int ql = tid & 3, qk = tid >> 2;                         // quad lane, key of the pass
     const int group = pheads / pkvh, kvh = h / group;
     const bool writer = (h % group) == 0;
@@ -199,81 +285,87 @@ __global__ void __launch_bounds__(256) k_dec_attn256(const half_t *pq, const uin
         }
         kcur = knxt;
     }
-    // ---- softmax over S (dec_attn_body's: probabilities from the F16 scores, fp32 sum, F16 e and P)
-    lmax = wave_max(lmax);
-    if (lane == 0) red[wave] = lmax;
-    __syncthreads();
-    const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    float lsum = 0.0f;
-    for (int j = tid; j < n_ctx; j += 256) {
-        const float e = expf(P.kq_scale * h2f(S[j]) - mx);
-        lsum += e;
-        S[j] = f2h(e);
-    }
-    lsum = wave_sum(lsum);
-    if (lane == 0) red[4 + wave] = lsum;
-    __syncthreads();
-    const float inv = 1.0f / (((red[4] + red[5]) + red[6]) + red[7]);
-    for (int j = tid; j < n_ctx; j += 256) S[j] = f2h(h2f(S[j]) * inv);
-    __syncthreads();
-
-    // ---- O = P.V: thread (sp, dg) accumulates keys sp, sp + 8, ... for its 8 dims, groups of TB keys, the next group requested
-    // before the current one is multiplied (clamped rows; the new token's value comes from LDS)
-    const int dg = tid % DG, sp = tid / DG;
-    constexpr int TB = 8;
-    u32x4 vcur[Q8 ? 1 : TB], vnxt[Q8 ? 1 : TB];
-    uint32_t sc_c[Q8 ? TB : 1], cw_c[Q8 ? TB : 1][2], sc_n[Q8 ? TB : 1], cw_n[Q8 ? TB : 1][2];      // Q8: block scale (half bits), the thread's 8 codes
-    const size_t vq_off = head_off + (size_t)(dg / 4) * 34;
-    auto vload = [&](u32x4 (&dst)[Q8 ? 1 : TB], uint32_t (&ds)[Q8 ? TB : 1], uint32_t (&dc)[Q8 ? TB : 1][2], int j0) {
-#pragma unroll
-        for (int u = 0; u < TB; u++) {
-            const int jr = min(j0 + u * NSPLIT, max(pos - 1, 0));
-            if constexpr (!Q8) dst[u] = IFA_GP(u32x4, pvc + (size_t)jr * row_bytes + head_off)[dg];
-            else {
-                const auto *blk = IFA_GP(uint16_t, pvc + (size_t)jr * row_bytes + vq_off);
-                typedef uint32_t u32x2_a2 __attribute__((ext_vector_type(2), aligned(2)));
-                ds[u] = blk[0];
-                const u32x2_a2 cw = *IFA_GP(u32x2_a2, blk + 1 + (dg % 4) * 4);
-                dc[u][0] = cw[0]; dc[u][1] = cw[1];
-            }
-        }
-    };
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; e++) o[e] = 0.0f;
-    vload(vcur, sc_c, cw_c, sp);
-    for (int j = sp; j < n_ctx; j += TB * NSPLIT) {
-        vload(vnxt, sc_n, cw_n, j + TB * NSPLIT);
-#pragma unroll
-        for (int u = 0; u < TB; u++) {
-            const int jj = j + u * NSPLIT;
-            if (jj >= n_ctx) break;
-            const float pj = h2f(S[jj]);
-            half8_t v8;
-            if (jj == pos) v8 = *reinterpret_cast<const half8_t *>(vn + dg * 8);
-            else if constexpr (!Q8) v8 = __builtin_bit_cast(half8_t, vcur[u]);
-            else {
-                const float sc = hbits2f((uint16_t)sc_c[u]);
-#pragma unroll
-                for (int e = 0; e < 8; e++) v8[e] = f2h((float)(int)(int8_t)((cw_c[u][e >> 2] >> (8 * (e & 3))) & 0xFFu) * sc);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; e++) o[e] = __builtin_fmaf(pj, (float)v8[e], o[e]);
-        }
-#pragma unroll
-        for (int u = 0; u < TB; u++) {
-            if constexpr (Q8) { sc_c[u] = sc_n[u]; cw_c[u][0] = cw_n[u][0]; cw_c[u][1] = cw_n[u][1]; }
-            else vcur[u] = vnxt[u];
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) opart[sp * HD + dg * 8 + e] = o[e];
-    __syncthreads();
-    float acc = opart[tid];
-    for (int s2 = 1; s2 < NSPLIT; s2++) acc = acc + opart[s2 * HD + tid];      // residue order
+    const float acc = dec256_softmax_pv<Q8>(S, red, opart, vn, pvc, row_bytes, head_off, n_ctx, lmax, P.kq_scale);
     const half_t yh = f2h(acc);
     P.out[(size_t)h * HD + tid] = yh;
     if (P.xq) dec_attn_emit_q8<HD>(P.xq, pheads * HD, h, tid, yh);
+}
+
+// The batched and the draft step, grid (heads, rows): k_dec_attn<HD, Q8, true>'s job at HD = 256, one workgroup per (head, row) with
+// the quad mapping above.  Row b's cache pointers and context come from DecAttnBatchRow[b] (one scalar fetch), its q | k | v from
+// q + b * q_stride, its (cos, sin) pairs from rope_tab + b * 256, its output goes to out + b * heads * 256; no quantised image.
+// P.skip_store (the draft step: the rows of ONE slot are in the cache already, k_draft_kv_store): nobody writes, a Q8 cache still
+// round-trips the row's own k and v in LDS, rows pos0 .. pos - 1 are history like any other.  Every cache request is clamped to the
+// row's own last cached row (pos - 1): a workgroup never touches row pos of the cache -- the writer head of its group may be storing it
+// -- nor a row past its context, which in a batched step may belong to nobody.
+// The table entry is the one thing k_dec_attn256 does not wait for: the first pass's rows cannot be requested before it is known
+// (another row's cache, another clamp).  The leading scalar arguments -- q | k | v, the table (P.batch_rows), the head counts, the row
+// stride (P.q_stride) -- are preloaded into SGPRs, so the entry is a 20-byte scalar fetch issued with the kernel's first instructions,
+// next to the requests for the row's q | k | v values, which hang on those arguments alone: one scalar round trip in front of the
+// first cache request, not two (docs/decode_batch_heads256.md).
+template <bool Q8>
+__global__ void __launch_bounds__(256) k_dec_attn256_batch(const half_t *pq, const DecAttnBatchRow *prows, int pheads, int pkvh, int pq_stride,
+                                                           const DecAttnParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int HD = D256, DG = HD / 8, NSPLIT = 256 / DG;       // 32 threads per V row, 8 key residues
+    half_t *qs = reinterpret_cast<half_t *>(smem);
+    half_t *kn = qs + HD;
+    half_t *vn = kn + HD;
+    float *red = reinterpret_cast<float *>(vn + HD);               // [16]
+    float *opart = red + 16;                                       // [NSPLIT][HD]
+    half_t *S = reinterpret_cast<half_t *>(opart + NSPLIT * HD);   // [n_ctx]
+    const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int ql = tid & 3, qk = tid >> 2;                         // quad lane, key of the pass
+    const int group = pheads / pkvh, kvh = h / group;
+    const size_t row_bytes = Q8 ? (size_t)pkvh * (HD / 32) * 34 : (size_t)pkvh * HD * 2;
+    const size_t head_off = Q8 ? (size_t)kvh * (HD / 32) * 34 : (size_t)kvh * HD * 2;
+
+    // ---- the table entry (uniform: one scalar fetch, as in dec_attn_body), behind it -- in program order, not in time -- the row's values
+    const DecAttnBatchRow br = prows[b];
+    const half_t *qrow = pq + (size_t)b * pq_stride;
+    const half_t q_in = qrow[(size_t)h * HD + tid], k_in = qrow[(size_t)(pheads + kvh) * HD + tid], v_in = qrow[(size_t)(pheads + pkvh + kvh) * HD + tid];
+    float rope_c = 1.0f, rope_s = 0.0f;
+    {
+        const int c = tid < HD / 2 ? tid : tid - HD / 2;
+        const float *rt = P.rope_tab ? P.rope_tab + (size_t)b * HD : reinterpret_cast<const float *>(qrow);      // (a valid dummy address without RoPE)
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        const f32x2 cs = *IFA_GP(f32x2, rt + 2 * c);
+        if (P.rope_order != 0) { rope_c = cs[0]; rope_s = cs[1]; }
+    }
+    const uint8_t *const pkc = br.kc, *const pvc = br.vc;
+    const int n_ctx = br.n_ctx, pos = n_ctx - 1;
+    const int jlast = max(pos - 1, 0);                             // the row's last cached row: the clamp of every request
+    const bool writer = (h % group) == 0 && !P.skip_store;
+    Dec256Key<Q8> kcur, knxt;
+    dec256_load_key<Q8>(kcur, pkc + (size_t)min(qk, jlast) * row_bytes + head_off, ql);
+    // (skip_store: store = true still runs a Q8 cache's round trip in LDS; `writer` false keeps the cache as k_draft_kv_store left it)
+    dec256_stage_new<Q8>(qs, kn, vn, q_in, k_in, v_in, rope_c, rope_s, P, const_cast<uint8_t *>(pkc), const_cast<uint8_t *>(pvc),
+                         (size_t)pos * row_bytes + head_off, true, writer);
+
+    // ---- scores: a quad per key, 64 keys per pass
+    half8_t qreg[8];
+    dec256_lds_share<Q8>(qreg, qs, ql);
+    const float alpha = 1.0f / sqrtf((float)HD) / P.kq_scale;
+    const float mk = P.alibi ? alibi_slope(h + P.alibi_base, P.alibi_total) : 0.0f;
+    float lmax = -INFINITY;
+    for (int jb = 0; jb < n_ctx; jb += D256_PASS) {
+        const int j = jb + qk;
+        dec256_load_key<Q8>(knxt, pkc + (size_t)min(j + D256_PASS, jlast) * row_bytes + head_off, ql);
+        half8_t kh[8];
+        if (j == pos) dec256_lds_share<Q8>(kh, kn, ql);       // the row's own (round-tripped) key never leaves the LDS
+        else dec256_key_halves<Q8>(kh, kcur);
+        const float c = dec256_quad_dot(qreg, kh);
+        if (ql == 0 && j < n_ctx) {
+            half_t s = f2h(alpha * c);
+            if (P.alibi) { float a = (float)j * mk; s = f2h(a + h2f(s)); }
+            S[j] = s;
+            lmax = fmaxf(lmax, P.kq_scale * h2f(s));
+        }
+        kcur = knxt;
+    }
+    const float acc = dec256_softmax_pv<Q8>(S, red, opart, vn, pvc, row_bytes, head_off, n_ctx, lmax, P.kq_scale);
+    P.out[((size_t)b * pheads + h) * HD + tid] = f2h(acc);
 }
 
 // Keys split over workgroups, grid (heads, nsplits): k_dec_attn_scores' contract (DecAttnSplitWs: S [heads][max_ctx], lmax

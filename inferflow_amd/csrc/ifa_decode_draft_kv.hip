@@ -12,7 +12,7 @@
 // The arithmetic is the attention kernel's, expression for expression: the pair rotation is rope_apply on the row staged in LDS
 // with the (cos, sin) pairs of m->brope (k_dec_batch_gather, one set per row), the F16 row is the rotated halves, the Q8_B32T2 row
 // is the in-kernel store's quantiser (block maximum over 32 lanes, scale = max / 127, codes roundf(value / scale) clamped).  So the
-// bytes equal what k_dec_attn<.., BATCH> writes for a query at that position, and row i of the step is bit for bit the row
+// bytes equal what k_dec_attn<.., BATCH> (head_dim 256: k_dec_attn256_batch) writes for a query at that position, and row i of the step is bit for bit the row
 // ifa_model_decode_batch computes for a query whose slot holds the same bytes in rows [0, pos0 + i).
 #include "ifa_engine_state.h"
 
@@ -25,7 +25,8 @@ __global__ void __launch_bounds__(256) k_draft_kv_store(const half_t *__restrict
                                                         const float *__restrict__ rope_tab, int rope_order, int rope_cols,
                                                         const AttnRowH *__restrict__ rows)
 {
-    static_assert(HD % 8 == 0 && HD <= 128 && (!Q8 || HD % 32 == 0), "head size: multiples of 8 up to 128 (Q8 rows: whole 32-blocks)");
+    // (256: 256 threads stage, 128 rotate, the 16 Q8 blocks take two rounds over the 8 half waves, an F16 slice is 32 16-byte pieces)
+    static_assert(HD % 8 == 0 && HD <= 256 && (!Q8 || HD % 32 == 0), "head size: multiples of 8 up to 256 (Q8 rows: whole 32-blocks)");
     __shared__ __attribute__((aligned(16))) half_t kn[HD];
     __shared__ __attribute__((aligned(16))) half_t vn[HD];
     const int kvh = blockIdx.x, r = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -86,6 +87,7 @@ int draft_kv_store_launch(ifa_model *m, int n, const half_t *k, const half_t *v,
     case 64: if (q8) IFA_DKV(64, true); else IFA_DKV(64, false); break;
     case 96: if (q8) IFA_DKV(96, true); else IFA_DKV(96, false); break;
     case 128: if (q8) IFA_DKV(128, true); else IFA_DKV(128, false); break;
+    case 256: if (q8) IFA_DKV(256, true); else IFA_DKV(256, false); break;
     case 48: if (q8) return ifa_fail(IFA_ERR_ARG, "draft step: Q8 cache with head_dim 48"); IFA_DKV(48, false); break;
     case 80: if (q8) return ifa_fail(IFA_ERR_ARG, "draft step: Q8 cache with head_dim 80"); IFA_DKV(80, false); break;
     default: return ifa_fail(IFA_ERR_ARG, "draft step: head_dim %d", c.head_dim);

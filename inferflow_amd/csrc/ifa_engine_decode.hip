@@ -197,6 +197,15 @@ static DecRouteFacts route_facts(const ifa_model *m, int reach, bool own_launche
     return f;
 }
 
+// The steps of a 256-wide model hang on ifa_attention_mfma_heads (level 1: the fused single-token step, level 2: also the fused batched,
+// draft and device-fed steps): the captured steps of every kind go when the level is not the one they were captured under.
+void mfma_heads_level_ready(ifa_model *m)
+{
+    if (m->cfg.head_dim != 256) return;
+    const int sw = ifa_attention_mfma_heads(-1);
+    if (sw != m->route_mfma_heads) { m->route_mfma_heads = sw; drop_graphs(m); }
+}
+
 // Plans the route of a decode call that reaches `reach` keys (the captured steps hold it: they go when it changes) and allocates what
 // its launches need (never under capture).  own_launches: the tensor-parallel step -- split and bucket are chosen, the fused launches are off.
 int decode_route_ready(ifa_model *m, int reach, bool own_launches)
@@ -205,10 +214,7 @@ int decode_route_ready(ifa_model *m, int reach, bool own_launches)
     const DecRoute route = plan_decode_route(route_facts(m, reach, own_launches));
     m->route_reach = reach;
     if (!(route == m->route)) { m->route = route; drop_graphs(m); }
-    if (c.head_dim == 256) {      // the fused step of this head size hangs on the switch: steps captured under another value go
-        const int sw = ifa_attention_mfma_heads(-1);
-        if (sw != m->route_mfma_heads) { m->route_mfma_heads = sw; drop_graphs(m); }
-    }
+    mfma_heads_level_ready(m);
     if (route.kind == DEC_ROUTE_FUSED_TAIL && !m->qa_gran) {
         const size_t n = (size_t)c.layers * (size_t)(c.heads + 2 * c.kv_heads) * c.head_dim;
         DevBuf<unsigned long long> gran; DevBuf<unsigned> call, err;      // installed together, zeroed

@@ -176,7 +176,10 @@ static RouteModelFacts route_model_facts(const ifa_model *m)
     const ifa_model_config &c = m->cfg;
     const size_t D = c.dim, QD = (size_t)c.heads * c.head_dim, KVD = (size_t)c.kv_heads * c.head_dim, F = c.ffn;
     const bool plain = !has_post_norms(m) && !c.parallel_attn && !c.share_input && !scale_on(c.attn_out_scale) && !scale_on(c.ffn_out_scale);
-    const bool hd_ok = c.head_dim == 32 || c.head_dim == 48 || c.head_dim == 64 || c.head_dim == 80 || c.head_dim == 96 || c.head_dim == 128;
+    // (256: k_dec_attn256_batch, only at level 2 of ifa_attention_mfma_heads -- asked per call; below it every path of a 256-wide model is
+    //  what it was before that kernel existed)
+    const bool hd_ok = c.head_dim == 32 || c.head_dim == 48 || c.head_dim == 64 || c.head_dim == 80 || c.head_dim == 96 || c.head_dim == 128
+                       || (c.head_dim == 256 && ifa_attention_mfma_heads(-1) >= 2);
     RouteModelFacts r;
     if (plain && gemm_rows_use_mfma() && c.norm_kind == 0 && !scale_on(c.out_scale) && !(D % 128 || QD % 128 || F % 128 || D > 4096 || KVD % 16) && hd_ok
         && !(c.kv_dtype == Q8_B32T2 && c.head_dim % 32 != 0) && dec_attn_smem(c.head_dim, c.max_ctx) <= IFA_LDS_LIMIT) r.rows_layers = 2;
@@ -592,7 +595,9 @@ static int batch_fused_layer(ifa_model *m, const BatchRoute &R, int l, int n, co
         A.skip_store = draft ? 1 : 0; A.xq = nullptr; A.trace = nullptr;
         const size_t asmem = dec_attn_smem(c.head_dim, c.max_ctx);
         const dim3 grid((unsigned)c.heads, (unsigned)n), block(256);
-        rc = attn_dispatch(c.head_dim, A.kv_q8 != 0, [&](auto hd, auto q8) {
+        // head_dim 256: a kernel of its own (a key row split over a quad of lanes: ifa_decode_attn256.h)
+        if (c.head_dim == 256) rc = launch_attn256_batch(m, n, asmem, A);
+        else rc = attn_dispatch(c.head_dim, A.kv_q8 != 0, [&](auto hd, auto q8) {
             return launch_lds(k_dec_attn<decltype(hd)::value, decltype(q8)::value, true>, grid, block, asmem, m->stream,
                               A.q, nullptr, nullptr, A.heads, A.kv_heads, A);
         });
@@ -665,6 +670,7 @@ int forward_batch(ifa_model *m, int n, const int *tokens_host, const int *pos_ho
     // (measured on Llama-2-7B Q4: the op-by-op step is bound by the small-T GEMM kernels, ~6.7 ms with or without the graph, so its replay
     //  is opt-in: set_option("batch_graph", 1).  The fused step -- five launches per layer, MoE layers routed on the device -- is
     //  launch-bound without a graph, so it is replayed)
+    mfma_heads_level_ready(m);      // (a 256-wide model's route hangs on the switch: steps captured under another level go)
     BatchRoute R;
     if ((rc = batch_route_ready(m, n, logits_out != nullptr, false, R))) return rc;
     const bool fused = R.kind == BATCH_FUSED, use_graph = R.captured != 0;

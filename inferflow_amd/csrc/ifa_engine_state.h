@@ -211,7 +211,7 @@ struct ifa_model : Scratch {
     // What the decode step of the last planned call runs (ifa_decode_route.h: the attention launch, its kernel instance, the chained
     // FFN launch) and the reach it was planned for; the captured steps hold it (decode_route_ready)
     DecRoute route; int route_reach = 256;
-    int route_mfma_heads = 0;      // ifa_attention_mfma_heads as the captured steps of a 256-wide model saw it (fused_supported asks it per call)
+    int route_mfma_heads = 0;      // ifa_attention_mfma_heads (level 0 / 1 / 2) as the captured steps of a 256-wide model saw it (asked per call)
     PromptRoute prompt_route;      // what the last prompt call ran (ifa_prompt_route.h, prompt_route_ready)
     // attention as the tail of the QKV launch (ifa_decode_qkv_attn.h): granules [layers][(heads + 2 kv_heads) * head_dim], the
     // decode-call counter the tags are built from, its own error word
@@ -484,11 +484,13 @@ bool fused_supported(const ifa_model *m, std::string *why);
 int sep_norm(ifa_model *m, const half_t *x, const Tensor &w, const Tensor &b, half_t *dst);
 void attn_params(ifa_model *m, int l, DecAttnParams &A);      // (the batch-1 step's; batch_fused_layer overrides the per-row fields)
 int decode_route_ready(ifa_model *m, int reach, bool own_launches = false);
+void mfma_heads_level_ready(ifa_model *m);
 void qkv_params(ifa_model *m, int l, const half_t *x, DecGemvParams &P);
 int launch_qkv_attn(ifa_model *m, int l, const half_t *x, unsigned tag_add = 0);
 int launch_qkv(ifa_model *m, int l, const half_t *x);
 int launch_attn(ifa_model *m, int l);
 int launch_attn256(ifa_model *m, const DecRoute &R, const DecAttnParams &A);      // (ifa_decode_attn256.hip: head_dim 256, never the fused tail)
+int launch_attn256_batch(ifa_model *m, int n, size_t lds, const DecAttnParams &A);      // (ifa_decode_attn256.hip: the batched / draft step's rows)
 int launch_wo(ifa_model *m, int l, const half_t *x, half_t *partial = nullptr);
 void moe_params(ifa_model *m, Layer &L, DecGemvParams &P, int slot, int tab_off);
 int launch_ffn13(ifa_model *m, int l, int moe_slot = -1, const half_t *x_layer = nullptr, int moe_nslots = 1);

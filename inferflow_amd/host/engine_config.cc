@@ -135,7 +135,12 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "lookup_ngram_min", config.lookup_ngram_min);
     if (!LookupConfigOk(config)) return false;
     cfg.GetItem(section, "lookup_sampled", config.lookup_sampled);
-    cfg.GetItem(section, "attention_mfma_heads", config.attention_mfma_heads);
+    {   // true / false (1 / 0) as ever, or the level 2
+        bool on = config.attention_mfma_heads != 0;
+        std::string level;
+        if (cfg.GetItem(section, "attention_mfma_heads", on)) config.attention_mfma_heads = on ? 1 : 0;
+        if (cfg.GetItem(section, "attention_mfma_heads", level) && IniConfig::Trim(level) == "2") config.attention_mfma_heads = 2;
+    }
     cfg.GetItem(section, "is_study_mode", config.debug.is_study_mode);
     cfg.GetItem(section, "show_tensors", config.debug.show_tensors);
     return true;

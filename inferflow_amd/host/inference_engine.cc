@@ -98,7 +98,7 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
     }
     shift_active_ = config_.context_shift && SupportsContextShift();
     device_sampler_active_ = config_.device_sampler && !multi_ && !config_.return_output_tensors;
-    if (config_.attention_mfma_heads) ifa_attention_mfma_heads(1);      // (process-wide; the key off leaves the switch as it is)
+    if (config_.attention_mfma_heads) ifa_attention_mfma_heads(config_.attention_mfma_heads);      // (the level, process-wide; the key off leaves the switch as it is)
     if (prefix_active_) slot_records_.assign((size_t)kv_slots_, SlotRecord());
     return true;
 }

@@ -135,7 +135,10 @@ struct InferenceConfig {
     // kernel.  The same key covers 256-wide heads (Gemma): their prompt chunks of at least 4 tokens run the same kernel at 256, and their
     // single-token steps take the fused, captured decode step (k_dec_attn256) instead of running op by op -- which also opens
     // device_sampler, sampled Generate and the device pool to them.  The switch is process-wide; other head sizes are not affected.  Off by default.
-    bool attention_mfma_heads = false;
+    // The key is a level: true / 1 as above; 2 (ifa_attention_mfma_heads(2)) also puts the batched, draft and device-fed steps of a 256-wide
+    // model and its prompts of 2 .. 32 tokens on the rows GEMM with k_dec_attn256_batch instead of op by op, so GenerateBatch runs batched
+    // (model_info "batch_generate") and GenerateLookup's draft steps are fused (docs/decode_batch_heads256.md).
+    int attention_mfma_heads = 0;
     // extension: context shift (host/context_shift.h; DESIGN.md "Context shift").  A query whose tokens reach max_context_len does not
     // end: the engine keeps its first context_shift_keep cache rows, drops the older half of the rows behind them and moves the rest
     // down on the device (ifa_model_kv_shift: K rows re-rotated to their new positions), then goes on.  An approximation by design
