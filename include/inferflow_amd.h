@@ -504,7 +504,12 @@ int ifa_model_reset(ifa_model *m);
  * of a prompt, one by one -- runs in the summation order of the reference's CUDA kernels, csrc/ifa_exact.hip: a parity instrument whose
  * logits, ids and int8 codes equal the CPU oracle's bit for bit; fails for models outside that step instead of changing arithmetic),
  * "q3h_native" (0; 1: Q3H_B64T1 Wo / W1 / W3 / W2 streamed at 32 bytes per block, pair codes decoded in the kernel: bit-identical, measured slower),
- * "perf_stat" (0; 1: steps and prompts take the op-by-op layer with a HIP event pair around every phase, see ifa_model_perf_stat) */
+ * "perf_stat" (0; 1: steps and prompts take the op-by-op layer with a HIP event pair around every phase, see ifa_model_perf_stat),
+ * "rows_i8" (0; 1: the rows-GEMM launches of batched / draft steps and of prompts of 2..32 tokens whose tensors are tiled Q4_B32T1 run
+ * k_gemm_rows_i8 where its plan accepts the shape -- every row in the single-token step's int8 arithmetic, bit-equal to the decode GEMV of
+ * that row whatever rows share the launch; docs/rows_gemm_int8.md.  Covered: rows of a multiple of 128 columns, the fused norm up to 4096
+ * columns; a launch outside that keeps the F16 kernel, and the lm_head of a batched step is the generic product, not this path: the
+ * layers' outputs are in the int8 arithmetic, the logits are not.  Measured about 3 x slower per step than the F16 kernels) */
 /* Independent KV caches inside one worker, one per concurrent query -- the reference keeps a LayerKVCache set
  * per query processor (QueryStateTable, src/transformer/query_state_table.h:19-85; KVCache::Init, kv_cache.cc:278-319).
  * ifa_model_kv_slots grows the number of caches to n_slots (slot 0 exists after finalize); ifa_model_select_kv
@@ -909,6 +914,24 @@ int ifa_gemm_big_plan(const int *facts, int n_facts, int *out, int n_out);
  * the order they are tried (kparts, kpm, tiles per workgroup or group, groups, grid, lds, scratch bytes): K parts first where they apply,
  * the plain launch (kparts 0) last. */
 int ifa_gemm_rows_plan(const int *facts, int n_facts, int *out, int n_out);
+/* The launch plan of the int8 rows GEMM (k_gemm_rows_i8; csrc/ifa_gemm_rows_i8_plan.h, docs/rows_gemm_int8.md).  Host-only.  facts[11], in the
+ * order of GemmRowsI8Facts: T, w_dtype, cols, nsets, rows0, rows1, rows2, epi (0 plain, 1 residual, 2 gated pair), norm, has_w1, num_cus.
+ * out[10], in the order of GemmRowsI8Plan: error (0 ok, 1 T outside 2..32, 2 dtype, 3 K no multiple of 128, 4 gated pair / epilogue, 5 rows,
+ * 6 fused norm past its K limit, 7 LDS), token_tiles (grid.x), total_rows, ntiles (16-row tiles; gated pair:
+ * pairs), tiles_per_wg, grid (grid.y), lds bytes, norm_k_max, row_stride (bytes of a token row's image in LDS),
+ * tokens_per_wg (token rows a workgroup stages: what the LDS holds, at most 16). */
+int ifa_gemm_rows_i8_plan(const int *facts, int n_facts, int *out, int n_out);
+/* Y[T][rows] = X[T][cols] . W^T for 2 <= T <= 32 over TILED Q4_B32T1A / B weights in the arithmetic of the single-token step: row t is bit
+ * for bit ifa_gemv_tiled(w_dtype, Wt, ..., ifa_quantize_act_q8(x_t), bias) (norm = 1: of ifa_layernorm(x_t) with norm_w, multi_base, eps;
+ * cols <= 4096), followed by the decode step's epilogue.  nsets 1..3 matrices form one row space (rows % 16 == 0 each when there are several),
+ * written to y_f16[t * ldy + row] or, with yset_f16, set i to yset_f16[i][t * rows[i] + row].  epi 0: + bias; 1: half(res[t * ldres + row] +
+ * y); 2: act(y1) * y3 with W1_tiled = w3 (one set; act_kind 0 SiLU, 1 GELU, 2 ReLU).  x_f16 / norm_w_f16 are 16-byte aligned and ldx % 8 == 0.
+ * num_cus: 0 = the device's, else the CU count the launch is planned for (fewer CUs: more tiles per workgroup).  IFA_ERR_ARG when
+ * ifa_gemm_rows_i8_plan refuses. */
+int ifa_gemm_rows_q8(int w_dtype, const void *const Wt_tiled[3], const int rows[3], int nsets, const void *W1_tiled, size_t cols,
+                     const void *x_f16, int ldx, int T, int epi, int norm, const void *norm_w_f16, float multi_base, float eps,
+                     const void *const bias_f16[3], const void *bias1_f16, const void *res_f16, int ldres, int act_kind, void *y_f16, int ldy,
+                     void *const yset_f16[3], int num_cus, ifa_stream stream);
 /* The last rows GEMM launches of this process, oldest first; reading clears them.  out[2 + 8 x 23]: out[0] records that follow (at most 8),
  * out[1] launches since the last read, then per record: T, total_rows, nblk, epi, norm, mo, tx, ch, nchunk, n_try, attempt (index of the
  * attempt that ran), the attempt's seven plan fields, and -- attempt > 0: the K-parts attempt was declined -- what the residency test saw:

@@ -164,6 +164,8 @@ SIGNATURES = {
     "ifa_gemm_mid_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_big_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_gemm_rows_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_gemm_rows_i8_plan": (_i, [_vp, _i, _vp, _i]),
+    "ifa_gemm_rows_q8": (_i, [_i, _vp, _vp, _i, _vp, _sz, _vp, _i, _i, _i, _i, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
     "ifa_moe_plan": (_i, [_vp, _i, _vp, _i]),
     "ifa_pool_rows_plan": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "ifa_model_moe_plan": (_i, [_vp, _i, _i, _i, _vp, _i]),

@@ -258,6 +258,8 @@ static const uint8_t *gm_w(const Tensor &t, int src)
     return (const uint8_t *)(src == GM_W_MO ? t.mo.get() : src == GM_W_X32 ? (t.x32 ? t.x32.get() : t.data.get()) : t.tiled.get());
 }
 
+static bool gm_i8_tensor(const Tensor &t) { return t.present() && t.tiled && (t.dtype == Q4_B32T1A || t.dtype == Q4_B32T1B); }
+
 static GmArgs gm_args(const ifa_model *m, int T, const GmPlan &g, const Tensor &w, const Tensor &bias, const half_t *X, size_t K, half_t *Y, size_t N)
 {
     GmArgs P;
@@ -266,6 +268,9 @@ static GmArgs gm_args(const ifa_model *m, int T, const GmPlan &g, const Tensor &
     P.W[0] = gm_w(w, g.src); P.rows[0] = (int)N; P.nsets = 1; P.nblk = (int)(K / 32);
     P.X = X; P.ldx = (int)K; P.bias[0] = (const half_t *)bias.data.get();
     P.Y = Y; P.ldy = (int)N;
+    // option rows_i8: a rows-GEMM launch of tiled Q4_B32T1 tensors may run k_gemm_rows_i8 from the tiled rows (gm_launch decides)
+    P.i8 = m->opt_rows_i8 && g.kernel == GM_K_ROWS && gm_i8_tensor(w);
+    P.Wt[0] = (const uint8_t *)w.tiled.get();
     return P;
 }
 
@@ -277,6 +282,8 @@ static GmArgs gm_qkv(const ifa_model *m, const Layer &L, int T, const GmPlan &g,
     GmArgs P = gm_args(m, T, g, L.t[T_WQ], L.t[T_WQ_B], x, c.dim, qkv, QD);
     P.W[1] = gm_w(L.t[T_WK], g.src); P.W[2] = gm_w(L.t[T_WV], g.src);
     P.rows[0] = QD; P.rows[1] = KVD; P.rows[2] = KVD; P.nsets = 3;
+    P.i8 = P.i8 && gm_i8_tensor(L.t[T_WK]) && gm_i8_tensor(L.t[T_WV]) && L.t[T_WK].dtype == L.t[T_WQ].dtype && L.t[T_WV].dtype == L.t[T_WQ].dtype;
+    P.Wt[1] = (const uint8_t *)L.t[T_WK].tiled.get(); P.Wt[2] = (const uint8_t *)L.t[T_WV].tiled.get();
     if (norm_fused) { P.norm_w = (const half_t *)L.t[T_ATTN_NORM].data.get(); P.multi_base = c.attn_norm_base; }
     P.bias[1] = (const half_t *)L.t[T_WK_B].data.get(); P.bias[2] = (const half_t *)L.t[T_WV_B].data.get();
     P.ldy = qkv ? QD + 2 * KVD : 0;
@@ -295,6 +302,8 @@ static GmArgs gm_w13(const ifa_model *m, const Layer &L, int T, const GmPlan &g,
 {
     GmArgs P = gm_args(m, T, g, L.t[T_W1], L.t[T_W1_B], norm_fused ? m->a : m->hn, m->cfg.dim, m->t1, m->cfg.ffn);
     P.W1 = gm_w(L.t[T_W3], g.src); P.bias1 = (const half_t *)L.t[T_W3_B].data.get();
+    P.i8 = P.i8 && gm_i8_tensor(L.t[T_W3]) && L.t[T_W3].dtype == L.t[T_W1].dtype;
+    P.Wt1 = (const uint8_t *)L.t[T_W3].tiled.get();
     if (norm_fused) { P.norm_w = (const half_t *)L.t[T_FFN_NORM].data.get(); P.multi_base = m->cfg.ffn_norm_base; }
     return P;
 }
@@ -310,7 +319,11 @@ static GmArgs gm_w2(const ifa_model *m, const Layer &L, int T, const GmPlan &g, 
 // (PromptRoute::res_mid), which the large tiles take then (with the no_waits of the plan that was tried, as ever)
 static int gm_launch(ifa_model *m, const Tensor &w, GmArgs &P, const GmPlan &g, const GmPlan &own, int epi, int norm)
 {
-    if (g.kernel == GM_K_ROWS) return gemm_rows_mfma_launch(P, epi, norm, m->stream);
+    if (g.kernel == GM_K_ROWS) {
+        // rows_i8: the launch in the single-token step's arithmetic where its plan takes the shape; every other launch as ever
+        if (P.i8 && gemm_rows_i8_ok(w.dtype, P, epi, norm)) return gemm_rows_i8_launch(w.dtype, P, epi, norm, m->stream);
+        return gemm_rows_mfma_launch(P, epi, norm, m->stream);
+    }
     if (g.kernel == GM_K_MID) {
         if (gemm_mid_ok(w.dtype, P, epi)) return gemm_mid(P, epi, m->stream);
         if (own.kernel == GM_K_MID) return ifa_fail(IFA_ERR_STATE, "mid-length GEMM declined a product of %zu x %zu", w.rows, w.cols);

@@ -32,6 +32,7 @@
 #include "ifa_decode_gemv.h"
 #include "ifa_moe.h"
 #include "ifa_gemm_rows_mfma.h"
+#include "ifa_gemm_rows_i8.h"
 #include "ifa_gemm_big.h"
 #include "ifa_decode_lmhead_tail.h"
 #include "ifa_decode_singles.h"
@@ -283,6 +284,7 @@ struct ifa_model : Scratch {
     int opt_prefill_mid = 1, opt_prefill_mid_max = 768;
     int opt_prefill_res_mid = 2048;   // prefill_mid_max + 1 .. this many tokens: wo / w2 still through k_gemm_mid, the other products through the large tiles (0: never)
     int opt_rows_kparts = 1, opt_gemm_splitk = 1;   // 0: never the launches whose workgroups wait for partner workgroups (K parts of the 9..32-row GEMM, split-K halves of the large-tile GEMM)
+    int opt_rows_i8 = 0;                       // 1: the rows-GEMM launches of tiled Q4_B32T1 tensors run k_gemm_rows_i8 (ifa_gemm_rows_i8.h): every row is the decode GEMV's arithmetic
     int opt_debug_mo_alloc_fail = 0;           // tests: ensure_mo_build fails like an exhausted allocator after its first copy
     // Memory of the step tails (StepTail above; the tails themselves live on the entry points' stacks).
     // Candidate pools (ifa_engine_pool.hip): the result block (PoolBlock), device / pinned.

@@ -41,6 +41,11 @@ struct GmArgs {
     // gemm_splitk = 0)
     unsigned *wait_err;
     int no_waits;
+    // model option rows_i8 (ifa_gemm_rows_i8.h): every set is a tiled Q4_B32T1 tensor and the launch may run k_gemm_rows_i8 from the
+    // TILED rows Wt[] / Wt1 (W[] / W1 stay what the plan's own kernel reads, e.g. the MO copies)
+    int i8;
+    const uint8_t *Wt[3];
+    const uint8_t *Wt1;
 };
 
 // MO layout ("MFMA operand order") of a matrix [rows][cols] of 4-bit codes with value q * scale + base, cols % 128 == 0: per tile of 16 rows

@@ -124,6 +124,7 @@ bool InferenceEngine::LoadConfig(InferenceConfig &config, const std::string &con
     cfg.GetItem(section, "prefix_cache_min_tokens", config.prefix_cache_min_tokens);
     if (config.prefix_cache_min_tokens < 1) { EngineSetError("prefix_cache_min_tokens must be at least 1 (got %d)", config.prefix_cache_min_tokens); return false; }
     cfg.GetItem(section, "context_shift", config.context_shift);
+    cfg.GetItem(section, "batch_rows_int8", config.batch_rows_int8);
     cfg.GetItem(section, "context_shift_keep", config.context_shift_keep);
     if (config.context_shift_keep < 0) { EngineSetError("context_shift_keep must be at least 0 (got %d)", config.context_shift_keep); return false; }
     cfg.GetItem(section, "batch_generate_round_steps", config.batch_generate_round_steps);

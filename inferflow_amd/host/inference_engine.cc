@@ -83,6 +83,7 @@ bool InferenceEngine::Init(const InferenceConfig &cfg)
     // reference times the host side of its launches for free, here the phases exist as separate launches only on the op-by-op step
     // (worker option perf_stat).  Key 0 (end to end) is filled whenever enable_perf_stat is on, like inference_engine.cc:986-988.
     perf_phases_ = !multi_ && config_.debug.is_study_mode && config_.debug.enable_perf_stat;
+    if (!multi_ && config_.batch_rows_int8 && ifa_model_set_option(model_, "rows_i8", 1) != IFA_OK) { EngineSetError("rows_i8: %s", ifa_last_error()); Clear(); return false; }
     if (perf_phases_ && ifa_model_set_option(model_, "perf_stat", 1) != IFA_OK) { EngineSetError("perf_stat: %s", ifa_last_error()); Clear(); return false; }
     // one KV cache per concurrent query, like the reference's per-query LayerKVCache sets
     kv_slots_ = std::max(1, std::min(config_.max_concurrent_queries, 64));

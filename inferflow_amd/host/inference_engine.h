@@ -146,6 +146,10 @@ struct InferenceConfig {
     // single-device engine with return_output_tensors = false; elsewhere the keys are accepted and the shift stays off (model_info
     // "context_shift" = 0).  QueryOptions::context_shift / context_keep override both per query.
     bool context_shift = false;
+    // extension: batched / draft steps and prompts of 2..32 tokens run their linears in the single-token step's int8 arithmetic
+    // (worker option "rows_i8", docs/rows_gemm_int8.md): a row's result no longer depends on the rows that share its step.  .ini key
+    // batch_rows_int8 = true|false
+    bool batch_rows_int8 = false;
     int context_shift_keep = 4;
     // extension: GenerateBatch.  A round of device-fed batched steps is at most this many steps long (1..256): it bounds the steps
     // a stopped query idles in its round and the wait before the call returns; 32 steps amortise the round's one synchronisation

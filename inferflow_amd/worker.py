@@ -501,6 +501,32 @@ def gemm_rows_plan(T, rows, cols, epi=0, norm=0, mo=1, num_cus=256, visible_cus=
     return d
 
 
+GEMM_ROWS_I8_PLAN = ("error", "token_tiles", "total_rows", "ntiles", "tiles_per_wg", "grid", "lds", "norm_k_max", "row_stride", "tokens_per_wg")
+
+
+def gemm_rows_i8_plan(T, rows, cols, w_dtype=13, epi=0, norm=0, has_w1=1, num_cus=256):
+    """ifa_gemm_rows_i8_plan: the pure launch plan of the int8 rows GEMM (csrc/ifa_gemm_rows_i8_plan.h, no device) as a dict of
+    GEMM_ROWS_I8_PLAN.  rows: the rows of the 1..3 sets; w_dtype: 13 / 14 = Q4_B32T1A / B."""
+    rows = tuple(rows)
+    r3 = rows + (0,) * (3 - len(rows))
+    facts = (C.c_int * 11)(int(T), int(w_dtype), int(cols), len(rows), r3[0], r3[1], r3[2], int(epi), int(norm), int(has_w1), int(num_cus))
+    out = (C.c_int * len(GEMM_ROWS_I8_PLAN))()
+    check(lib().ifa_gemm_rows_i8_plan(facts, 11, out, len(out)))
+    return dict(zip(GEMM_ROWS_I8_PLAN, out))
+
+
+def gemm_rows_q8(w_dtype, wt, rows, cols, x, T, y=None, ldy=0, yset=None, epi=0, norm=0, norm_w=None, multi_base=0.0, eps=1e-5, bias=None,
+                 w1=None, bias1=None, res=None, ldres=0, act_kind=0, ldx=None, num_cus=0, stream=None):
+    """ifa_gemm_rows_q8: the int8 rows GEMM at op level.  wt / bias / yset: sequences of 1..3 device pointers (one per set, bias entries
+    may be None); x, y, res, w1, norm_w: device pointers; num_cus > 0: the CU count the launch is planned for.  Returns the status code (0 = ok)."""
+    n = len(rows)
+    ptrs = lambda seq: (C.c_void_p * 3)(*[(seq[i] if seq is not None and i < len(seq) else None) for i in range(3)])
+    return lib().ifa_gemm_rows_q8(int(w_dtype), ptrs(wt), (C.c_int * 3)(*(tuple(rows) + (0,) * (3 - n))), n, w1, int(cols), x,
+                                  int(cols if ldx is None else ldx), int(T), int(epi), int(norm), norm_w, float(multi_base), float(eps),
+                                  ptrs(bias) if bias is not None else None, bias1, res, int(ldres), int(act_kind), y, int(ldy),
+                                  ptrs(yset) if yset is not None else None, int(num_cus), stream)
+
+
 MOE_FACTS = ("T", "experts", "top_k", "dim", "ffn", "w_dtype", "w_ax8", "w_q4", "full_quant_gemv", "norm_kind", "gate_f16", "gate_cols_match",
              "has_ffn_norm", "experts_uniform", "have_table", "have_table_aos", "have_table_mo", "moe_device", "moe_router_fused", "moe_singles",
              "moe_overlap", "gemm_rows", "rows_mo", "rows_use_mfma", "rows_mfma_ok", "rows_q4_ok", "singles_ok", "caller_norm")
